@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env agent-steps/sec of the HIP step engine (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no torchrun around it launches its own N ranks (one process per
@@ -12,6 +12,10 @@ the workload: PredatorCapturePrey-v0, 4096 envs x 5 agents per GPU (BASELINE.jso
 N GPUs = N x 4096 envs, weak scaling), random policy.  Actions are synthetic (uniform ints,
 seed 1234 + rank) and resident in HBM before the timed region; finished envs are reset inside
 the launch.  Prints ONE JSON line on rank 0.
+
+--dump-outputs DIR writes what the last timed step returned (obs, reward, done, dist_travelled, violation,
+remaining) as DIR/<name>.npy in float32, so that two builds can be compared output for output: the inputs
+(initial states and action batches) depend on the arguments only.
 """
 import argparse
 import json
@@ -28,6 +32,7 @@ PCP_OVERRIDES = {"predator": 3, "capture": 2, "n_agents": 5}   # BASELINE: 5 age
 ALGO_BYTES_PER_ENV_STEP = 585
 # the same for the other BASELINE configurations (Warehouse N=8, D=18; MaterialTransport N=6, D=9)
 ALGO_BYTES_OTHER = {"Warehouse": 896, "MaterialTransport": 510}
+DUMP_MAX_BYTES = 64 * 10**6   # --dump-outputs: at most this much in all (a fixed, seeded sample of envs beyond it)
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8.0 TB/s spec
 F32_MFMA_PEAK_TFLOPS, BF16_MFMA_PEAK_TFLOPS = 157.3, 2500.0   # dense matrix peaks (MI355X_MICROARCH.md; never the 2:1-sparsity figures)
 
@@ -53,6 +58,36 @@ def bench_overrides(scenario):
     if scenario == "MaterialTransport":
         return {"n_agents": 6, "n_fast_agents": 3, "n_slow_agents": 3, "start_dist": 0.25}
     return {}
+
+
+def dump_outputs(env, out_dir, rank, world):
+    """--dump-outputs: the arrays the last step returned to its caller (env.step's obs, reward, done and info), as float32
+    .npy files.  Beyond DUMP_MAX_BYTES the rows of a fixed sample of envs (seed 0, ascending) are written, with their
+    indices in env_index.npy.  With several ranks every rank writes its own shard's files (suffix _rank<r>).
+    Returns the record for the JSON line."""
+    import numpy as np
+    import torch
+    arrays = {"obs": env.obs, "reward": env.reward, "done": env.done_u8, "dist_travelled": env.dist_travelled,
+              "violation": env.violation, "remaining": env.remaining}
+    row_bytes = sum(t[0].numel() for t in arrays.values()) * 4
+    E, budget = env.E, DUMP_MAX_BYTES // world
+    idx = None
+    if E * row_bytes > budget:
+        m = max(1, (budget - 4096) // (row_bytes + 8))   # 8 bytes of env_index per row, 4 KB for the .npy headers
+        idx = np.sort(np.random.RandomState(0).choice(E, m, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    sel = None if idx is None else torch.as_tensor(idx, device=env.device)
+    names = []
+    for name, t in arrays.items():
+        t = t if sel is None else t.index_select(0, sel)
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), t.to(torch.float32).cpu().numpy())
+        names.append(name + suffix)
+    if idx is not None:
+        np.save(os.path.join(out_dir, "env_index" + suffix + ".npy"), idx.astype(np.float64))
+        names.append("env_index" + suffix)
+    return {"dir": out_dir, "arrays": names, "envs": E if idx is None else int(len(idx)), "of_envs": E, "dtype": "float32",
+            "what": "the outputs of the last timed step"}
 
 
 def committed_counters():
@@ -658,8 +693,10 @@ def main():
                     help="how the certificate's QP is evaluated (config key barrier_solver): exact = the projection (the headline); "
                          "cvxopt = the restated interior-point iterate the reference's stack computes (profiling runs of that mode)")
     ap.add_argument("--spinup-ms", type=float, default=1000.0,
-                    help="untimed step launches before reset() + the W warm-up steps, so that a GPU that idled while the host did the CPU "
+                    help="untimed step launches (after which the state reset() made is restored) before the W warm-up steps, so that a GPU that idled while the host did the CPU "
                          "baseline (or while the previous process exited) is at its clocks when the warm-up starts; 0 = none")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (obs, reward, done, info) as DIR/<name>.npy (float32)")
     ap.add_argument("--dist-backend", default=None, help="nccl (default, = RCCL) | gloo (CPU rehearsal of the N>1 path)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal only: every rank uses cuda:0 (a 1-GPU box); never for a measured run")
@@ -667,6 +704,10 @@ def main():
                     help="no GPU work: ranks rendezvous, broadcast the parameter block, shard the envs, gather "
                          "(empty) statistics and print the line with value null -- the N > 1 plumbing on a CPU box")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the GPU run (a --dry-run computes nothing)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))            # this process never touches a GPU
@@ -740,6 +781,9 @@ def main():
     env.reset()
     step = env.step_raw
     if args.spinup_ms > 0:   # not part of W or K: the same launches on scratch state, then the episode starts over
+        # from the state reset() made: the spin-up runs for a time, not a step count, and each episode it finishes moves
+        # the env's sampler on (reset_count), so a second reset() would start from a different state in every run
+        start = env.state_dict()
         t_spin = time.perf_counter()
         i = 0
         while (time.perf_counter() - t_spin) * 1e3 < args.spinup_ms:
@@ -747,7 +791,8 @@ def main():
                 step(ptrs[i % n_batches])
                 i += 1
             torch.cuda.synchronize(dev)
-        env.reset()
+        env.load_state_dict(start)
+        del start
 
     def barrier():
         torch.cuda.synchronize(dev)
@@ -775,6 +820,7 @@ def main():
     elapsed = time.perf_counter() - t0          # this rank's K steps, device-complete
     barrier()
     assert rc == 0
+    dumped = dump_outputs(env, args.dump_outputs, rank, world) if args.dump_outputs else None
     gpu_ms_total = ev0.elapsed_time(ev1)
     # every rank's own clock and its own HIP-event time, so that a slow N-GPU line says WHICH rank was slow (the value is
     # still computed from the max over ranks, as the contract asks)
@@ -833,7 +879,7 @@ def main():
             "config": {"workload": f"{args.scenario}-v0, {E} envs x {N} agents per GPU, random policy, "
                                    f"auto-reset, update_frequency {env.params.update_frequency}, barrier_solver {args.barrier_solver}, "
                                    f"one rg_step launch per env step; "
-                                   f"{args.spinup_ms:g} ms of untimed spin-up launches + reset() before the {W} warm-up steps",
+                                   f"{args.spinup_ms:g} ms of untimed spin-up launches, then the state of reset() restored, before the {W} warm-up steps",
                        "envs_per_gpu": E, "agents": N, "parallelism": f"env-sharded x{world}"},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic,
@@ -855,6 +901,8 @@ def main():
         }
         if collective is not None:
             out["collective"] = collective
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if stats is not None:
             rs, cs, ss = stats
             n_ep = int(cs.sum().item())
