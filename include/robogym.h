@@ -27,12 +27,13 @@
 extern "C" {
 #endif
 
-/* 6 (round 5): rg_scenario_params ends in the barrier-QP solver selection (qp_mode + cvxopt's options): RG_QP_CVXOPT computes the
+/* 7: + rg_policy_rollout() and rg_policy_io (T actor steps and env steps in one launch), rg_sizeof_policy_io().
+ * 6 (round 5): rg_scenario_params ends in the barrier-QP solver selection (qp_mode + cvxopt's options): RG_QP_CVXOPT computes the
  * interior-point iterate the reference's stack computes (utilities/controller.py:13-16,23) instead of the exact projection;
  * rg_step_io.zero_obs_on_end; + rg_actor_forward_explore(), rg_actor_pack_gru_f16x2() and rg_actor_weights.gru_packed == 3.
  * 5 (round 4): + rg_actor_pack_gru_bf16x3() and rg_actor_weights.gru_packed == 2; rg_rollout takes every shape (no E*N*D % 4
  * rule); the one-lane-per-env step kernel covers N <= 6. */
-#define RG_ABI_VERSION 6
+#define RG_ABI_VERSION 7
 #define RG_MAX_AGENTS 16
 #define RG_MAX_PREY 64
 
@@ -298,6 +299,39 @@ int rg_actor_pack_gru_bf16x3(const float *src, int32_t n_sets, int32_t hidden_di
  * the matrix cores take as it is. */
 int rg_actor_pack_gru_f16x2(const float *src, int32_t n_sets, int32_t hidden_dim, void *dst, void *hip_stream);
 const char *rg_actor_last_error(void);
+
+/* ---- policy-in-the-loop rollouts ---------------------------------------------------------------
+ * The evaluation / data-collection loop of misc.py:155-185 (`actor(obs, hs)`, arg-max, env.step; the actor of
+ * utilities/rnn_agent.py:5-29) -- what the actor launch followed by the env step launch computes, T times -- in ONE launch.
+ * Every array is a device pointer; E, N, D, H as above, T = num_steps. */
+typedef struct rg_policy_io {
+    float *hidden;             /* [E][N][H] in/out: the actor's hidden state before the first and after the last time step */
+    const uint8_t *restart;    /* [E] or NULL: nonzero = the env starts a new episode at the first time step (zero observation
+                                  and zero hidden state, as the actor launch's restart flag) */
+    int32_t append_agent_id;   /* the one-hot agent id goes after each observation row */
+    int32_t restart_on_done;   /* later time steps restart an env after the previous step's `done` (nonzero) or its `ended` =
+                                  done | truncated (zero: what a gymma runner does) */
+    const float *explore_u;    /* [T][E][N] or NULL: epsilon-greedy uniforms, the rule of the actor's explore entry point */
+    float epsilon;             /* in [1e-6, 1] when explore_u is given */
+    int32_t *actions;          /* [T][E][N] out (required: the env step reads the actions from here) */
+    float *obs;                /* [T + 1][E][N][D] or NULL: obs[0] is read as the first input, obs[t + 1] receives step t's
+                                  observation (the trainer's batch layout); NULL: the step io's obs, read and rewritten in place */
+    float *reward_sum;         /* [T][E] or NULL (then the step io's reward_sum, rewritten every step) */
+    uint8_t *ended;            /* [T][E] or NULL (then the step io's ended, rewritten every step) */
+    float *dist_sum;           /* [E][N] or NULL: += dist_travelled of every step, float32 additions in step order */
+} rg_policy_io;
+int rg_sizeof_policy_io(void);
+/* num_steps time steps of: the actor for every agent row (the two-binary16-plane GRU, gru_packed == 3, hidden_dim 64 or 128),
+ * its greedy or epsilon-greedy action, one env step with the gymma block (io must carry it: elapsed, truncated, ended,
+ * reward_sum, time_limit; zero_obs_on_end as the caller sets it), the new observation and end flags feeding the next time step.
+ * Replaces the loop body of misc.py:155-185 with utilities/rnn_agent.py:5-29 as the policy.  Results are bit-identical to
+ * alternating the actor launch (restart flags: `restart` first, then the previous step's ended or done flags) and the env step
+ * launch num_steps times; the arrays of io without a leading T hold the last step's values, as they would then.
+ * Envs advance independently (no device-wide synchronisation), auto-reset runs inside the launch.  Refused with a reason in
+ * the last-error text: the interior-point mode (RG_QP_CVXOPT), gru_packed other than 3 or use_rnn = 0, hidden_dim other than
+ * 64 / 128, an input width other than obs_dim (+ n_agents with append_agent_id), num_steps < 1, a missing gymma block. */
+int rg_policy_rollout(rg_handle *h, const rg_actor_weights *w, int32_t num_steps, const rg_policy_io *pio, const rg_step_io *io,
+                      int32_t auto_reset, uint64_t seed);
 
 #ifdef __cplusplus
 }

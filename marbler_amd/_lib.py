@@ -8,7 +8,7 @@ import ctypes as C
 import os
 
 MAX_AGENTS, MAX_PREY = 16, 64
-ABI_VERSION = 6
+ABI_VERSION = 7
 RESET_BOOK_EPISODE = 1
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -80,9 +80,16 @@ class RgActorWeights(C.Structure):
                 ("n_actions", C.c_int32), ("use_rnn", C.c_int32), ("gru_packed", C.c_int32)]
 
 
+class RgPolicyIO(C.Structure):
+    _fields_ = [("hidden", C.c_void_p), ("restart", C.c_void_p), ("append_agent_id", C.c_int32), ("restart_on_done", C.c_int32),
+                ("explore_u", C.c_void_p), ("epsilon", C.c_float), ("actions", C.c_void_p), ("obs", C.c_void_p),
+                ("reward_sum", C.c_void_p), ("ended", C.c_void_p), ("dist_sum", C.c_void_p)]
+
+
 EXPORTS = ("rg_abi_version", "rg_last_error", "rg_sizeof_params", "rg_sizeof_state", "rg_sizeof_step_io", "rg_next_init_stride",
            "rg_create", "rg_destroy", "rg_bind_state", "rg_set_stream", "rg_reset", "rg_step", "rg_rollout", "rg_get_obs", "rg_step_kernel",
-           "rg_actor_forward", "rg_actor_forward_explore", "rg_actor_pack_gru", "rg_actor_pack_gru_bf16x3", "rg_actor_pack_gru_f16x2", "rg_actor_last_error")
+           "rg_actor_forward", "rg_actor_forward_explore", "rg_actor_pack_gru", "rg_actor_pack_gru_bf16x3", "rg_actor_pack_gru_f16x2", "rg_actor_last_error",
+           "rg_sizeof_policy_io", "rg_policy_rollout")
 
 _lib = None
 
@@ -132,13 +139,17 @@ def load():
     lib.rg_actor_pack_gru_f16x2.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.rg_actor_pack_gru_f16x2.restype = C.c_int
     lib.rg_actor_last_error.restype = C.c_char_p
+    lib.rg_policy_rollout.argtypes = [C.c_void_p, C.POINTER(RgActorWeights), C.c_int32, C.POINTER(RgPolicyIO), C.POINTER(RgStepIO),
+                                      C.c_int32, C.c_uint64]
+    lib.rg_policy_rollout.restype = C.c_int
+    lib.rg_sizeof_policy_io.restype = C.c_int
     for f in (lib.rg_destroy, lib.rg_bind_state, lib.rg_set_stream, lib.rg_reset, lib.rg_step, lib.rg_rollout, lib.rg_get_obs,
               lib.rg_sizeof_params, lib.rg_sizeof_state, lib.rg_sizeof_step_io):
         f.restype = C.c_int
     if lib.rg_abi_version() != ABI_VERSION:
         raise RobogymError(f"ABI version {lib.rg_abi_version()} != {ABI_VERSION}; rebuild the library")
     if (lib.rg_sizeof_params() != C.sizeof(RgScenarioParams) or lib.rg_sizeof_state() != C.sizeof(RgState)
-            or lib.rg_sizeof_step_io() != C.sizeof(RgStepIO)):
+            or lib.rg_sizeof_step_io() != C.sizeof(RgStepIO) or lib.rg_sizeof_policy_io() != C.sizeof(RgPolicyIO)):
         raise RobogymError("struct layout of the binding differs from the compiled library; rebuild")
     _lib = lib
     return lib

@@ -171,6 +171,25 @@ __device__ __forceinline__ bool group_any(bool pred, int gbase) {
     return ((m >> gbase) & GM) != 0ull;
 }
 
+// ------------------------------------------------------------------ synchronisation of the step's one wavefront
+// The step and reset code below assumes a ONE-wave workgroup: its barriers make LDS (and the wave's own global stores) visible
+// across the lanes of that wave.  WgSync is what the step kernels use: a workgroup barrier.  WaveSync is the same ordering for a
+// wave that runs the step INSIDE a multi-wave workgroup (rg_policy_rollout: the other waves wait elsewhere), where a workgroup
+// barrier under the wave's own control flow would never be met: the workgroup-scope fences (LDS wait, and whatever the memory
+// model asks for global memory) around a wave barrier.
+struct WgSync {
+    __device__ __forceinline__ static void sync() { __syncthreads(); }
+};
+struct WaveSync {
+    __device__ __forceinline__ static void sync() {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+#ifndef RG_HOST_SIM   // (the host simulation of tests/sanitize runs a wave's lanes as threads: its fences are barriers already)
+        __builtin_amdgcn_wave_barrier();
+#endif
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+};
+
 // ------------------------------------------------------------------ LDS scratch (one wavefront)
 // The step's scratch and the reset sampler's are never live together (the fused reset runs after the step's last LDS
 // read, an explicit reset runs alone), so they share the block: 7.5 KB instead of 13.5 KB per one-wave workgroup --
@@ -216,7 +235,7 @@ __device__ __forceinline__ int normal_int(uint32_t r1, uint32_t r2, float mean, 
 // Partial Fisher-Yates over the grid cells.  The agents' draw and (PredatorCapturePrey) the prey's
 // draw are independent chains, so they run side by side on lanes 0 and 1 of the group, each on its
 // own permutation array (same instructions, different data).
-template <int GW>
+template <int GW, typename Sync = WgSync>
 __device__ __forceinline__ void fisher_yates2(Lds<GW> &lds, int g, int ag, bool do_reset, const rg_grid &grid_a,
                                               int count_a, int first_a, const rg_grid &grid_b, int count_b,
                                               int first_b) {
@@ -227,7 +246,7 @@ __device__ __forceinline__ void fisher_yates2(Lds<GW> &lds, int g, int ag, bool 
         // the permutation array.  Position p holds p unless an earlier step k swapped something into it
         // (j_k == p, value t_k = what position k held then); the latest such step wins.  All in registers:
         // no dependent LDS round trips on the chain.
-        __syncthreads();  // the Philox draws are in LDS
+        Sync::sync();  // the Philox draws are in LDS
         if (do_reset && ag < 2) {
             const int which = ag;
             const int C = which ? Cb : Ca, count = which ? count_b : count_a, first = which ? first_b : first_a;
@@ -252,14 +271,14 @@ __device__ __forceinline__ void fisher_yates2(Lds<GW> &lds, int g, int ag, bool 
                 if (i < count) lds.sel[g][which][i] = static_cast<uint8_t>(sv);
             }
         }
-        __syncthreads();
+        Sync::sync();
         return;
     }
     if (do_reset) {
         for (int i = ag; i < Ca; i += GW) lds.perm[g][0][i] = static_cast<uint8_t>(i);
         for (int i = ag; i < Cb; i += GW) lds.perm[g][1][i] = static_cast<uint8_t>(i);
     }
-    __syncthreads();
+    Sync::sync();
     if (do_reset && ag < 2) {
         const int which = ag;
         const int C = which ? Cb : Ca, count = which ? count_b : count_a, first = which ? first_b : first_a;
@@ -273,7 +292,7 @@ __device__ __forceinline__ void fisher_yates2(Lds<GW> &lds, int g, int ag, bool 
             lds.sel[g][which][i] = pj;
         }
     }
-    __syncthreads();
+    Sync::sync();
 }
 
 // rps: `choices = np.random.choice(x_range * y_range, N, replace=False) + 1`, then `x, y = divmod(c, y_range)`: the
@@ -328,7 +347,7 @@ __device__ __forceinline__ ResetDst reset_dst_next(const KernelArgs &a, int e) {
 
 // episode_pre >= 0: the env's reset_count, already fetched by the caller (the step kernels prefetch it with the rest of
 // the state, so a finished env's reset does not start with a memory round trip of its own)
-template <int SCN, int GW>
+template <int SCN, int GW, typename Sync = WgSync>
 __device__ __forceinline__ void reset_group(const KernelArgs &a, Lds<GW> &lds, int e, int g, int ag, bool do_reset,
                                             int episode_pre, const ResetDst &dst) {
     const rg_scenario_params &p = a.p;
@@ -351,7 +370,7 @@ __device__ __forceinline__ void reset_group(const KernelArgs &a, Lds<GW> &lds, i
                 for (int t = 0; t < 4; ++t) lds.draws[g][4 * b + t] = blk[t];
             }
         }
-        __syncthreads();
+        Sync::sync();
         if (do_reset) {
             const int gc = 1 + static_cast<int>((static_cast<uint64_t>(lds.draws[g][CELLS]) * 11u) >> 32);
             for (int i = ag; i < CELLS; i += GW) {
@@ -401,7 +420,7 @@ __device__ __forceinline__ void reset_group(const KernelArgs &a, Lds<GW> &lds, i
             lds.draws[g][4 * b + 3] = blk[3];
         }
     }
-    fisher_yates2<GW>(lds, g, ag, do_reset, p.agent_grid, N, ZD, p.prey_grid, P, ZD + 2 * N);  // syncs inside
+    fisher_yates2<GW, Sync>(lds, g, ag, do_reset, p.agent_grid, N, ZD, p.prey_grid, P, ZD + 2 * N);  // syncs inside
     if (do_reset && ag < N) {
         float x, y;
         cell_xy(p.agent_grid, lds.sel[g][0][ag], x, y);
@@ -449,10 +468,10 @@ __device__ __forceinline__ void reset_group(const KernelArgs &a, Lds<GW> &lds, i
 }
 
 // the draw straight into the env's state: scenario.reset()
-template <int SCN, int GW>
+template <int SCN, int GW, typename Sync = WgSync>
 __device__ __forceinline__ void reset_group(const KernelArgs &a, Lds<GW> &lds, int e, int g, int ag, bool do_reset,
                                             int episode_pre = -1) {
-    reset_group<SCN, GW>(a, lds, e, g, ag, do_reset, episode_pre, reset_dst_state(a, e));
+    reset_group<SCN, GW, Sync>(a, lds, e, g, ag, do_reset, episode_pre, reset_dst_state(a, e));
 }
 
 }  // namespace rg

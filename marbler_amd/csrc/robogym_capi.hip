@@ -129,6 +129,15 @@ static int check_params(const rg_scenario_params *p) {
     return 0;
 }
 
+// rg_policy_rollout's kernels live in their own translation units (robogym_policy_h64.hip, robogym_policy_h128.hip).  Declared
+// weak: the host-only sanitizer build of this file links without them, and the entry point then refuses to run.
+namespace rg {
+hipError_t launch_policy_rollout_h64(const KernelArgs &, const rg_actor_weights &, const rg_policy_io &, int32_t, hipStream_t)
+    __attribute__((weak));
+hipError_t launch_policy_rollout_h128(const KernelArgs &, const rg_actor_weights &, const rg_policy_io &, int32_t, hipStream_t)
+    __attribute__((weak));
+}  // namespace rg
+
 extern "C" {
 
 int rg_abi_version(void) { return RG_ABI_VERSION; }
@@ -138,6 +147,7 @@ const char *rg_last_error(void) { return g_err; }
 int rg_sizeof_params(void) { return static_cast<int>(sizeof(rg_scenario_params)); }
 int rg_sizeof_state(void) { return static_cast<int>(sizeof(rg_state)); }
 int rg_sizeof_step_io(void) { return static_cast<int>(sizeof(rg_step_io)); }
+int rg_sizeof_policy_io(void) { return static_cast<int>(sizeof(rg_policy_io)); }
 int rg_next_init_stride(const rg_scenario_params *params) {
     if (check_params(params) != 0) return -1;
     return rg::next_init_stride(*params);
@@ -338,6 +348,41 @@ int rg_rollout(rg_handle *h, const int32_t *actions, int32_t num_steps, const rg
         if (int rc = launched(rg::launch_step_tpe(ak, h->stream))) return rc;
     }
     return 0;
+}
+
+int rg_policy_rollout(rg_handle *h, const rg_actor_weights *w, int32_t num_steps, const rg_policy_io *pio, const rg_step_io *io,
+                      int32_t auto_reset, uint64_t seed) {
+    rg::KernelArgs a;
+    if (int rc = fill_args(h, a)) return rc;
+    if (!w || !pio || !io) return fail(-23, "weights, policy io or step io is NULL");
+    if (num_steps < 1) return fail(-27, "num_steps < 1");
+    if (h->params.qp_mode == RG_QP_CVXOPT) return fail(-40, "rg_policy_rollout: the interior-point mode (barrier_solver: cvxopt) is not supported");
+    if (!w->use_rnn || w->gru_packed != 3)
+        return fail(-41, "rg_policy_rollout: the actor must be a GRU with gru_packed == 3 (two binary16 planes, pack_gru='f16x2')");
+    if (w->hidden_dim != 64 && w->hidden_dim != 128) return fail(-42, "rg_policy_rollout: hidden_dim must be 64 or 128");
+    const int N = h->params.n_agents;
+    if (w->n_sets != 1 && w->n_sets != N) return fail(-43, "rg_policy_rollout: n_sets must be 1 (shared) or n_agents");
+    if (w->input_dim != h->params.obs_dim + (pio->append_agent_id ? N : 0))
+        return fail(-44, "rg_policy_rollout: the actor's input_dim != obs_dim (+ n_agents with append_agent_id)");
+    if (w->input_dim > 64) return fail(-44, "rg_policy_rollout: input_dim above 64 is not supported");
+    if (w->n_actions < 1 || w->n_actions > 32) return fail(-45, "rg_policy_rollout: n_actions must be in 1..32");
+    if (!w->w1 || !w->b1 || !w->wih || !w->bih || !w->whh || !w->bhh || !w->w2 || !w->b2) return fail(-46, "rg_policy_rollout: a weight array is NULL");
+    if (!pio->hidden || !pio->actions) return fail(-47, "rg_policy_rollout: hidden and actions are required");
+    if ((reinterpret_cast<uintptr_t>(pio->hidden) | reinterpret_cast<uintptr_t>(pio->obs) | reinterpret_cast<uintptr_t>(w->w1) |
+         reinterpret_cast<uintptr_t>(w->wih) | reinterpret_cast<uintptr_t>(w->whh) | reinterpret_cast<uintptr_t>(w->w2)) & 15u)
+        return fail(-26, "rg_policy_rollout: hidden, obs, w1, wih, whh and w2 must be 16-byte aligned");
+    if (pio->explore_u && !(pio->epsilon >= 1e-6f && pio->epsilon <= 1.0f)) return fail(-48, "rg_policy_rollout: epsilon must be in [1e-6, 1] with explore_u");
+    if (!io->elapsed) return fail(-29, "rg_policy_rollout: the step io must carry the gymma block (elapsed, truncated, ended, reward_sum)");
+    if (int rc = check_io(io)) return rc;
+    auto launch = w->hidden_dim == 64 ? rg::launch_policy_rollout_h64 : rg::launch_policy_rollout_h128;
+    if (!launch) return fail(-100, "rg_policy_rollout: this build has no device code");
+    a.io = *io;
+    a.auto_reset = auto_reset;
+    a.seed = seed;
+    a.next_stride = 0;   // AHEAD = false inside the launch, as in rg_rollout
+    RG_ON_DEVICE(h);
+    if (int rc = sync_seed(h, seed)) return rc;
+    return launched(launch(a, *w, *pio, num_steps, h->stream));
 }
 
 int rg_step_kernel(const rg_handle *h) {

@@ -312,7 +312,9 @@ __device__ __forceinline__ void write_neighbour_obs(Lds<GW> &lds, int N, int Knb
 // the launch costs the MEAN wavefront, and drawing ahead moves the sampler's work without removing any.
 // GYM: the gymma block of rg_step_io (gym's TimeLimit + reductions) is compiled in.  Its own instantiations (generic agent
 // count, single-step launch): the benchmark kernels carry none of it.
-template <int SCN, int GW, bool OBS_ONLY, int NT, bool AHEAD, bool GYM, int QPM = 0, typename QpLds = void>
+// Sync: how the wave's lanes meet (device_common.h): WgSync in the step kernels (one-wave workgroups), WaveSync where the step
+// runs on one wave of a larger workgroup (policy_rollout.h): every barrier below sits under the wave's own control flow.
+template <int SCN, int GW, bool OBS_ONLY, int NT, bool AHEAD, bool GYM, int QPM = 0, typename QpLds = void, typename Sync = WgSync>
 __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, const StepView &sv, QpLds *qp_lds = nullptr) {
     constexpr int EPW = WAVE / GW;  // envs per wave
     RG_STAMPS_BEGIN()
@@ -780,7 +782,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     if constexpr (SCN == RG_SCN_PREDATOR_CAPTURE_PREY) {
         const int P = q_P;
         const float sr2 = sr * sr, cr2 = cr * cr;
-        if (P > 8) __syncthreads();  // LDS prey block visible (single-wave workgroup: waitcnt + s_barrier)
+        if (P > 8) Sync::sync();  // LDS prey block visible (single-wave workgroup: waitcnt + s_barrier)
         if (P <= 8) {  // the flag bytes fetched in the prologue -> bit masks of the env
             RG_LATE(flag_raw[0]);
             RG_LATE(flag_raw[1]);
@@ -905,7 +907,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         lds.own[lane][3] = qy;
         lds.own[lane][4] = sr;
         lds.own[lane][5] = cr;
-        __syncthreads();
+        Sync::sync();
         if (od == 6) {
             if (lane_ok) {
 #pragma unroll
@@ -940,7 +942,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         lds.own[lane][0] = x;
         lds.own[lane][1] = y;
         lds.own[lane][2] = loaded ? 1.0f : 0.0f;
-        __syncthreads();
+        Sync::sync();
         if (lane_ok) {
             obs_row[0] = x;
             obs_row[1] = y;
@@ -971,7 +973,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     } else if constexpr (SCN == RG_SCN_SIMPLE) {  // scenarios/Simple/simple.py:155-225
         lds.own[lane][0] = x;
         lds.own[lane][1] = y;
-        __syncthreads();
+        Sync::sync();
         if (lane_ok) {
             obs_row[0] = x;
             obs_row[1] = y;
@@ -996,7 +998,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
 #pragma unroll
             for (int t = 0; t < 6; ++t) gdst[ag * 6 + t] = grid_pre[t];
         }
-        __syncthreads();
+        Sync::sync();
         const uint8_t *grid = &lds.grid[g][0];
         // get_cell_from_pose: int() truncates toward zero; /0.25 is exact
         int row = -static_cast<int>((y - 1.0f) / 0.25f), col = static_cast<int>((x + 1.5f) / 0.25f);
@@ -1011,7 +1013,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         lds.own[lane][1] = y;
         lds.own[lane][2] = static_cast<float>(here);
         lds.aload[lane] = row * 16 + col;
-        __syncthreads();
+        Sync::sync();
         const float goalx = static_cast<float>(goal_col) * 0.25f - 1.5f, goaly = -1.0f * 0.25f + 0.75f;
         if (lane_ok) {
             obs_row[0] = x;
@@ -1051,7 +1053,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             const float dx = x - goalx, dy = y - goaly;
             lds.ax[lane] = dx * dx + dy * dy;
             lds.ay[lane] = static_cast<float>(pix * 2 + reached);
-            __syncthreads();
+            Sync::sync();
             if (viol) {
                 reward = p.violation_reward;
                 done = true;
@@ -1097,7 +1099,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             lds.ax[lane] = x;
             lds.ay[lane] = y;
             lds.aload[lane] = load;
-            __syncthreads();
+            Sync::sync();
             if (viol) {
                 reward = p.violation_reward;
                 done = true;
@@ -1147,7 +1149,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             int total = 0;
             {   // info['remaining'] = zone loads + agent loads (after the update)
                 lds.aload[lane] = lane_ok ? load : 0;
-                __syncthreads();
+                Sync::sync();
                 for (int j = 0; j < N; ++j) total += lds.aload[gbase + j];
             }
             if (done) remaining = zone0 + zone1 + total;
@@ -1173,9 +1175,9 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         // sum of the agents' rewards in agent order (read when shared_reward == 0, and by the gymma block)
         float rsum = 0.0f;
         if ((stats && !p.shared_reward) || gym) {
-            __syncthreads();
+            Sync::sync();
             lds.ax[lane] = lane_ok ? reward : 0.0f;
-            __syncthreads();
+            Sync::sync();
             for (int j = 0; j < N; ++j) rsum = rsum + lds.ax[gbase + j];
         }
         // ---- stores
@@ -1226,9 +1228,9 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         // ---- fused auto-reset of finished envs (scenario.reset(); ~1 env in 70 per step)
         // an env whose block holds exactly the episode that starts now copies it; any other runs the sampler
         if (a.auto_reset && __any(env_ok & ended)) {
-            __syncthreads();  // the wave's state stores are issued before the resetting lanes rewrite them
+            Sync::sync();  // the wave's state stores are issued before the resetting lanes rewrite them
             if constexpr (AHEAD) load_next(env_ok & ended & have_next & !next_early);  // ended some other way: fetched late
-            if (__any(env_ok & ended & !have_next)) reset_group<SCN, GW>(a, lds, e, g, ag, env_ok & ended & !have_next, rc_raw);
+            if (__any(env_ok & ended & !have_next)) reset_group<SCN, GW, Sync>(a, lds, e, g, ag, env_ok & ended & !have_next, rc_raw);
             if (env_ok & ended & have_next) {  // the same stores reset_group makes with commit = true
                 if (ag < N) {
                     float *X = a.st.poses + eN * 3;
@@ -1280,8 +1282,8 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         // before): the draw must not lengthen the waves the launch is waiting for.
         if (AHEAD && ahead && !(replayed | __any(max_sweeps > 2)) && __any(env_ok & !ended & !have_next)) {
             const bool need = env_ok & !ended & !have_next;
-            __syncthreads();  // (LDS scratch of a reset above is free again)
-            reset_group<SCN, GW>(a, lds, e, g, ag, need, rc_raw, reset_dst_next(a, e));
+            Sync::sync();  // (LDS scratch of a reset above is free again)
+            reset_group<SCN, GW, Sync>(a, lds, e, g, ag, need, rc_raw, reset_dst_next(a, e));
             if (need && ag == 0) a.st.next_episode[e] = rc_raw;
         }
         RG_STAMP(6);  // reset done

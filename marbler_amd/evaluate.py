@@ -156,6 +156,42 @@ class BatchedActor(object):
         return q_out, actions_out
 
 
+def policy_rollout(env, actor, T, io, hidden, actions, restart=None, append_agent_id=True, restart_on_done=False, explore_u=None,
+                   epsilon=0.0, obs=None, reward_sum=None, ended=None, dist_sum=None):
+    """rg_policy_rollout: T time steps of actor -> action -> env step in ONE launch on the env's handle (csrc/policy_rollout.h).
+    env: a VecRobotariumEnv; io: the rg_step_io it steps with (it must carry the gymma block); the tensors are device tensors in
+    the layouts of include/robogym.h rg_policy_io (None = NULL).  Raises ValueError for a configuration the launch refuses."""
+    import ctypes as C
+    from . import _lib
+    lib = _lib.load()
+    if int(env.params.qp_mode) != 0:
+        raise ValueError("one launch: the interior-point mode (barrier_solver: cvxopt) is not supported")
+    if not (actor.use_rnn and actor.pack_gru == "f16x2"):
+        raise ValueError("one launch: the actor must be a GRU packed as two binary16 planes (pack_gru=True / 'f16x2')")
+    if actor.hidden_dim not in (64, 128):
+        raise ValueError("one launch: hidden size must be 64 or 128")
+    in_dim = env.D + (env.N if append_agent_id else 0)
+    if in_dim != actor.input_dim:
+        raise ValueError(f"one launch: the actor expects {actor.input_dim} inputs per agent, the env provides {in_dim}")
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    if explore_u is not None and (explore_u.dtype != torch.float32 or not explore_u.is_contiguous()):
+        raise ValueError("explore_u must be a contiguous float32 [T, E, N] tensor")
+    env._sync_stream()   # the handle launches on torch's current stream
+    ws = actor._weights_struct()
+    ev = getattr(actor, "_pack_done", None)
+    if ev is not None:   # the weights were packed (once) on the then-current stream: order this stream behind them
+        if ev.query():
+            actor._pack_done = None
+        else:
+            torch.cuda.current_stream(env.device).wait_event(ev)
+    pio = _lib.RgPolicyIO(ptr(hidden), ptr(restart), 1 if append_agent_id else 0, 1 if restart_on_done else 0, ptr(explore_u),
+                          float(epsilon), ptr(actions), ptr(obs), ptr(reward_sum), ptr(ended), ptr(dist_sum))
+    rc = lib.rg_policy_rollout(env._h, C.byref(ws), int(T), C.byref(pio), C.byref(io), 1 if env.auto_reset else 0, env.seed)
+    if rc != 0:
+        msg = f"rg_policy_rollout ({rc}): {lib.rg_last_error().decode()}"
+        raise (_lib.RobogymError if rc <= -30 and rc > -40 or rc == -100 else ValueError)(msg)
+
+
 def explore_select(greedy, u, epsilon, n_actions, out=None):
     """The epsilon-greedy rule of rg_actor_forward_explore in torch ops (the composed runner path and the tests use it): with
     k = int(u * (n_actions / epsilon)) in float32, the action is k where k < n_actions (u < epsilon; k uniform), else greedy."""
@@ -174,7 +210,7 @@ def load_actor(model_file, model_config, n_agents, device="cuda:0"):
 
 
 @torch.no_grad()
-def run_eval(env, actor, steps, obs_agent_id=True, use_graph=False, fused=None):
+def run_eval(env, actor, steps, obs_agent_id=True, use_graph=False, fused=None, one_launch=False):
     """Greedy rollout of `actor` on a VecRobotariumEnv (auto_reset on) for `steps` env steps.
     Mirrors run_env's per-step body (misc.py:160-172): optional one-hot agent id appended to the
     observation, actor forward, arg-max, env.step; hidden states restart at zero with each episode.
@@ -185,7 +221,10 @@ def run_eval(env, actor, steps, obs_agent_id=True, use_graph=False, fused=None):
     replay is one launch per step.  Same arithmetic, same results.
     fused (default: when the actor's shape allows): the whole policy step in one launch of the MFMA
     kernel (csrc/actor_mfma.hip) -- an iteration is then three launches (actor, env step, distance
-    sum); float32 like the torch path, sums in a different order (action values agree to 1e-5)."""
+    sum); float32 like the torch path, sums in a different order (action values agree to 1e-5).
+    one_launch: the fused loop with the actor and the env step inside ONE launch per (up to) 64 steps (rg_policy_rollout):
+    the same statistics as fused=True bit for bit, and the env left in the same state.  Needs an actor packed as two binary16
+    planes and the exact barrier QP; anything else raises ValueError."""
     E, N = env.E, env.N
     dev = env.device
     eye = torch.eye(N, device=dev).unsqueeze(0).expand(E, N, N)
@@ -208,6 +247,32 @@ def run_eval(env, actor, steps, obs_agent_id=True, use_graph=False, fused=None):
         hidden.copy_(torch.where(keep, h, 0.0))
         obs_in.copy_(torch.where(keep, obs, 0.0))   # a finished env restarts from the reference's reset() observation (zeros)
 
+    if one_launch:
+        from . import _lib
+        if use_graph:
+            raise ValueError("one_launch and use_graph are two different ways to cut launches: pick one")
+        if env.elapsed is None:   # the launch always runs the gymma block: give it a TimeLimit that never fires
+            io = _lib.RgStepIO.from_buffer_copy(env._io)
+            scratch = [torch.zeros(E, dtype=torch.int32, device=dev), torch.zeros(E, dtype=torch.uint8, device=dev),
+                       torch.zeros(E, dtype=torch.uint8, device=dev), torch.zeros(E, device=dev)]
+            io.elapsed, io.truncated, io.ended, io.reward_sum = (t.data_ptr() for t in scratch)
+            io.time_limit = 2 ** 31 - 1
+        else:
+            io = env._io
+        chunk = min(int(steps), 64)
+        act = torch.empty(chunk, E, N, dtype=torch.int32, device=dev)
+        done = 0
+        while done < steps:
+            k = min(chunk, steps - done)
+            # like the fused loop: the actor reads env.obs and restarts after env.done_u8, the step rewrites both
+            policy_rollout(env, actor, k, io, hidden, act, restart=env.done_u8, append_agent_id=obs_agent_id, restart_on_done=True,
+                           dist_sum=dist)
+            done += k
+        torch.cuda.synchronize(dev)
+        ret_sum, episodes, ep_steps = env.episode_stats()
+        n = max(int(episodes), 1)
+        return {"episodes": int(episodes), "mean_return": float(ret_sum) / n, "mean_steps": float(ep_steps) / n,
+                "mean_dist_per_step": float(dist.sum()) / (steps * E * N)}
     if fused is None:
         fused = actor.fused_supported()
     if fused:

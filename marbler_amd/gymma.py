@@ -21,7 +21,7 @@ single-env form with EPyMARL's Python types, for dropping into an unmodified EPy
 import numpy as np
 import torch
 
-from .evaluate import explore_select
+from .evaluate import explore_select, policy_rollout
 from .vec_env import VecRobotariumEnv
 
 N_ACTIONS = {"PredatorCapturePrey": 5, "Warehouse": 5, "MaterialTransport": 20, "Simple": 5, "ArcticTransport": 5}
@@ -252,12 +252,15 @@ class BatchedRunner(object):
         venv.reset()
 
     @torch.no_grad()
-    def run(self, T):
+    def run(self, T, one_launch=False):
         """With the fused env step and the fused actor a time step is TWO launches, with exploration too: the actor reads the
         previous step's episode-end flags and observation straight from the batch and writes its (epsilon-)greedy actions into it; the env step reads
         those actions and writes the next observation (zeros for an env that ended: the reset observation), the summed reward
         and the episode-end flags into the batch (VecRobotariumEnv.step_into).  `state` is a view of `obs` ([E, N * D] of the
-        same memory: gymma's state IS the concatenated observations); `episode_start` is filled once per call."""
+        same memory: gymma's state IS the concatenated observations); `episode_start` is filled once per call.
+        one_launch: the whole collection in ONE launch (rg_policy_rollout: the actor and the env step alternate inside it, the
+        hidden state resident on the CU) -- the same dict, hidden state and env state bit for bit.  Needs the fused env and an
+        actor packed as two binary16 planes; anything else raises ValueError instead of falling back."""
         v, env, dev = self.venv, self.venv.env, self.venv.env.device
         E, N, D, A = v.E, v.n_agents, v.obs_size, v.n_actions
         if int(T) < 1:
@@ -273,13 +276,20 @@ class BatchedRunner(object):
         eps = self.epsilon
         # exploration: ONE uniform per agent and time step, drawn for the whole call in one launch (evaluate.explore_select is the rule)
         u_all = torch.rand(T, E, N, generator=self.gen, device=dev) if eps > 0.0 else None
+        if one_launch and not direct:
+            raise ValueError("one_launch needs a fused GymmaVecEnv and an actor the fused kernel supports "
+                             "(hidden size 64 / 128, at most 32 actions and 64 inputs)")
         if direct:
             out["state"] = out["obs"].view(T + 1, E, N * D)
             out["obs"][0] = v.get_obs()            # zeros right after a reset, like the reference's reset()
             out["episode_start"][0] = self._restart.view(torch.bool)
             term_u8 = out["terminated"].view(torch.uint8)
             env._sync_stream()
-            for t in range(T):
+            if one_launch:
+                policy_rollout(env, self.actor, T, env._io_into, self.hidden, out["actions"], restart=self._restart,
+                               append_agent_id=self.obs_agent_id, explore_u=u_all, epsilon=eps, obs=out["obs"],
+                               reward_sum=out["reward"], ended=term_u8)
+            for t in range(0 if one_launch else T):
                 obs = out["obs"][t]
                 restart = self._restart if t == 0 else term_u8[t - 1]
                 self.actor.forward_fused(obs, self.hidden, append_agent_id=self.obs_agent_id, restart=restart, q_out=self._q,
