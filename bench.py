@@ -1,11 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- env agent-steps/sec of the HIP step engine (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no torchrun around it launches its own N ranks (one process per
 GPU, backend nccl = RCCL; the parent never touches a GPU) and relays rank 0's line.
+
+A plain run does what the headline needs and no more: set up, spin up, warm up, time the K steps, dump the outputs
+(if asked) and print the line.  --full adds everything measured beside it: the CPU baseline, the live rocprofv3
+counter passes, the per-launch event-pair roofline probe and the side legs (graph replay, rg_rollout, host boundary,
+saturated batches, actor, interior-point mode).  None of them enters `value`.
 
 One "step" = one rg_step launch = one env step (U = 29 sim sub-iterations) of every env of
 the workload: PredatorCapturePrey-v0, 4096 envs x 5 agents per GPU (BASELINE.json configs[1];
@@ -683,10 +688,13 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--envs-per-gpu", type=int, default=ENVS_PER_GPU)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-saturated", action="store_true", help="skip the 524288-env side measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what is measured beside the headline: CPU baseline, live counter passes, per-launch roofline "
+                         "probe, side legs (off by default: a plain run times the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the live counter passes")
+    ap.add_argument("--no-saturated", action="store_true", help="with --full: skip the side legs")
     ap.add_argument("--no-graph", action="store_true",
-                    help="skip the graph_replay side measurement (profiling runs: its launches would mix into the headline kernel's row)")
+                    help="with --full: skip the graph_replay side measurement (profiling runs: its launches would mix into the headline kernel's row)")
     ap.add_argument("--counters-child", action="store_true", help=argparse.SUPPRESS)   # a rocprofv3 --pmc pass of live_counters()
     ap.add_argument("--scenario", default="PredatorCapturePrey")
     ap.add_argument("--barrier-solver", default="exact", choices=("exact", "cvxopt"),
@@ -727,7 +735,7 @@ def main():
         return counters_child(args)
     cpu_ref = None
     live, live_src = {}, None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline and not args.dry_run:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline and not args.dry_run:
         cpu_ref = cpu_baseline()
         if args.scenario == "PredatorCapturePrey" and args.envs_per_gpu == ENVS_PER_GPU and args.gpus == 1 and args.barrier_solver == "exact":
             live, live_src = live_counters(args)   # (also before this process touches the GPU)
@@ -832,17 +840,19 @@ def main():
         per_rank = [[float(v[0]), float(v[1])] for v in everyone]
         elapsed = max(v[0] for v in per_rank) * K * 1e-3
 
-    # ---- roofline leg: the same launches with a HIP event pair around each (stream = the launch stream)
-    n_probe = min(K, 300)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_probe)]
-    for i, (a, b) in enumerate(evs):
-        a.record()
-        step(ptrs[i % n_batches])
-        b.record()
-    torch.cuda.synchronize(dev)
-    durs = sorted(a.elapsed_time(b) for a, b in evs)
-    kernel_ms = sum(durs) / len(durs)
-    kernel_ms_median = durs[len(durs) // 2]
+    # ---- roofline leg (--full): the same launches with a HIP event pair around each (stream = the launch stream)
+    probe = {}
+    if args.full:
+        n_probe = min(K, 300)
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_probe)]
+        for i, (a, b) in enumerate(evs):
+            a.record()
+            step(ptrs[i % n_batches])
+            b.record()
+        torch.cuda.synchronize(dev)
+        durs = sorted(a.elapsed_time(b) for a, b in evs)
+        probe = {"kernel_ms_avg_event_pair_per_launch": sum(durs) / len(durs),
+                 "kernel_ms_median_event_pair_per_launch": durs[len(durs) // 2]}
 
     # episode statistics gathered to rank 0 (RCCL all_gather over xGMI when world > 1)
     stats = rgdist.gather_episode_stats(env.done_return_sum, env.done_count, env.done_steps_sum, dst=0, total_envs=world * E)
@@ -875,7 +885,7 @@ def main():
             "metric": "env agent-steps/sec", "value": value, "unit": "agent-steps/s", "n_gpus": world,
             "steps": K, "warmup": W, "spinup_ms": args.spinup_ms, "ms_per_step": elapsed / K * 1e3, "higher_is_better": True,
             "per_rank_ms_per_step": [round(v[0], 6) for v in per_rank], "per_rank_kernel_ms_per_step": [round(v[1], 6) for v in per_rank],
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": f"{args.scenario}-v0, {E} envs x {N} agents per GPU, random policy, "
                                    f"auto-reset, update_frequency {env.params.update_frequency}, barrier_solver {args.barrier_solver}, "
                                    f"one rg_step launch per env step; "
@@ -893,8 +903,7 @@ def main():
                                     if env.step_kernel == "group"
                                     else f"rg::tpe::step_kernel<{args.scenario},N={N}> (one lane per env)"),
                          "kernel_ms_avg": gpu_ms_total / K,   # HIP events around the timed region / K (back-to-back launches)
-                         "kernel_ms_avg_event_pair_per_launch": kernel_ms,
-                         "kernel_ms_median_event_pair_per_launch": kernel_ms_median,
+                         **probe,
                          "algorithmic_bytes_per_launch": bytes_per_launch,
                          "note": "latency/VALU-bound fused step (~120 flop/B): HBM fraction is structurally tiny, "
                                  "see DESIGN.md"},
@@ -909,7 +918,7 @@ def main():
             out["episodes"] = {"finished": n_ep,
                                "mean_return": float(rs.sum().item() / max(n_ep, 1)),
                                "mean_length": float(ss.sum().item() / max(n_ep, 1))}
-        if world == 1 and not args.no_saturated and args.scenario == "PredatorCapturePrey" and args.barrier_solver == "exact":
+        if args.full and world == 1 and not args.no_saturated and args.scenario == "PredatorCapturePrey" and args.barrier_solver == "exact":
             if not args.no_graph:
                 out["graph_replay"] = graph_leg(env, dev, ptrs, min(K, 100))
             out["rollout"] = rollout_leg(env, dev, n_act, 777)

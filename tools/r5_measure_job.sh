@@ -30,7 +30,7 @@ prof() {  # name, bench args ...: bench line, kernel trace, three PMC passes of 
 
 if has headline; then
   # the full default line (cpu baseline, saturated legs, actor leg) once, then the profiled command (no side legs in the trace)
-  timeout -k 10 500 python3 bench.py > $OUT/final_bench.json 2> $OUT/final_bench.err || { tail -5 $OUT/final_bench.err; exit 2; }
+  timeout -k 10 500 python3 bench.py --full > $OUT/final_bench.json 2> $OUT/final_bench.err || { tail -5 $OUT/final_bench.err; exit 2; }
   python3 -c "
 import json
 d = json.loads(open('$OUT/final_bench.json').read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ TAG=${1:-stall}
 SET=${2:-sq}
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python3 bench.py --steps 300 --warmup 50 --no-cpu-baseline"
+BENCH="python3 bench.py --full --steps 300 --warmup 50 --no-cpu-baseline"
 pass() {
   local name=$1; shift
   timeout -k 10 100 rocprofv3 --pmc "$@" -d $OUT/$name -o p -- $BENCH > $OUT/$name.log 2>&1
