@@ -27,7 +27,8 @@
 extern "C" {
 #endif
 
-/* 7: + rg_policy_rollout() and rg_policy_io (T actor steps and env steps in one launch), rg_sizeof_policy_io().
+/* 7: + rg_policy_rollout() and rg_policy_io (T actor steps and env steps in one launch), rg_sizeof_policy_io(); later, purely
+ * additive (no existing layout or entry point changed): + rg_set_lidar(), rg_lidar_params, rg_sizeof_lidar_params().
  * 6 (round 5): rg_scenario_params ends in the barrier-QP solver selection (qp_mode + cvxopt's options): RG_QP_CVXOPT computes the
  * interior-point iterate the reference's stack computes (utilities/controller.py:13-16,23) instead of the exact projection;
  * rg_step_io.zero_obs_on_end; + rg_actor_forward_explore(), rg_actor_pack_gru_f16x2() and rg_actor_weights.gru_packed == 3.
@@ -244,6 +245,32 @@ int rg_get_obs(rg_handle *h, float *obs);
  * query exists so that tests and profiles can say which one ran.  Negative: error. */
 int rg_step_kernel(const rg_handle *h);
 
+/* ---- lidar range observation (opt-in; out of parity scope: the reference has no lidar) --------------------------------
+ * With rays > 0, every observation row the handle writes (rg_step, rg_rollout, rg_get_obs) carries `rays` floats at columns
+ * offset .. offset + rays - 1 = obs_dim - 1, after the scenario's own columns.  Ray k of an agent at pose (x, y, theta) points
+ * along (cos theta, sin theta) rotated by (dir[k][0], dir[k][1]) = binary32(cos, sin of 2 pi k / rays): ray 0 straight ahead,
+ * counter-clockwise.  Its range t is the smallest positive distance from the robot's centre to the disk (radius
+ * robot_diameter / 2) of another robot of the same env, or to a wall of the arena [bound_x0, bound_x0 + bound_w] x
+ * [bound_y0, bound_y0 + bound_h]; the value stored is min(t, range) / range: exactly 1 when nothing lies within range, 0 when the
+ * centre lies inside another robot's disk, 0 on every ray of an agent whose centre lies outside the arena.  A row the
+ * engine zeroes (zero_obs_on_end) is zero in the lidar columns too.
+ * Layout: 16 + 256 bytes, no padding; checked against the binding with rg_sizeof_lidar_params(). */
+#define RG_LIDAR_MAX_RAYS 32
+typedef struct rg_lidar_params {
+    int32_t rays;                        /* R: 0 (off) or a multiple of 4 in 4..32 */
+    int32_t offset;                      /* first lidar column: >= the scenario's own width, offset + rays == obs_dim */
+    float range;                         /* L in metres: > 0, finite */
+    float inv_range;                     /* binary32(1 / L) */
+    float dir[RG_LIDAR_MAX_RAYS][2];     /* rows 0 .. rays - 1: the direction table above */
+} rg_lidar_params;
+int rg_sizeof_lidar_params(void);
+/* Turns the lidar on for every later launch of the handle (lp->rays > 0), or off (lp NULL or lp->rays == 0: the default kernel
+ * choice comes back).  With the lidar on the handle steps with the lane-group kernel at every batch size (rg_step_kernel()
+ * reports 0) and rg_policy_rollout refuses it.  Errors: -1 NULL handle, -50 rays not a multiple of 4 in 4..32, -51
+ * offset + rays != obs_dim, -52 offset below the scenario's own width, -53 range not positive and finite, -100 a build without
+ * the lidar kernels. */
+int rg_set_lidar(rg_handle *h, const rg_lidar_params *lp);
+
 /* ---- policy inference for evaluation rollouts ------------------------
  * The EPyMARL recurrent actor the reference evaluates with (utilities/rnn_agent.py:5-29 `RNNAgent`:
  * fc1 -> ReLU -> GRUCell -> fc2; utilities/rnn_ns_agent.py:5-36 `RNNNSAgent`: one per agent), for all
@@ -329,7 +356,8 @@ int rg_sizeof_policy_io(void);
  * launch num_steps times; the arrays of io without a leading T hold the last step's values, as they would then.
  * Envs advance independently (no device-wide synchronisation), auto-reset runs inside the launch.  Refused with a reason in
  * the last-error text: the interior-point mode (RG_QP_CVXOPT), gru_packed other than 3 or use_rnn = 0, hidden_dim other than
- * 64 / 128, an input width other than obs_dim (+ n_agents with append_agent_id), num_steps < 1, a missing gymma block. */
+ * 64 / 128, an input width other than obs_dim (+ n_agents with append_agent_id), num_steps < 1, a missing gymma block, a handle
+ * with the lidar on (-49). */
 int rg_policy_rollout(rg_handle *h, const rg_actor_weights *w, int32_t num_steps, const rg_policy_io *pio, const rg_step_io *io,
                       int32_t auto_reset, uint64_t seed);
 

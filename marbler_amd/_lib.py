@@ -86,10 +86,18 @@ class RgPolicyIO(C.Structure):
                 ("reward_sum", C.c_void_p), ("ended", C.c_void_p), ("dist_sum", C.c_void_p)]
 
 
+LIDAR_MAX_RAYS = 32
+
+
+class RgLidarParams(C.Structure):
+    _fields_ = [("rays", C.c_int32), ("offset", C.c_int32), ("range", C.c_float), ("inv_range", C.c_float),
+                ("dir", (C.c_float * 2) * LIDAR_MAX_RAYS)]
+
+
 EXPORTS = ("rg_abi_version", "rg_last_error", "rg_sizeof_params", "rg_sizeof_state", "rg_sizeof_step_io", "rg_next_init_stride",
            "rg_create", "rg_destroy", "rg_bind_state", "rg_set_stream", "rg_reset", "rg_step", "rg_rollout", "rg_get_obs", "rg_step_kernel",
            "rg_actor_forward", "rg_actor_forward_explore", "rg_actor_pack_gru", "rg_actor_pack_gru_bf16x3", "rg_actor_pack_gru_f16x2", "rg_actor_last_error",
-           "rg_sizeof_policy_io", "rg_policy_rollout")
+           "rg_sizeof_policy_io", "rg_policy_rollout", "rg_sizeof_lidar_params", "rg_set_lidar")
 
 _lib = None
 
@@ -143,13 +151,17 @@ def load():
                                       C.c_int32, C.c_uint64]
     lib.rg_policy_rollout.restype = C.c_int
     lib.rg_sizeof_policy_io.restype = C.c_int
+    lib.rg_set_lidar.argtypes = [C.c_void_p, C.POINTER(RgLidarParams)]
+    lib.rg_set_lidar.restype = C.c_int
+    lib.rg_sizeof_lidar_params.restype = C.c_int
     for f in (lib.rg_destroy, lib.rg_bind_state, lib.rg_set_stream, lib.rg_reset, lib.rg_step, lib.rg_rollout, lib.rg_get_obs,
               lib.rg_sizeof_params, lib.rg_sizeof_state, lib.rg_sizeof_step_io):
         f.restype = C.c_int
     if lib.rg_abi_version() != ABI_VERSION:
         raise RobogymError(f"ABI version {lib.rg_abi_version()} != {ABI_VERSION}; rebuild the library")
     if (lib.rg_sizeof_params() != C.sizeof(RgScenarioParams) or lib.rg_sizeof_state() != C.sizeof(RgState)
-            or lib.rg_sizeof_step_io() != C.sizeof(RgStepIO) or lib.rg_sizeof_policy_io() != C.sizeof(RgPolicyIO)):
+            or lib.rg_sizeof_step_io() != C.sizeof(RgStepIO) or lib.rg_sizeof_policy_io() != C.sizeof(RgPolicyIO)
+            or lib.rg_sizeof_lidar_params() != C.sizeof(RgLidarParams)):
         raise RobogymError("struct layout of the binding differs from the compiled library; rebuild")
     _lib = lib
     return lib

@@ -25,6 +25,8 @@ struct rg_handle {
     bool use_tpe;  // step with the thread-per-env kernel (robogym_tpe.hip) instead of the lane-group kernel
     bool seed_seen;      // the precomputed-reset blocks (rg_state.next_init) were drawn with last_seed
     uint64_t last_seed;
+    bool default_tpe;    // use_tpe as rg_create chose it (restored when the lidar goes off)
+    rg_lidar_params lidar;   // rays == 0: off (rg_set_lidar)
 };
 
 // Which step kernel: both give identical results.  The lane-group kernel has the shorter chain for
@@ -136,7 +138,27 @@ hipError_t launch_policy_rollout_h64(const KernelArgs &, const rg_actor_weights 
     __attribute__((weak));
 hipError_t launch_policy_rollout_h128(const KernelArgs &, const rg_actor_weights &, const rg_policy_io &, int32_t, hipStream_t)
     __attribute__((weak));
+// The lidar kernels (lidar_kernels.h) live in their own translation units; weak for the same reason.
+#define RG_LIDAR_LAUNCH(name) hipError_t name(const KernelArgs &, const rg_lidar_params &, hipStream_t) __attribute__((weak));
+RG_LIDAR_LAUNCH(launch_lidar_step)
+RG_LIDAR_LAUNCH(launch_lidar_obs)
+RG_LIDAR_LAUNCH(launch_lidar_rollout)
+RG_LIDAR_LAUNCH(launch_lidar_step_ipm)
+RG_LIDAR_LAUNCH(launch_lidar_rollout_ipm)
+#undef RG_LIDAR_LAUNCH
 }  // namespace rg
+
+// The scenario's own observation width: the columns its builder writes (the lidar block may start at or after it).
+static int own_obs_width(const rg_scenario_params &p) {
+    const int nb = p.num_neighbors >= p.n_agents - 1 ? p.n_agents - 1 : p.num_neighbors;
+    switch (p.scenario) {
+        case RG_SCN_PREDATOR_CAPTURE_PREY: return (p.capability_aware ? 6 : 4) * (nb + 1);
+        case RG_SCN_WAREHOUSE: return 3 * (nb + 1);
+        case RG_SCN_SIMPLE: return 2 * (p.n_agents + 1);
+        case RG_SCN_ARCTIC_TRANSPORT: return 30;
+        default: return p.capability_aware ? 11 : 9;
+    }
+}
 
 extern "C" {
 
@@ -148,6 +170,7 @@ int rg_sizeof_params(void) { return static_cast<int>(sizeof(rg_scenario_params))
 int rg_sizeof_state(void) { return static_cast<int>(sizeof(rg_state)); }
 int rg_sizeof_step_io(void) { return static_cast<int>(sizeof(rg_step_io)); }
 int rg_sizeof_policy_io(void) { return static_cast<int>(sizeof(rg_policy_io)); }
+int rg_sizeof_lidar_params(void) { return static_cast<int>(sizeof(rg_lidar_params)); }
 int rg_next_init_stride(const rg_scenario_params *params) {
     if (check_params(params) != 0) return -1;
     return rg::next_init_stride(*params);
@@ -189,7 +212,31 @@ rg_handle *rg_create(const rg_scenario_params *params, int32_t num_envs, int64_t
         if (!strcmp(force, "group")) h->use_tpe = false;
         else if (!strcmp(force, "tpe") && rg::tpe_supported(*params)) h->use_tpe = true;
     }
+    h->default_tpe = h->use_tpe;
+    memset(&h->lidar, 0, sizeof(h->lidar));
     return h;
+}
+
+int rg_set_lidar(rg_handle *h, const rg_lidar_params *lp) {
+    if (!h) return fail(-1, "handle is NULL");
+    if (!lp || lp->rays == 0) {
+        memset(&h->lidar, 0, sizeof(h->lidar));
+        h->use_tpe = h->default_tpe;
+        return 0;
+    }
+    if (lp->rays < 4 || lp->rays > RG_LIDAR_MAX_RAYS || (lp->rays & 3))
+        return fail(-50, "rg_set_lidar: rays must be 0 or a multiple of 4 in 4..32");
+    if (lp->offset + lp->rays != h->params.obs_dim)
+        return fail(-51, "rg_set_lidar: offset + rays must equal obs_dim (the lidar block ends the observation row)");
+    if (lp->offset < own_obs_width(h->params))
+        return fail(-52, "rg_set_lidar: offset lies inside the scenario's own observation columns");
+    if (!(lp->range > 0.0f && lp->range <= 3.402823466e38f)) return fail(-53, "rg_set_lidar: range must be positive and finite");
+    if (!rg::launch_lidar_step || !rg::launch_lidar_obs || !rg::launch_lidar_rollout || !rg::launch_lidar_step_ipm ||
+        !rg::launch_lidar_rollout_ipm)
+        return fail(-100, "rg_set_lidar: this build has no lidar kernels");
+    h->lidar = *lp;
+    h->use_tpe = false;   // the lidar is built into the lane-group kernel only
+    return 0;
 }
 
 int rg_destroy(rg_handle *h) {
@@ -312,6 +359,9 @@ int rg_step(rg_handle *h, const int32_t *actions, const rg_step_io *io, int32_t 
     a.seed = seed;
     RG_ON_DEVICE(h);
     if (int rc = sync_seed(h, seed)) return rc;
+    if (h->lidar.rays)
+        return launched(h->params.qp_mode == RG_QP_CVXOPT ? rg::launch_lidar_step_ipm(a, h->lidar, h->stream)
+                                                          : rg::launch_lidar_step(a, h->lidar, h->stream));
     return launched(h->use_tpe ? rg::launch_step_tpe(a, h->stream) : rg::launch_step(a, false, h->stream));
 }
 
@@ -334,6 +384,9 @@ int rg_rollout(rg_handle *h, const int32_t *actions, int32_t num_steps, const rg
     a.seed = seed;
     RG_ON_DEVICE(h);
     if (int rc = sync_seed(h, seed)) return rc;
+    if (h->lidar.rays)
+        return launched(h->params.qp_mode == RG_QP_CVXOPT ? rg::launch_lidar_rollout_ipm(a, h->lidar, h->stream)
+                                                          : rg::launch_lidar_rollout(a, h->lidar, h->stream));
     if (!h->use_tpe) return launched(rg::launch_rollout(a, h->stream));
     // thread-per-env: the multi-step kernel holds more values live (313 VGPRs at N = 5: one wave per
     // SIMD); it pays while the batch is at most one wave per SIMD (the latency regime), beyond that
@@ -357,6 +410,7 @@ int rg_policy_rollout(rg_handle *h, const rg_actor_weights *w, int32_t num_steps
     if (!w || !pio || !io) return fail(-23, "weights, policy io or step io is NULL");
     if (num_steps < 1) return fail(-27, "num_steps < 1");
     if (h->params.qp_mode == RG_QP_CVXOPT) return fail(-40, "rg_policy_rollout: the interior-point mode (barrier_solver: cvxopt) is not supported");
+    if (h->lidar.rays) return fail(-49, "rg_policy_rollout: a handle with the lidar observation on (rg_set_lidar) is not supported");
     if (!w->use_rnn || w->gru_packed != 3)
         return fail(-41, "rg_policy_rollout: the actor must be a GRU with gru_packed == 3 (two binary16 planes, pack_gru='f16x2')");
     if (w->hidden_dim != 64 && w->hidden_dim != 128) return fail(-42, "rg_policy_rollout: hidden_dim must be 64 or 128");
@@ -397,6 +451,7 @@ int rg_get_obs(rg_handle *h, float *obs) {
     if (reinterpret_cast<uintptr_t>(obs) & 15u) return fail(-26, "obs must be 16-byte aligned");
     a.io.obs = obs;
     RG_ON_DEVICE(h);
+    if (h->lidar.rays) return launched(rg::launch_lidar_obs(a, h->lidar, h->stream));
     return launched(rg::launch_step(a, true, h->stream));
 }
 

@@ -30,6 +30,7 @@
 
 #include "device_common.h"
 #include "ipm_qp.h"
+#include "lidar.h"
 #include "probes/diag.h"   // diagnostic hooks: every RG_* macro below expands to nothing in the shipped build
 
 namespace rg {
@@ -314,8 +315,11 @@ __device__ __forceinline__ void write_neighbour_obs(Lds<GW> &lds, int N, int Knb
 // count, single-step launch): the benchmark kernels carry none of it.
 // Sync: how the wave's lanes meet (device_common.h): WgSync in the step kernels (one-wave workgroups), WaveSync where the step
 // runs on one wave of a larger workgroup (policy_rollout.h): every barrier below sits under the wave's own control flow.
-template <int SCN, int GW, bool OBS_ONLY, int NT, bool AHEAD, bool GYM, int QPM = 0, typename QpLds = void, typename Sync = WgSync>
-__device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, const StepView &sv, QpLds *qp_lds = nullptr) {
+// LIDAR: the range block of `lid` (lidar.h) goes after the scenario's own columns.  Its own instantiations (lidar_kernels.h).
+template <int SCN, int GW, bool OBS_ONLY, int NT, bool AHEAD, bool GYM, int QPM = 0, typename QpLds = void, typename Sync = WgSync,
+          bool LIDAR = false>
+__device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, const StepView &sv, QpLds *qp_lds = nullptr,
+                                          const rg_lidar_params *lid = nullptr) {
     constexpr int EPW = WAVE / GW;  // envs per wave
     RG_STAMPS_BEGIN()
     const rg_scenario_params &p = a.p;
@@ -1048,6 +1052,9 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                 o[7] = static_cast<float>(grid[down * 12 + right]);
             }
         }
+        // (ArcticTransport: the lidar block right after its own columns, before the reward's LDS traffic -- placed after the
+        // reward, ROCm 7.2 put register copies above an exec restore in the reward's join, tools/isa_scan.py exec_prologue)
+        if constexpr (LIDAR) write_lidar<SCN, GW, OBS_ONLY, Sync>(*lid, a, lds, lane, gbase, N, ag, lane_ok, x, y, th, obs_row);
         if constexpr (!OBS_ONLY) {
             // shared reward over the two ground robots, in agent order (ArcticTransport.py:125-134)
             const float dx = x - goalx, dy = y - goaly;
@@ -1162,6 +1169,8 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         }
     }
 
+    // the lidar block, from the poses the own columns were built from (the staged LDS rows are still intact here)
+    if constexpr (LIDAR && SCN != RG_SCN_ARCTIC_TRANSPORT) write_lidar<SCN, GW, OBS_ONLY, Sync>(*lid, a, lds, lane, gbase, N, ag, lane_ok, x, y, th, obs_row);
     RG_STAMP(4);  // scenario epilogue computed
     if constexpr (!OBS_ONLY) {
         // gym's TimeLimit on top of the scenario (gymma block of rg_step_io): the limit ends an episode the scenario did not

@@ -1,7 +1,7 @@
 """Multi-GPU: one process per GPU, envs sharded in contiguous blocks, no per-step exchange.
 
 The path shards trivially (envs are independent); the only collectives
-are a broadcast of the scenario parameter block from rank 0 at init and a gather of
+are a broadcast of the scenario parameter block (and of the lidar block next to it) from rank 0 at init and a gather of
 per-env episode statistics per reporting interval -- both through torch.distributed
 (backend "nccl" = RCCL over xGMI on ROCm; "gloo" on CPU for the world_size-2 tests).
 """
@@ -69,6 +69,28 @@ def broadcast_params(params, src=0, device=None):
         buf = torch.zeros(ctypes.sizeof(RgScenarioParams), dtype=torch.uint8, device=device)
     dist.broadcast(buf, src=src)
     return params_from_bytes(buf.cpu().numpy().tobytes())
+
+
+def broadcast_lidar(lidar, src=0, device=None):
+    """The lidar block next to the parameter block: rank `src` sends its RgLidarParams (None = no lidar, sent as rays = 0);
+    every rank returns a copy of it, or None.  Every rank calls it (a collective), whatever its own argument."""
+    import ctypes
+    from ._lib import RgLidarParams
+    if not dist.is_initialized():
+        return lidar
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = collective_device(device)
+    n = ctypes.sizeof(RgLidarParams)
+    if dist.get_rank() == src:
+        blk = lidar if lidar is not None else RgLidarParams()
+        buf = torch.frombuffer(bytearray(ctypes.string_at(ctypes.addressof(blk), n)), dtype=torch.uint8).to(device)
+    else:
+        buf = torch.zeros(n, dtype=torch.uint8, device=device)
+    dist.broadcast(buf, src=src)
+    out = RgLidarParams()
+    ctypes.memmove(ctypes.addressof(out), buf.cpu().numpy().tobytes(), n)
+    return out if out.rays > 0 else None
 
 
 def gather_episode_stats(done_return_sum, done_count, done_steps_sum, dst=0, total_envs=None):

@@ -12,7 +12,7 @@ import os
 import numpy as np
 import yaml
 
-from ._lib import MAX_AGENTS, MAX_PREY, RgGrid, RgScenarioParams
+from ._lib import LIDAR_MAX_RAYS, MAX_AGENTS, MAX_PREY, RgGrid, RgLidarParams, RgScenarioParams
 
 SCENARIO_IDS = {"PredatorCapturePrey": 0, "Warehouse": 1, "MaterialTransport": 2, "Simple": 3, "ArcticTransport": 4}
 COLLISION_VARIANTS = {"center": 0, "offset": 1}
@@ -237,10 +237,50 @@ def make_params(scenario, cfg):
         p.agent_grid = g
         p.prey_grid = _dummy_grid()
         p.keep_theta = 0
+    p.obs_dim += lidar_config(cfg)[0]   # the lidar block follows the scenario's own columns
     if p.qp_mode == BARRIER_SOLVERS["cvxopt"] and p.n_agents > CVXOPT_MAX_AGENTS:
         raise ValueError(f"barrier_solver: cvxopt is built for n_agents <= {CVXOPT_MAX_AGENTS} (its QP is solved in one lane: 2N unknowns, "
                          f"N(N-1)/2 rows in registers); got {p.n_agents}")
     return p
+
+
+def lidar_config(cfg):
+    """(R, L) of the config keys `lidar_rays` (0 = off, or a multiple of 4 in 4..32) and `lidar_range` (metres, > 0).
+    Not part of the reference (it has no lidar): both keys are optional, and without them nothing changes."""
+    rays, rng = cfg.get("lidar_rays", 0), cfg.get("lidar_range", 1.0)
+    if isinstance(rays, bool) or not isinstance(rays, (int, np.integer)) or not (rays == 0 or (4 <= rays <= LIDAR_MAX_RAYS and rays % 4 == 0)):
+        raise ValueError(f"lidar_rays must be 0 or a multiple of 4 in 4..{LIDAR_MAX_RAYS} (got {rays!r})")
+    if isinstance(rng, bool) or not isinstance(rng, (int, float, np.integer, np.floating)):
+        raise ValueError(f"lidar_range must be a positive finite number of metres (got {rng!r})")
+    rng = float(rng)
+    if not (rng > 0.0 and math.isfinite(rng) and math.isfinite(float(np.float32(rng)))):
+        raise ValueError(f"lidar_range must be a positive finite number of metres (got {rng!r})")
+    return int(rays), rng
+
+
+def lidar_directions(rays):
+    """The ray table [R][2]: cos, sin of 2 pi k / R computed in binary64, rounded to binary32 (ray 0 straight ahead, counter-clockwise)."""
+    a = 2.0 * np.pi * np.arange(rays, dtype=np.float64) / rays
+    return np.stack([np.cos(a), np.sin(a)], axis=1).astype(np.float32)
+
+
+def lidar_params(scenario, cfg, params):
+    """The rg_lidar_params block of a config (None when `lidar_rays` is 0 or absent): the lidar block is the last R columns of
+    the row `params` (make_params(scenario, cfg)) describes."""
+    if scenario not in SCENARIO_IDS:
+        raise KeyError(f"scenario {scenario!r} is not built (have {sorted(SCENARIO_IDS)})")
+    rays, rng = lidar_config(cfg)
+    if rays == 0:
+        return None
+    lp = RgLidarParams()
+    lp.rays = rays
+    lp.offset = int(params.obs_dim) - rays
+    lp.range = float(np.float32(rng))
+    lp.inv_range = float(np.float32(1.0 / float(np.float32(rng))))
+    d = lidar_directions(rays)
+    for k in range(rays):
+        lp.dir[k][0], lp.dir[k][1] = float(d[k, 0]), float(d[k, 1])
+    return lp
 
 
 def params_to_bytes(p):

@@ -15,14 +15,14 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .params import load_config, make_params
+from .params import lidar_params, load_config, make_params
 
 VIOLATION_MESSAGES = ("", "collision", "boundary", "collision_boundary")  # roboEnv.py:82-94
 
 
 class VecRobotariumEnv(object):
     def __init__(self, scenario, num_envs, config_path=None, overrides=None, device="cuda:0", seed=0,
-                 env_offset=0, auto_reset=True, reference_reset_obs=True, params=None, collect_qp_stats=False):
+                 env_offset=0, auto_reset=True, reference_reset_obs=True, params=None, collect_qp_stats=False, lidar=None):
         """scenario: 'PredatorCapturePrey' | 'Warehouse' | 'MaterialTransport' | 'Simple' | 'ArcticTransport'
         (wrapper.py:12-16).
         config_path / overrides: the reference's scenario YAML (same keys) and a dict of overrides.
@@ -32,14 +32,21 @@ class VecRobotariumEnv(object):
         auto_reset: finished envs are reset inside the step launch.
         reference_reset_obs: reset() returns zeros like the reference (PredatorCapturePrey.py:136);
             False returns the observation of the fresh state (get_obs()).
-        params: a ready RgScenarioParams (e.g. received by broadcast) instead of a config."""
+        params: a ready RgScenarioParams (e.g. received by broadcast) instead of a config.
+        lidar: with `params`, its RgLidarParams (params.lidar_params; dist.broadcast_lidar), or None for no lidar.  From a config
+            the keys `lidar_rays` / `lidar_range` decide (DESIGN.md "Lidar")."""
         self.lib = _lib.load()
         self.scenario = scenario
         self.cfg = None
         if params is None:
             self.cfg = load_config(scenario, config_path, overrides)
             params = make_params(scenario, self.cfg)
+            if lidar is None:
+                lidar = lidar_params(scenario, self.cfg, params)
+        if lidar is not None and int(lidar.rays) == 0:
+            lidar = None
         self.params = params
+        self.lidar = lidar   # RgLidarParams or None: the last lidar.rays columns of every observation row
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.RobogymError("VecRobotariumEnv runs on an AMD GPU only (device='cuda:N'); no CPU path exists")
@@ -109,6 +116,13 @@ class VecRobotariumEnv(object):
             self.next_init.data_ptr() if self.next_init is not None else None,
             self.next_episode.data_ptr() if self.next_episode is not None else None)
         _lib.check(self.lib.rg_bind_state(self._h, C.byref(st)), "rg_bind_state")
+        if self.lidar is not None:
+            rc = self.lib.rg_set_lidar(self._h, C.byref(self.lidar))
+            if rc != 0:
+                msg = "rg_set_lidar failed (%d): %s" % (rc, self.lib.rg_last_error().decode())
+                self.lib.rg_destroy(self._h)
+                self._h = None
+                raise (ValueError if -60 < rc <= -50 else _lib.RobogymError)(msg)
         self._io = _lib.RgStepIO(self.obs.data_ptr(), self.reward.data_ptr(), self.done_u8.data_ptr(),
                                  self.dist_travelled.data_ptr(), self.violation.data_ptr(),
                                  self.remaining.data_ptr(),
