@@ -28,7 +28,8 @@ extern "C" {
 #endif
 
 /* 7: + rg_policy_rollout() and rg_policy_io (T actor steps and env steps in one launch), rg_sizeof_policy_io(); later, purely
- * additive (no existing layout or entry point changed): + rg_set_lidar(), rg_lidar_params, rg_sizeof_lidar_params().
+ * additive (no existing layout or entry point changed): + rg_set_lidar(), rg_lidar_params, rg_sizeof_lidar_params(); + rg_set_teams(),
+ * rg_team_params, rg_sizeof_team_params().
  * 6 (round 5): rg_scenario_params ends in the barrier-QP solver selection (qp_mode + cvxopt's options): RG_QP_CVXOPT computes the
  * interior-point iterate the reference's stack computes (utilities/controller.py:13-16,23) instead of the exact projection;
  * rg_step_io.zero_obs_on_end; + rg_actor_forward_explore(), rg_actor_pack_gru_f16x2() and rg_actor_weights.gru_packed == 3.
@@ -267,9 +268,46 @@ int rg_sizeof_lidar_params(void);
 /* Turns the lidar on for every later launch of the handle (lp->rays > 0), or off (lp NULL or lp->rays == 0: the default kernel
  * choice comes back).  With the lidar on the handle steps with the lane-group kernel at every batch size (rg_step_kernel()
  * reports 0) and rg_policy_rollout refuses it.  Errors: -1 NULL handle, -50 rays not a multiple of 4 in 4..32, -51
- * offset + rays != obs_dim, -52 offset below the scenario's own width, -53 range not positive and finite, -100 a build without
- * the lidar kernels. */
+ * offset + rays != obs_dim, -52 offset below the scenario's own width, -53 range not positive and finite, -54 a handle with a
+ * team pool (rg_set_teams), -100 a build without the lidar kernels. */
 int rg_set_lidar(rg_handle *h, const rg_lidar_params *lp);
+
+/* ---- team pool: per-episode agent capabilities (opt-in; out of parity scope: the reference has no pool) ----------------
+ * A handle with a pool carries C capability sets (1 <= C <= RG_TEAM_MAX_SETS); set t gives every agent a its own values in row t
+ * of [C][N] tables: agent_step[t][a] (PredatorCapturePrey, Warehouse, Simple: step_dist; MaterialTransport: speed),
+ * sensing_radius[t][a], capture_radius[t][a] (PredatorCapturePrey) and torque[t][a] (MaterialTransport).  Every env e carries a
+ * team index team_index[e] in [0, C), and every launch of the handle (rg_step, rg_rollout, rg_get_obs) reads set
+ * team_index[e]'s values wherever it reads rg_scenario_params' agent_step / sensing_radius / capture_radius / torque, the
+ * partners' values included.  The index is part of the env's state; the engine writes it when an episode starts:
+ *   RG_TEAM_EPISODE: t = (uint64(w0) * C) >> 32, w0 = word 0 of philox4x32_10(counter = (ge_lo, ge_hi, episode, 0x80000000),
+ *                    key = (seed_lo, seed_hi)), ge = env_offset + e, episode = the reset_count value the reset sampler draws
+ *                    the episode with -- rg_reset (masked or not) and the step's auto-reset (drawn-ahead blocks included).
+ *                    (The block 0x80000000 lies far above the sampler's own blocks: no existing draw changes.)
+ *   RG_TEAM_FIXED:   t = ge mod C, written by rg_set_teams and kept for the handle's life.
+ * The tables and the index array are caller-owned device memory (the library never allocates) and must stay valid while the
+ * pool is set; an index outside [0, C) (a caller's write) is read as C - 1.  Tables a scenario does not read may be NULL.
+ * Layout: 8 + 5 pointers = 48 bytes, no padding; checked against the binding with rg_sizeof_team_params(). */
+#define RG_TEAM_MAX_SETS 64
+#define RG_TEAM_EPISODE 0
+#define RG_TEAM_FIXED 1
+typedef struct rg_team_params {
+    int32_t n_sets;                 /* C: 0 (off) or 1..64 */
+    int32_t mode;                   /* RG_TEAM_EPISODE | RG_TEAM_FIXED */
+    const float *agent_step;        /* [C][N] every scenario */
+    const float *sensing_radius;    /* [C][N] PredatorCapturePrey */
+    const float *capture_radius;    /* [C][N] PredatorCapturePrey */
+    const int32_t *torque;          /* [C][N] MaterialTransport */
+    int32_t *team_index;            /* [E]    the envs' team indices (state) */
+} rg_team_params;
+int rg_sizeof_team_params(void);
+/* Sets the handle's pool for every later launch (tp->n_sets > 0), or removes it (tp NULL or tp->n_sets == 0: the handle's own
+ * kernel choice comes back).  With a pool the handle steps with the lane-group kernel at every batch size (rg_step_kernel()
+ * reports 0) and rg_policy_rollout refuses it.  RG_TEAM_FIXED writes team_index on the handle's stream (needs rg_bind_state
+ * first).  Errors: -1 NULL handle, -22 fixed mode before rg_bind_state, -60 n_sets outside 1..64, -61 unknown mode,
+ * -62 ArcticTransport (its agent types are fixed), -63 a handle with the lidar on, -64 a table the scenario reads or
+ * team_index is NULL, -30 the launch failed, -100 a build without the team kernels.  rg_set_lidar refuses a handle with a
+ * pool (-54). */
+int rg_set_teams(rg_handle *h, const rg_team_params *tp);
 
 /* ---- policy inference for evaluation rollouts ------------------------
  * The EPyMARL recurrent actor the reference evaluates with (utilities/rnn_agent.py:5-29 `RNNAgent`:
@@ -357,7 +395,7 @@ int rg_sizeof_policy_io(void);
  * Envs advance independently (no device-wide synchronisation), auto-reset runs inside the launch.  Refused with a reason in
  * the last-error text: the interior-point mode (RG_QP_CVXOPT), gru_packed other than 3 or use_rnn = 0, hidden_dim other than
  * 64 / 128, an input width other than obs_dim (+ n_agents with append_agent_id), num_steps < 1, a missing gymma block, a handle
- * with the lidar on (-49). */
+ * with the lidar on (-49), a handle with a team pool (-39). */
 int rg_policy_rollout(rg_handle *h, const rg_actor_weights *w, int32_t num_steps, const rg_policy_io *pio, const rg_step_io *io,
                       int32_t auto_reset, uint64_t seed);
 

@@ -17,9 +17,10 @@ LIB = os.path.join(HERE, "librobogym_hip.so")
 SOURCES = ["robogym_kernels.hip", "robogym_rollout_group.hip", "robogym_kernels_ipm.hip", "robogym_rollout_group_ipm.hip",
            "robogym_tpe.hip", "robogym_rollout_tpe.hip", "robogym_capi.hip", "actor_mfma.hip", "robogym_policy_h64.hip",
            "robogym_policy_h128.hip", "robogym_lidar.hip", "robogym_lidar_rollout.hip", "robogym_lidar_ipm.hip",
-           "robogym_lidar_rollout_ipm.hip"]
+           "robogym_lidar_rollout_ipm.hip", "robogym_team.hip", "robogym_team_rollout.hip", "robogym_team_ipm.hip",
+           "robogym_team_rollout_ipm.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("sim_math.h", "kernel_args.h", "device_common.h", "step_group.h", "step_tpe.h", "step_tpe_ipm.h", "ipm_qp.h",
-                                           "actor_common.h", "actor_body.inc", "policy_rollout.h", "lidar.h", "lidar_kernels.h", os.path.join("probes", "diag.h"), os.path.join("probes", "actor_diag.h"))
+                                           "actor_common.h", "actor_body.inc", "policy_rollout.h", "lidar.h", "lidar_kernels.h", "team.h", "team_kernels.h", os.path.join("probes", "diag.h"), os.path.join("probes", "actor_diag.h"))
                                            if os.path.exists(os.path.join(CSRC, h))] + \
           [os.path.join(HERE, "..", "include", "robogym.h")]
 ARCH = "gfx950"
@@ -58,7 +59,10 @@ FILE_FLAGS = {"robogym_tpe.hip": ["-fno-slp-vectorize"], "robogym_rollout_tpe.hi
               "robogym_policy_h64.hip": GROUP_SLP, "robogym_policy_h128.hip": GROUP_SLP,
               # the lidar kernels (lidar_kernels.h): lane-group kernels, with the flags of their mode
               "robogym_lidar.hip": GROUP_SLP, "robogym_lidar_rollout.hip": GROUP_SLP,
-              "robogym_lidar_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_lidar_rollout_ipm.hip": GROUP_SLP + IPM_SCHED}
+              "robogym_lidar_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_lidar_rollout_ipm.hip": GROUP_SLP + IPM_SCHED,
+              # the team kernels (team_kernels.h): lane-group kernels, with the flags of their mode
+              "robogym_team.hip": GROUP_SLP, "robogym_team_rollout.hip": GROUP_SLP,
+              "robogym_team_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_team_rollout_ipm.hip": GROUP_SLP + IPM_SCHED}
 BASE_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 STAMP = LIB + ".flags"
 

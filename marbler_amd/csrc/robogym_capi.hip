@@ -25,8 +25,9 @@ struct rg_handle {
     bool use_tpe;  // step with the thread-per-env kernel (robogym_tpe.hip) instead of the lane-group kernel
     bool seed_seen;      // the precomputed-reset blocks (rg_state.next_init) were drawn with last_seed
     uint64_t last_seed;
-    bool default_tpe;    // use_tpe as rg_create chose it (restored when the lidar goes off)
+    bool default_tpe;    // use_tpe as rg_create chose it (restored when the lidar and the team pool are both off)
     rg_lidar_params lidar;   // rays == 0: off (rg_set_lidar)
+    rg_team_params teams;    // n_sets == 0: no pool (rg_set_teams)
 };
 
 // Which step kernel: both give identical results.  The lane-group kernel has the shorter chain for
@@ -146,6 +147,15 @@ RG_LIDAR_LAUNCH(launch_lidar_rollout)
 RG_LIDAR_LAUNCH(launch_lidar_step_ipm)
 RG_LIDAR_LAUNCH(launch_lidar_rollout_ipm)
 #undef RG_LIDAR_LAUNCH
+// The team kernels (team_kernels.h) likewise.
+#define RG_TEAM_LAUNCH(name) hipError_t name(const KernelArgs &, const rg_team_params &, hipStream_t) __attribute__((weak));
+RG_TEAM_LAUNCH(launch_team_step)
+RG_TEAM_LAUNCH(launch_team_obs)
+RG_TEAM_LAUNCH(launch_team_rollout)
+RG_TEAM_LAUNCH(launch_team_step_ipm)
+RG_TEAM_LAUNCH(launch_team_rollout_ipm)
+RG_TEAM_LAUNCH(launch_team_index)
+#undef RG_TEAM_LAUNCH
 }  // namespace rg
 
 // The scenario's own observation width: the columns its builder writes (the lidar block may start at or after it).
@@ -171,6 +181,7 @@ int rg_sizeof_state(void) { return static_cast<int>(sizeof(rg_state)); }
 int rg_sizeof_step_io(void) { return static_cast<int>(sizeof(rg_step_io)); }
 int rg_sizeof_policy_io(void) { return static_cast<int>(sizeof(rg_policy_io)); }
 int rg_sizeof_lidar_params(void) { return static_cast<int>(sizeof(rg_lidar_params)); }
+int rg_sizeof_team_params(void) { return static_cast<int>(sizeof(rg_team_params)); }
 int rg_next_init_stride(const rg_scenario_params *params) {
     if (check_params(params) != 0) return -1;
     return rg::next_init_stride(*params);
@@ -214,6 +225,7 @@ rg_handle *rg_create(const rg_scenario_params *params, int32_t num_envs, int64_t
     }
     h->default_tpe = h->use_tpe;
     memset(&h->lidar, 0, sizeof(h->lidar));
+    memset(&h->teams, 0, sizeof(h->teams));
     return h;
 }
 
@@ -221,9 +233,10 @@ int rg_set_lidar(rg_handle *h, const rg_lidar_params *lp) {
     if (!h) return fail(-1, "handle is NULL");
     if (!lp || lp->rays == 0) {
         memset(&h->lidar, 0, sizeof(h->lidar));
-        h->use_tpe = h->default_tpe;
+        h->use_tpe = h->teams.n_sets ? false : h->default_tpe;
         return 0;
     }
+    if (h->teams.n_sets) return fail(-54, "rg_set_lidar: the handle has a team pool (rg_set_teams); a pool and the lidar do not combine");
     if (lp->rays < 4 || lp->rays > RG_LIDAR_MAX_RAYS || (lp->rays & 3))
         return fail(-50, "rg_set_lidar: rays must be 0 or a multiple of 4 in 4..32");
     if (lp->offset + lp->rays != h->params.obs_dim)
@@ -345,7 +358,10 @@ int rg_reset(rg_handle *h, const uint8_t *mask, uint64_t seed, int32_t flags) {
     a.seed = seed;
     a.reset_flags = flags;
     RG_ON_DEVICE(h);
-    return launched(rg::launch_reset(a, h->stream));
+    if (int rc = launched(rg::launch_reset(a, h->stream))) return rc;
+    // the team index of every episode just started (a second launch on the same stream: the reset kernels stay as they are)
+    if (h->teams.n_sets) return launched(rg::launch_team_index(a, h->teams, h->stream));
+    return 0;
 }
 
 int rg_step(rg_handle *h, const int32_t *actions, const rg_step_io *io, int32_t auto_reset, uint64_t seed) {
@@ -359,6 +375,9 @@ int rg_step(rg_handle *h, const int32_t *actions, const rg_step_io *io, int32_t 
     a.seed = seed;
     RG_ON_DEVICE(h);
     if (int rc = sync_seed(h, seed)) return rc;
+    if (h->teams.n_sets)
+        return launched(h->params.qp_mode == RG_QP_CVXOPT ? rg::launch_team_step_ipm(a, h->teams, h->stream)
+                                                          : rg::launch_team_step(a, h->teams, h->stream));
     if (h->lidar.rays)
         return launched(h->params.qp_mode == RG_QP_CVXOPT ? rg::launch_lidar_step_ipm(a, h->lidar, h->stream)
                                                           : rg::launch_lidar_step(a, h->lidar, h->stream));
@@ -384,6 +403,9 @@ int rg_rollout(rg_handle *h, const int32_t *actions, int32_t num_steps, const rg
     a.seed = seed;
     RG_ON_DEVICE(h);
     if (int rc = sync_seed(h, seed)) return rc;
+    if (h->teams.n_sets)
+        return launched(h->params.qp_mode == RG_QP_CVXOPT ? rg::launch_team_rollout_ipm(a, h->teams, h->stream)
+                                                          : rg::launch_team_rollout(a, h->teams, h->stream));
     if (h->lidar.rays)
         return launched(h->params.qp_mode == RG_QP_CVXOPT ? rg::launch_lidar_rollout_ipm(a, h->lidar, h->stream)
                                                           : rg::launch_lidar_rollout(a, h->lidar, h->stream));
@@ -411,6 +433,7 @@ int rg_policy_rollout(rg_handle *h, const rg_actor_weights *w, int32_t num_steps
     if (num_steps < 1) return fail(-27, "num_steps < 1");
     if (h->params.qp_mode == RG_QP_CVXOPT) return fail(-40, "rg_policy_rollout: the interior-point mode (barrier_solver: cvxopt) is not supported");
     if (h->lidar.rays) return fail(-49, "rg_policy_rollout: a handle with the lidar observation on (rg_set_lidar) is not supported");
+    if (h->teams.n_sets) return fail(-39, "rg_policy_rollout: a handle with a team pool (rg_set_teams) is not supported");
     if (!w->use_rnn || w->gru_packed != 3)
         return fail(-41, "rg_policy_rollout: the actor must be a GRU with gru_packed == 3 (two binary16 planes, pack_gru='f16x2')");
     if (w->hidden_dim != 64 && w->hidden_dim != 128) return fail(-42, "rg_policy_rollout: hidden_dim must be 64 or 128");
@@ -439,6 +462,38 @@ int rg_policy_rollout(rg_handle *h, const rg_actor_weights *w, int32_t num_steps
     return launched(launch(a, *w, *pio, num_steps, h->stream));
 }
 
+int rg_set_teams(rg_handle *h, const rg_team_params *tp) {
+    if (!h) return fail(-1, "handle is NULL");
+    if (!tp || tp->n_sets == 0) {
+        memset(&h->teams, 0, sizeof(h->teams));
+        h->use_tpe = h->lidar.rays ? false : h->default_tpe;
+        return 0;
+    }
+    if (tp->n_sets < 1 || tp->n_sets > RG_TEAM_MAX_SETS) return fail(-60, "rg_set_teams: n_sets must be 0 or in 1..64");
+    if (tp->mode != RG_TEAM_EPISODE && tp->mode != RG_TEAM_FIXED)
+        return fail(-61, "rg_set_teams: unknown mode (RG_TEAM_EPISODE or RG_TEAM_FIXED)");
+    if (h->params.scenario == RG_SCN_ARCTIC_TRANSPORT)
+        return fail(-62, "rg_set_teams: ArcticTransport's agent types are fixed by the scenario; it takes no team pool");
+    if (h->lidar.rays) return fail(-63, "rg_set_teams: the handle has the lidar on (rg_set_lidar); a pool and the lidar do not combine");
+    const int sc = h->params.scenario;
+    if (!tp->team_index || !tp->agent_step || (sc == RG_SCN_PREDATOR_CAPTURE_PREY && (!tp->sensing_radius || !tp->capture_radius)) ||
+        (sc == RG_SCN_MATERIAL_TRANSPORT && !tp->torque))
+        return fail(-64, "rg_set_teams: team_index, agent_step and the scenario's other tables (PredatorCapturePrey: sensing_radius, "
+                         "capture_radius; MaterialTransport: torque) are required");
+    if (!rg::launch_team_step || !rg::launch_team_obs || !rg::launch_team_rollout || !rg::launch_team_step_ipm ||
+        !rg::launch_team_rollout_ipm || !rg::launch_team_index)
+        return fail(-100, "rg_set_teams: this build has no team kernels");
+    if (tp->mode == RG_TEAM_FIXED) {   // the index of every env for the handle's life: env_offset + e mod C
+        rg::KernelArgs a;
+        if (int rc = fill_args(h, a)) return rc;
+        RG_ON_DEVICE(h);
+        if (int rc = launched(rg::launch_team_index(a, *tp, h->stream))) return rc;
+    }
+    h->teams = *tp;
+    h->use_tpe = false;   // the pool is built into the lane-group kernel only
+    return 0;
+}
+
 int rg_step_kernel(const rg_handle *h) {
     if (!h) return fail(-1, "handle is NULL");
     return h->use_tpe ? 1 : 0;
@@ -451,6 +506,7 @@ int rg_get_obs(rg_handle *h, float *obs) {
     if (reinterpret_cast<uintptr_t>(obs) & 15u) return fail(-26, "obs must be 16-byte aligned");
     a.io.obs = obs;
     RG_ON_DEVICE(h);
+    if (h->teams.n_sets) return launched(rg::launch_team_obs(a, h->teams, h->stream));
     if (h->lidar.rays) return launched(rg::launch_lidar_obs(a, h->lidar, h->stream));
     return launched(rg::launch_step(a, true, h->stream));
 }

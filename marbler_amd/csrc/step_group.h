@@ -31,6 +31,7 @@
 #include "device_common.h"
 #include "ipm_qp.h"
 #include "lidar.h"
+#include "team.h"
 #include "probes/diag.h"   // diagnostic hooks: every RG_* macro below expands to nothing in the shipped build
 
 namespace rg {
@@ -316,10 +317,12 @@ __device__ __forceinline__ void write_neighbour_obs(Lds<GW> &lds, int N, int Knb
 // Sync: how the wave's lanes meet (device_common.h): WgSync in the step kernels (one-wave workgroups), WaveSync where the step
 // runs on one wave of a larger workgroup (policy_rollout.h): every barrier below sits under the wave's own control flow.
 // LIDAR: the range block of `lid` (lidar.h) goes after the scenario's own columns.  Its own instantiations (lidar_kernels.h).
+// TEAM: the agents' capabilities come from set team_index[e] of the pool `tm` (team.h), and an episode that starts here draws
+// the env's next index.  Its own instantiations (team_kernels.h).
 template <int SCN, int GW, bool OBS_ONLY, int NT, bool AHEAD, bool GYM, int QPM = 0, typename QpLds = void, typename Sync = WgSync,
-          bool LIDAR = false>
+          bool LIDAR = false, bool TEAM = false>
 __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, const StepView &sv, QpLds *qp_lds = nullptr,
-                                          const rg_lidar_params *lid = nullptr) {
+                                          const rg_lidar_params *lid = nullptr, const rg_team_params *tm = nullptr) {
     constexpr int EPW = WAVE / GW;  // envs per wave
     RG_STAMPS_BEGIN()
     const rg_scenario_params &p = a.p;
@@ -349,6 +352,16 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     else if constexpr (SCN == RG_SCN_SIMPLE) asm volatile("" ::"s"(q_prey));
     else if constexpr (SCN == RG_SCN_ARCTIC_TRANSPORT) asm volatile("" ::"s"(q_grid), "s"(q_pix), "s"(q_reached), "s"(q_gcol));
     else asm volatile("" ::"s"(q_msg), "s"(q_zone), "s"(q_load));
+    int32_t *q_tidx = TEAM ? tm->team_index : nullptr;
+    const float *q_tstep = TEAM ? tm->agent_step : nullptr, *q_tsr = TEAM ? tm->sensing_radius : nullptr;
+    const float *q_tcr = TEAM ? tm->capture_radius : nullptr;
+    const int32_t *q_ttq = TEAM ? tm->torque : nullptr;
+    const int q_tC = TEAM ? tm->n_sets : 1;
+    if constexpr (TEAM) {
+        asm volatile("" ::"s"(q_tidx), "s"(q_tstep), "s"(q_tC));
+        if constexpr (SCN == RG_SCN_PREDATOR_CAPTURE_PREY) asm volatile("" ::"s"(q_tsr), "s"(q_tcr));
+        else if constexpr (SCN == RG_SCN_MATERIAL_TRANSPORT) asm volatile("" ::"s"(q_ttq));
+    }
 
     const int N = NT > 0 ? NT : q_N;
     const int lane = threadIdx.x;
@@ -375,6 +388,10 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     int st_cnt = 0, st_steps = 0;
     const bool stats = (!OBS_ONLY) && q_ret != nullptr;
     int pix = 0, reached = 0;  // ArcticTransport (pix feeds this step's goals)
+    int team_raw = 0, tq_raw = 0;  // TEAM: the env's set index (fetched first: the pool loads below depend on it); own torque
+    if constexpr (TEAM) {
+        if (env_ok) team_raw = q_tidx[e];
+    }
     if (lane_ok) {
         const float *X = q_poses + eN * 3;
         x = X[ag];
@@ -382,12 +399,25 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         th = X[2 * N + ag];
         if constexpr (!OBS_ONLY) act = q_act[eN + ag];
         if constexpr (SCN == RG_SCN_ARCTIC_TRANSPORT) pix = q_pix[eN + ag];
+        if constexpr (!TEAM) {
         agent_step = p.agent_step[ag];
         if constexpr (SCN == RG_SCN_PREDATOR_CAPTURE_PREY) {
             sr = p.sensing_radius[ag];
             cr = p.capture_radius[ag];
         }
+        }
         if constexpr (!OBS_ONLY) carry = q_carry[eN + ag];
+        if constexpr (TEAM) {
+            // the lane's row of the env's set, behind the state loads above (they do not wait for the index); the step
+            // length feeds the goal, the rest (radii, torque) only the epilogue, where RG_LATE pins their first use
+            const size_t ti = static_cast<size_t>(team_clamp(team_raw, q_tC)) * N + ag;
+            agent_step = q_tstep[ti];
+            if constexpr (SCN == RG_SCN_PREDATOR_CAPTURE_PREY) {
+                sr = q_tsr[ti];
+                cr = q_tcr[ti];
+            }
+            if constexpr (SCN == RG_SCN_MATERIAL_TRANSPORT) tq_raw = q_ttq[ti];
+        }
     }
     int rc_raw = -1;  // reset_count, for the fused reset of an env that finishes in this launch
     // The env's NEXT initial state, drawn ahead of time into its block of next_init (device_common.h ResetDst) at the
@@ -785,6 +815,10 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
 
     if constexpr (SCN == RG_SCN_PREDATOR_CAPTURE_PREY) {
         const int P = q_P;
+        if constexpr (TEAM) {
+            RG_LATE(sr);
+            RG_LATE(cr);
+        }
         const float sr2 = sr * sr, cr2 = cr * cr;
         if (P > 8) Sync::sync();  // LDS prey block visible (single-wave workgroup: waitcnt + s_barrier)
         if (P <= 8) {  // the flag bytes fetched in the prologue -> bit masks of the env
@@ -1089,6 +1123,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             RG_LATE(msg[i]);
             if (!OBS_ONLY && i < N) msg[i] = msg[i] % 4;  // MaterialTransport.py:119-120
         }
+        if constexpr (TEAM) RG_LATE(tq_raw);
         if (lane_ok) {
             obs_row[0] = x;
             obs_row[1] = y;
@@ -1098,7 +1133,8 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
 #pragma unroll
             for (int i = 0; i < 4; ++i) obs_row[5 + i] = static_cast<float>(msg[i]);
             if (p.capability_aware) {
-                obs_row[9] = static_cast<float>(p.torque[ag]);
+                if constexpr (TEAM) obs_row[9] = static_cast<float>(tq_raw);
+                else obs_row[9] = static_cast<float>(p.torque[ag]);
                 obs_row[10] = agent_step;
             }
         }
@@ -1106,6 +1142,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             lds.ax[lane] = x;
             lds.ay[lane] = y;
             lds.aload[lane] = load;
+            if constexpr (TEAM) team_lds<SCN, GW>().torque[lane] = tq_raw;   // the replay reads every partner's
             Sync::sync();
             if (viol) {
                 reward = p.violation_reward;
@@ -1120,7 +1157,9 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                 for (int j = 0; j < N; ++j) {
                     const float jx = lds.ax[gbase + j], jy = lds.ay[gbase + j];
                     int jl = lds.aload[gbase + j];
-                    const int tq = p.torque[j];
+                    int tq;
+                    if constexpr (TEAM) tq = team_lds<SCN, GW>().torque[gbase + j];
+                    else tq = p.torque[j];
                     if (jl > 0) {
                         if (jx < -1.5f + egw) {
                             reward = reward + static_cast<float>(jl) * p.unload_multiplier;
@@ -1281,6 +1320,11 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                     a.st.reset_count[e] = rc_raw + 1;
                     a.st.episode_steps[e] = 0;
                 }
+            }
+            // the new episode's team: the episode just started is episode rc_raw on either path above (the drawn-ahead block is
+            // tagged with it), and the index is a function of that episode alone -- nothing of it is drawn ahead
+            if constexpr (TEAM) {
+                if (env_ok & ended & (ag == 0)) q_tidx[e] = team_draw(*tm, static_cast<uint64_t>(a.env_offset + e), rc_raw, a.seed);
             }
         }
         // ---- draw ahead: an env that goes on and whose block does not hold its next episode (consumed by the reset of

@@ -1,7 +1,7 @@
 """Multi-GPU: one process per GPU, envs sharded in contiguous blocks, no per-step exchange.
 
 The path shards trivially (envs are independent); the only collectives
-are a broadcast of the scenario parameter block (and of the lidar block next to it) from rank 0 at init and a gather of
+are a broadcast of the scenario parameter block (and of the lidar block and team pool next to it) from rank 0 at init and a gather of
 per-env episode statistics per reporting interval -- both through torch.distributed
 (backend "nccl" = RCCL over xGMI on ROCm; "gloo" on CPU for the world_size-2 tests).
 """
@@ -91,6 +91,34 @@ def broadcast_lidar(lidar, src=0, device=None):
     out = RgLidarParams()
     ctypes.memmove(ctypes.addressof(out), buf.cpu().numpy().tobytes(), n)
     return out if out.rays > 0 else None
+
+
+def broadcast_teams(teams, src=0, device=None):
+    """The team pool next to the parameter block: rank `src` sends its params.TeamPool (None = no pool); every rank returns a
+    copy of it, or None.  Every rank calls it (a collective), whatever its own argument.  Two collectives: a header
+    (n_sets, n_agents, mode), then the four [C][N] tables as one int32 buffer (the float tables by their bits)."""
+    import numpy as np
+    from .params import TeamPool
+    if not dist.is_initialized():
+        return teams
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = collective_device(device)
+    me = dist.get_rank() == src
+    hdr = torch.tensor([teams.n_sets, teams.n_agents, teams.mode] if (me and teams is not None) else [0, 0, 0],
+                       dtype=torch.int32, device=device)
+    dist.broadcast(hdr, src=src)
+    C_, N, mode = (int(v) for v in hdr.cpu())
+    if C_ == 0:
+        return None
+    if me:
+        flat = np.concatenate([np.ascontiguousarray(getattr(teams, k)).view(np.int32).ravel() for k in TeamPool.TABLES])
+        buf = torch.as_tensor(flat, dtype=torch.int32).to(device)
+    else:
+        buf = torch.zeros(4 * C_ * N, dtype=torch.int32, device=device)
+    dist.broadcast(buf, src=src)
+    t = buf.cpu().numpy().reshape(4, C_, N)
+    return TeamPool(mode, t[0].view(np.float32), t[1].view(np.float32), t[2].view(np.float32), t[3])
 
 
 def gather_episode_stats(done_return_sum, done_count, done_steps_sum, dst=0, total_envs=None):

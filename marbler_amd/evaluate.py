@@ -166,6 +166,8 @@ def policy_rollout(env, actor, T, io, hidden, actions, restart=None, append_agen
     lib = _lib.load()
     if int(env.params.qp_mode) != 0:
         raise ValueError("one launch: the interior-point mode (barrier_solver: cvxopt) is not supported")
+    if getattr(env, "teams", None) is not None:
+        raise ValueError("one launch: an env with a team pool (teams) is not supported; use the two-launch path")
     if getattr(env, "lidar", None) is not None:
         raise ValueError("one launch: an env with the lidar observation (lidar_rays > 0) is not supported; use the two-launch path")
     if not (actor.use_rnn and actor.pack_gru == "f16x2"):

@@ -276,6 +276,8 @@ class BatchedRunner(object):
         eps = self.epsilon
         # exploration: ONE uniform per agent and time step, drawn for the whole call in one launch (evaluate.explore_select is the rule)
         u_all = torch.rand(T, E, N, generator=self.gen, device=dev) if eps > 0.0 else None
+        if one_launch and getattr(env, "teams", None) is not None:
+            raise ValueError("one_launch: an env with a team pool (teams) is not supported; run(T) collects it on the two-launch path")
         if one_launch and env.lidar is not None:
             raise ValueError("one_launch: an env with the lidar observation (lidar_rays > 0) is not supported; run(T) collects it "
                              "on the two-launch path")

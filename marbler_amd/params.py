@@ -12,7 +12,7 @@ import os
 import numpy as np
 import yaml
 
-from ._lib import LIDAR_MAX_RAYS, MAX_AGENTS, MAX_PREY, RgGrid, RgLidarParams, RgScenarioParams
+from ._lib import LIDAR_MAX_RAYS, MAX_AGENTS, MAX_PREY, TEAM_EPISODE, TEAM_FIXED, TEAM_MAX_SETS, RgGrid, RgLidarParams, RgScenarioParams
 
 SCENARIO_IDS = {"PredatorCapturePrey": 0, "Warehouse": 1, "MaterialTransport": 2, "Simple": 3, "ArcticTransport": 4}
 COLLISION_VARIANTS = {"center": 0, "offset": 1}
@@ -281,6 +281,103 @@ def lidar_params(scenario, cfg, params):
     for k in range(rays):
         lp.dir[k][0], lp.dir[k][1] = float(d[k, 0]), float(d[k, 1])
     return lp
+
+
+# ------------------------------------------------------------------ team pool (DESIGN.md "Team pool")
+# the capabilities a set may give, per scenario: config name -> the per-agent table it fills (rg_team_params)
+TEAM_CAPABILITIES = {"PredatorCapturePrey": {"sensing_radius": "sensing_radius", "capture_radius": "capture_radius",
+                                             "step_dist": "agent_step"},
+                     "MaterialTransport": {"speed": "agent_step", "torque": "torque"},
+                     "Warehouse": {"step_dist": "agent_step"},
+                     "Simple": {"step_dist": "agent_step"}}
+TEAM_SAMPLING = {"episode": TEAM_EPISODE, "fixed": TEAM_FIXED}
+
+
+class TeamPool(object):
+    """C capability sets of an N-agent scenario: [C][N] numpy tables agent_step, sensing_radius, capture_radius (float32) and
+    torque (int32), and the sampling mode (TEAM_EPISODE | TEAM_FIXED).  Tables a scenario does not read hold its own values."""
+
+    TABLES = ("agent_step", "sensing_radius", "capture_radius", "torque")
+
+    def __init__(self, mode, agent_step, sensing_radius, capture_radius, torque):
+        self.mode = int(mode)
+        self.agent_step = np.ascontiguousarray(agent_step, np.float32)
+        self.sensing_radius = np.ascontiguousarray(sensing_radius, np.float32)
+        self.capture_radius = np.ascontiguousarray(capture_radius, np.float32)
+        self.torque = np.ascontiguousarray(torque, np.int32)
+
+    @property
+    def n_sets(self):
+        return int(self.agent_step.shape[0])
+
+    @property
+    def n_agents(self):
+        return int(self.agent_step.shape[1])
+
+    def __eq__(self, other):
+        return isinstance(other, TeamPool) and self.mode == other.mode and all(
+            np.array_equal(getattr(self, k), getattr(other, k)) for k in self.TABLES)
+
+    def __repr__(self):
+        return f"TeamPool(n_sets={self.n_sets}, n_agents={self.n_agents}, mode={self.mode})"
+
+
+def _is_number(v):
+    return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+def team_pool(scenario, cfg, params):
+    """The TeamPool of a config (None without a `teams` key): `teams` is a list of 1..64 mappings from a capability name of
+    the scenario (TEAM_CAPABILITIES) to a list of N numbers; a capability a set leaves out takes the config's own per-agent
+    value (make_params).  `team_sampling`: 'episode' (default: drawn at every episode start) or 'fixed' (env_offset + e mod C).
+    Not part of the reference (it has no pool): without the keys nothing changes."""
+    if scenario not in SCENARIO_IDS:
+        raise KeyError(f"scenario {scenario!r} is not built (have {sorted(SCENARIO_IDS)})")
+    sampling = cfg.get("team_sampling", "episode")
+    if not isinstance(sampling, str) or sampling not in TEAM_SAMPLING:
+        raise ValueError(f"team_sampling must be one of {sorted(TEAM_SAMPLING)} (got {sampling!r})")
+    teams = cfg.get("teams")
+    if teams is None:
+        return None
+    if scenario == "ArcticTransport":
+        raise ValueError("teams: ArcticTransport's agent types are fixed by the scenario (ArcticTransport.py:26-33); it takes no team pool")
+    if lidar_config(cfg)[0] > 0:
+        raise ValueError("teams: a team pool does not combine with the lidar (lidar_rays > 0)")
+    if isinstance(teams, (str, bytes)) or not isinstance(teams, (list, tuple)) or not 1 <= len(teams) <= TEAM_MAX_SETS:
+        raise ValueError(f"teams must be a list of 1..{TEAM_MAX_SETS} capability sets (got {teams!r:.80})")
+    N = int(params.n_agents)
+    caps = TEAM_CAPABILITIES[scenario]
+    own = {"agent_step": [params.agent_step[a] for a in range(N)], "sensing_radius": [params.sensing_radius[a] for a in range(N)],
+           "capture_radius": [params.capture_radius[a] for a in range(N)], "torque": [params.torque[a] for a in range(N)]}
+    tables = {k: np.tile(np.asarray(v, np.float64 if k != "torque" else np.int64), (len(teams), 1)) for k, v in own.items()}
+    for t, st in enumerate(teams):
+        if not isinstance(st, dict):
+            raise ValueError(f"teams[{t}] must be a mapping from a capability name to a list of {N} numbers (got {st!r:.80})")
+        for name, vals in st.items():
+            key = f"teams[{t}].{name}"
+            if name not in caps:
+                raise ValueError(f"{key}: {name!r} is not a capability of {scenario} (have {sorted(caps)})")
+            if isinstance(vals, (str, bytes)) or not hasattr(vals, "__len__") or len(vals) != N:
+                raise ValueError(f"{key} must be a list of n_agents = {N} numbers (got {vals!r:.80})")
+            vals = list(vals)
+            if not all(_is_number(v) for v in vals):
+                raise ValueError(f"{key} must hold numbers (got {vals!r:.80})")
+            if name == "torque":
+                if not all(math.isfinite(float(v)) and float(v) == int(v) and 0 <= int(v) < 2**31 for v in vals):
+                    raise ValueError(f"{key} must hold integers >= 0 (got {vals!r:.80})")
+                tables["torque"][t] = [int(v) for v in vals]
+                continue
+            fv = [float(v) for v in vals]
+            with np.errstate(over="ignore"):   # (a value beyond binary32's range rounds to inf: refused below)
+                finite = all(math.isfinite(v) and math.isfinite(float(np.float32(v))) for v in fv)
+            if name in ("sensing_radius", "capture_radius"):
+                if not finite or not all(v >= 0.0 for v in fv):
+                    raise ValueError(f"{key} must hold finite radii >= 0 (got {vals!r:.80})")
+            elif not finite or not all(v > 0.0 for v in fv):
+                raise ValueError(f"{key} must hold finite values > 0 (got {vals!r:.80})")
+            tables[caps[name]][t] = fv
+    return TeamPool(TEAM_SAMPLING[sampling], tables["agent_step"], tables["sensing_radius"], tables["capture_radius"],
+                    tables["torque"])
 
 
 def params_to_bytes(p):

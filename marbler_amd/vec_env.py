@@ -15,14 +15,15 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .params import lidar_params, load_config, make_params
+from .params import TeamPool, lidar_params, load_config, make_params, team_pool
 
 VIOLATION_MESSAGES = ("", "collision", "boundary", "collision_boundary")  # roboEnv.py:82-94
 
 
 class VecRobotariumEnv(object):
     def __init__(self, scenario, num_envs, config_path=None, overrides=None, device="cuda:0", seed=0,
-                 env_offset=0, auto_reset=True, reference_reset_obs=True, params=None, collect_qp_stats=False, lidar=None):
+                 env_offset=0, auto_reset=True, reference_reset_obs=True, params=None, collect_qp_stats=False, lidar=None,
+                 teams=None):
         """scenario: 'PredatorCapturePrey' | 'Warehouse' | 'MaterialTransport' | 'Simple' | 'ArcticTransport'
         (wrapper.py:12-16).
         config_path / overrides: the reference's scenario YAML (same keys) and a dict of overrides.
@@ -34,7 +35,10 @@ class VecRobotariumEnv(object):
             False returns the observation of the fresh state (get_obs()).
         params: a ready RgScenarioParams (e.g. received by broadcast) instead of a config.
         lidar: with `params`, its RgLidarParams (params.lidar_params; dist.broadcast_lidar), or None for no lidar.  From a config
-            the keys `lidar_rays` / `lidar_range` decide (DESIGN.md "Lidar")."""
+            the keys `lidar_rays` / `lidar_range` decide (DESIGN.md "Lidar").
+        teams: a params.TeamPool (params.team_pool; dist.broadcast_teams) or the config's `teams` list (sampled per episode), or
+            None: from a config the keys `teams` / `team_sampling` decide (DESIGN.md "Team pool").  With a pool every env draws
+            one of its capability sets per episode; `team_index` [E] int32 says which (part of the state)."""
         self.lib = _lib.load()
         self.scenario = scenario
         self.cfg = None
@@ -43,9 +47,19 @@ class VecRobotariumEnv(object):
             params = make_params(scenario, self.cfg)
             if lidar is None:
                 lidar = lidar_params(scenario, self.cfg, params)
+            if teams is None:
+                teams = team_pool(scenario, self.cfg, params)
         if lidar is not None and int(lidar.rays) == 0:
             lidar = None
+        if teams is not None and not isinstance(teams, TeamPool):
+            teams = team_pool(scenario, {"teams": teams}, params)
+        if teams is not None:
+            if teams.n_agents != int(params.n_agents):
+                raise ValueError(f"teams: the pool is built for {teams.n_agents} agents, the scenario has {int(params.n_agents)}")
+            if lidar is not None:
+                raise ValueError("teams: a team pool does not combine with the lidar (lidar_rays > 0)")
         self.params = params
+        self.teams = teams   # params.TeamPool or None
         self.lidar = lidar   # RgLidarParams or None: the last lidar.rays columns of every observation row
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -99,6 +113,15 @@ class VecRobotariumEnv(object):
             self.next_episode = zeros((E,), i32, fill=-1)
         self._alloc_outputs()
         self.qp_sweeps = zeros((E,), i32) if collect_qp_stats else None
+        # ---- team pool (rg_team_params): the [C][N] tables and every env's set index (state)
+        self.team_index = self.team_table = None
+        if teams is not None:
+            self.team_index = zeros((E,), i32)
+            self.team_table = {}
+            for k in TeamPool.TABLES:
+                v = getattr(teams, k)
+                self.team_table[k] = zeros(v.shape, i32 if k == "torque" else f32)
+                self.team_table[k].copy_(torch.as_tensor(v))
 
         if dev.index is None:
             self.device = dev = torch.device("cuda", torch.cuda.current_device())
@@ -123,6 +146,17 @@ class VecRobotariumEnv(object):
                 self.lib.rg_destroy(self._h)
                 self._h = None
                 raise (ValueError if -60 < rc <= -50 else _lib.RobogymError)(msg)
+        if self.teams is not None:
+            tt = self.team_table
+            self._team_params = _lib.RgTeamParams(self.teams.n_sets, self.teams.mode, tt["agent_step"].data_ptr(),
+                                                  tt["sensing_radius"].data_ptr(), tt["capture_radius"].data_ptr(),
+                                                  tt["torque"].data_ptr(), self.team_index.data_ptr())
+            rc = self.lib.rg_set_teams(self._h, C.byref(self._team_params))
+            if rc != 0:
+                msg = "rg_set_teams failed (%d): %s" % (rc, self.lib.rg_last_error().decode())
+                self.lib.rg_destroy(self._h)
+                self._h = None
+                raise (ValueError if -70 < rc <= -60 else _lib.RobogymError)(msg)
         self._io = _lib.RgStepIO(self.obs.data_ptr(), self.reward.data_ptr(), self.done_u8.data_ptr(),
                                  self.dist_travelled.data_ptr(), self.violation.data_ptr(),
                                  self.remaining.data_ptr(),
@@ -398,6 +432,8 @@ class VecRobotariumEnv(object):
     def state_dict(self):
         """Snapshot of the env state (cloned tensors) + the sampler key, loadable with load_state_dict()."""
         sd = {k: getattr(self, k).clone() for k in self.STATE_KEYS}
+        if self.team_index is not None:
+            sd["team_index"] = self.team_index.clone()   # the team of every env's running episode (team pool only)
         if self.elapsed is not None:
             sd["elapsed"] = self.elapsed.clone()     # gym TimeLimit's counter (enable_time_limit)
         sd["seed"] = torch.tensor([self.seed & 0xFFFFFFFF, self.seed >> 32], dtype=torch.int64)
@@ -413,7 +449,9 @@ class VecRobotariumEnv(object):
         if self.elapsed is None and "elapsed" in sd:
             raise KeyError("snapshot carries 'elapsed' (gym TimeLimit counter) but this env has no time limit: call "
                            "enable_time_limit() first, or drop the key")
-        unknown = [k for k in sd if k != "seed" and k != "elapsed" and k not in self.STATE_KEYS]
+        if self.team_index is None and "team_index" in sd:
+            raise KeyError("snapshot carries 'team_index' (team pool) but this env has no team pool")
+        unknown = [k for k in sd if k not in ("seed", "elapsed", "team_index") and k not in self.STATE_KEYS]
         if unknown:
             raise KeyError(f"unknown snapshot keys {unknown}")
         if self.next_episode is not None:
