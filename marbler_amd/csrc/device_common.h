@@ -74,6 +74,23 @@ __device__ __forceinline__ float cross_lane(float v) {
     return __builtin_bit_cast(float, cross_lane_i<M>(__builtin_bit_cast(int, v)));
 }
 
+// 16-lane rows of two 8-lane halves (step_group.h, the SPAN kernels).  DPP bank_mask picks the lanes a move writes (bank i = lanes
+// 4i .. 4i + 3 of the row); the others keep `v`.
+// to_lower_half: the lower half gets the upper half's v (row_ror:8), the upper half keeps its own; to_upper_half the other way round
+__device__ __forceinline__ float to_lower_half(float v) {
+    const int b = __builtin_bit_cast(int, v);
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(b, b, 0x128, 0xF, 0x3, false));
+}
+__device__ __forceinline__ float to_upper_half(float v) {
+    const int b = __builtin_bit_cast(int, v);
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(b, b, 0x128, 0xF, 0xC, false));
+}
+// the upper half mirrored in itself (lane 8 + a <- lane 8 + (7 - a): row_half_mirror), the lower half unchanged
+__device__ __forceinline__ float mirror_upper_half(float v) {
+    const int b = __builtin_bit_cast(int, v);
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(b, b, 0x141, 0xF, 0xC, false));
+}
+
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 // d[i] <- bits of d[i].x * d[i].x + d[i].y * d[i].y in binary32, i < K: VOP3P v_dot2_f32_f16 with a literal-zero addend
 // (the compiler's own selection for __builtin_amdgcn_fdot2 is v_dot2c, which costs an extra v_mov to clear the

@@ -28,6 +28,7 @@ struct rg_handle {
     bool default_tpe;    // use_tpe as rg_create chose it (restored when the lidar and the team pool are both off)
     rg_lidar_params lidar;   // rays == 0: off (rg_set_lidar)
     rg_team_params teams;    // n_sets == 0: no pool (rg_set_teams)
+    bool span;           // rg_step's lane-group launch may put an env on a 16-lane row (step_group.h); RG_STEP_SPAN=0 forces 8-lane groups
 };
 
 // Which step kernel: both give identical results.  The lane-group kernel has the shorter chain for
@@ -224,6 +225,10 @@ rg_handle *rg_create(const rg_scenario_params *params, int32_t num_envs, int64_t
         else if (!strcmp(force, "tpe") && rg::tpe_supported(*params)) h->use_tpe = true;
     }
     h->default_tpe = h->use_tpe;
+    {
+        const char *span = getenv("RG_STEP_SPAN");
+        h->span = !(span && !strcmp(span, "0"));
+    }
     memset(&h->lidar, 0, sizeof(h->lidar));
     memset(&h->teams, 0, sizeof(h->teams));
     return h;
@@ -381,6 +386,7 @@ int rg_step(rg_handle *h, const int32_t *actions, const rg_step_io *io, int32_t 
     if (h->lidar.rays)
         return launched(h->params.qp_mode == RG_QP_CVXOPT ? rg::launch_lidar_step_ipm(a, h->lidar, h->stream)
                                                           : rg::launch_lidar_step(a, h->lidar, h->stream));
+    if (!h->span) a.envs_per_wave = -1;   // asks launch_step for 8-lane groups throughout (it sets the real value itself)
     return launched(h->use_tpe ? rg::launch_step_tpe(a, h->stream) : rg::launch_step(a, false, h->stream));
 }
 

@@ -54,7 +54,9 @@ static_assert(CHUNK >= 1 && CHUNK <= 5, "the sparse collision pre-test covers su
 // followed by Robotarium.set_velocities' clipping.  Called in wave-uniform control flow.
 // QPM: how the certificate's QP is evaluated (include/robogym.h RG_QP_*): 0 the exact projection by the Hildreth sweeps below,
 // 1 cvxopt's interior-point iterate (ipm_qp.h; qp = the wave's LDS of that mode: one record per lane, one workspace per env).
-template <int GW, int QPM = 0, typename QpLds = void>
+// SPAN (16-lane rows, step_once): the pair constants are split between the group and its replica (below); the sweeps run in
+// the group, and the replica takes the result over.
+template <int GW, int QPM = 0, typename QpLds = void, bool SPAN = false>
 __device__ __forceinline__ int controller(const rg_scenario_params &p, const Consts &k, int N, int ag, bool lane_ok,
                                           bool upd, float x, float y, float c, float s, float gx, float gy, float &v,
                                           float &w, QpLds *qp RG_CTRL_TICKS_PARAM) {
@@ -113,9 +115,8 @@ __device__ __forceinline__ int controller(const rg_scenario_params &p, const Con
     const bool has_unsafe = p.barrier_has_unsafe_gain != 0;
     float ex[GW - 1], ey[GW - 1], fx[GW - 1], fy[GW - 1], bp[GW - 1], emax[GW - 1];
     float mu[GW - 1], dmu[GW - 1];  // dmu: the change of mu over sweep 2 (d1), then over sweep 3 (d2), of a block of four sweeps
-    static_for<1, GW>([&](auto KK) {
-        constexpr int K = decltype(KK)::value;
-        const float pxi = xor_lane<K>(xix), pyi = xor_lane<K>(xiy);
+    // the constants of the pair (this lane's agent, agent ag ^ K) from the partner's (pxi, pyi) into slot i of the arrays
+    auto pair_consts = [&](float pxi, float pyi, int K, int i) {
         const float dx = xix - pxi, dy = xiy - pyi;
         const float ee = dx * dx + dy * dy;
         const float h = ee - k.r2;
@@ -124,14 +125,53 @@ __device__ __forceinline__ int controller(const rg_scenario_params &p, const Con
         const float n2 = 2.0f * ee;
         const bool ok = lane_ok & ((ag ^ K) < N) & (n2 > 0.0f);
         const float rn2 = ok ? 1.0f / n2 : 0.0f;
-        ex[K - 1] = dx;
-        ey[K - 1] = dy;
-        fx[K - 1] = dx * rn2;
-        fy[K - 1] = dy * rn2;
-        bp[K - 1] = (0.5f * b) * rn2;
-        emax[K - 1] = ok ? fmaxf(__builtin_fabsf(dx), __builtin_fabsf(dy)) : 0.0f;
-        mu[K - 1] = dmu[K - 1] = 0.0f;
-    });
+        ex[i] = dx;
+        ey[i] = dy;
+        fx[i] = dx * rn2;
+        fy[i] = dy * rn2;
+        bp[i] = (0.5f * b) * rn2;
+        emax[i] = ok ? fmaxf(__builtin_fabsf(dx), __builtin_fabsf(dy)) : 0.0f;
+    };
+    const bool helper = SPAN && (threadIdx.x & GW) != 0;
+    if constexpr (SPAN) {
+        // Four rounds' worth of work instead of seven.  The replica's partner values are mirrored first (lane 8 + a holds agent
+        // a ^ 7), so that ONE quad permute xor S pairs the group's lane a with agent a ^ S (rounds 1..3) and the replica's lane
+        // 8 + a with agent a ^ S ^ 7 (rounds 6, 5, 4); "S = 0" is round 7 in the replica (and an absent pair in the group).
+        // Slot S keeps its result in array slot 7 - S - 1 for now; the group then fetches the replica's rounds 4..7 across
+        // the row, one row_ror:8 move per value.  The same operations on the same operands as the seven rounds: same bits.
+        static_assert(GW == 8, "16-lane rows of two 8-lane halves");
+        const float mx = mirror_upper_half(xix), my = mirror_upper_half(xiy);
+        static_for<0, 4>([&](auto SS) {
+            constexpr int S = decltype(SS)::value;
+            const int K = helper ? S ^ 7 : S;
+            if constexpr (S == 0) pair_consts(mx, my, K, 6);
+            else pair_consts(xor_lane<S>(mx), xor_lane<S>(my), K, (S ^ 7) - 1);
+        });
+        static_for<1, 4>([&](auto SS) {   // the group: rounds 1..3 its own, 4..6 and 7 (already in place) from the replica
+            constexpr int S = decltype(SS)::value, J = (S ^ 7) - 1;
+            ex[S - 1] = ex[J];
+            ey[S - 1] = ey[J];
+            fx[S - 1] = fx[J];
+            fy[S - 1] = fy[J];
+            bp[S - 1] = bp[J];
+            emax[S - 1] = emax[J];
+        });
+        static_for<3, 7>([&](auto JJ) {
+            constexpr int J = decltype(JJ)::value;
+            ex[J] = to_lower_half(ex[J]);
+            ey[J] = to_lower_half(ey[J]);
+            fx[J] = to_lower_half(fx[J]);
+            fy[J] = to_lower_half(fy[J]);
+            bp[J] = to_lower_half(bp[J]);
+            emax[J] = to_lower_half(emax[J]);
+        });
+    } else {
+        static_for<1, GW>([&](auto KK) {
+            constexpr int K = decltype(KK)::value;
+            pair_consts(xor_lane<K>(xix), xor_lane<K>(xiy), K, K - 1);
+        });
+    }
+    static_for<0, GW - 1>([&](auto KK) { mu[decltype(KK)::value] = dmu[decltype(KK)::value] = 0.0f; });
     RG_CTRL_PIN_ROUNDS(GW, fx, bp, emax)
     RG_CTRL_TICK(0);  // position controller + pair constants
     {   // "Threshold control inputs before QP": decided on squares; never taken after the 0.15 clip
@@ -147,7 +187,7 @@ __device__ __forceinline__ int controller(const rg_scenario_params &p, const Con
     // A group drops out when converged (its lanes are exec-masked for the whole sweep body: groups
     // are uniform, so an active lane never reads a masked partner); the wave loops while any group
     // is active.
-    bool active = upd;
+    bool active = upd & !helper;   // (SPAN: the replica holds rounds of its own in the arrays; it takes the group's result below)
     int sweeps = 0, my_sweeps = 0;
     // one sweep over the GW-1 rounds + the convergence test; PHASE = sweep number mod 4 selects the
     // restart bookkeeping: d1 and d2 of oracle_core.h (the changes of the multipliers over sweeps 2 and 3 of a block of four)
@@ -212,6 +252,10 @@ __device__ __forceinline__ int controller(const rg_scenario_params &p, const Con
         sweep(std::integral_constant<int, 3>{});
         if (!__any(active)) break;
         sweep(std::integral_constant<int, 0>{});
+    }
+    if constexpr (SPAN) {
+        ux = to_upper_half(ux);
+        uy = to_upper_half(uy);
     }
     RG_CTRL_PIN2(ux, uy);
     RG_CTRL_TICK(1);  // sweeps
@@ -319,11 +363,18 @@ __device__ __forceinline__ void write_neighbour_obs(Lds<GW> &lds, int N, int Knb
 // LIDAR: the range block of `lid` (lidar.h) goes after the scenario's own columns.  Its own instantiations (lidar_kernels.h).
 // TEAM: the agents' capabilities come from set team_index[e] of the pool `tm` (team.h), and an episode that starts here draws
 // the env's next index.  Its own instantiations (team_kernels.h).
+// SPAN: an env owns a whole 16-lane DPP row (GW = 8): lanes 8..15 of the row (the "helper" half) run a bit-identical replica of
+// lanes 0..7 -- same loads, same code, same votes -- and take over part of the env's order-free work (the sparse and dense
+// collision pre-tests, whose result is a minimum over pairs and sub-steps); they make no global store.  Every DPP exchange and
+// reduction at GW = 8 stays inside its 8-lane half (quad permutes, row_half_mirror), so no value mixes the two halves except
+// where a result is brought across on purpose (row_ror:8, xor_lane_i<8>).
 template <int SCN, int GW, bool OBS_ONLY, int NT, bool AHEAD, bool GYM, int QPM = 0, typename QpLds = void, typename Sync = WgSync,
-          bool LIDAR = false, bool TEAM = false>
+          bool LIDAR = false, bool TEAM = false, bool SPAN = false>
 __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, const StepView &sv, QpLds *qp_lds = nullptr,
                                           const rg_lidar_params *lid = nullptr, const rg_team_params *tm = nullptr) {
-    constexpr int EPW = WAVE / GW;  // envs per wave
+    static_assert(!SPAN || (GW == 8 && QPM == 0 && !GYM && !LIDAR && !TEAM), "the 16-lane rows: exact mode, GW = 8, no side blocks");
+    constexpr int RW = SPAN ? 2 * GW : GW;  // lanes per env
+    constexpr int EPW = WAVE / RW;  // envs per wave
     RG_STAMPS_BEGIN()
     const rg_scenario_params &p = a.p;
     const Consts &k = a.k;
@@ -366,13 +417,15 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     const int N = NT > 0 ? NT : q_N;
     const int lane = threadIdx.x;
     const int ag = lane & (GW - 1);
-    const int g = lane / GW;
-    const int gbase = lane & ~(GW - 1);
+    const int g = lane / RW;
+    const int gbase = lane & ~(RW - 1);   // (with SPAN, group reads of LDS rows and ballots see the lower half of the row)
+    const bool helper = SPAN && (lane & GW) != 0;
     const int epw = q_epw > 0 ? q_epw : EPW;
     const int chunk = xcd_chunk(q_G);
     const int e = chunk * epw + g;
     const bool env_ok = (g < epw) & (e < q_E);
     const bool lane_ok = env_ok && ag < N;
+    const bool env_st = env_ok & !helper, lane_st = lane_ok & !helper;   // the lanes that store
     const size_t eN = static_cast<size_t>(e) * N;
 
     // ---- loads, ALL issued before anything waits for one of them (coalesced: a wave covers EPW consecutive
@@ -604,7 +657,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         for (int it0 = 0; it0 < U; it0 += period) {
             const int n = (U - it0) < period ? (U - it0) : period;
             RG_HEADING_SINCOS(th, s, c);
-            const int sw = controller<GW, QPM>(p, k, N, ag, lane_ok, env_ok & !dead, x, y, c, s, gx, gy, v, w, qp_lds RG_CTRL_TICKS_ARG);
+            const int sw = controller<GW, QPM, QpLds, SPAN>(p, k, N, ag, lane_ok, env_ok & !dead, x, y, c, s, gx, gy, v, w, qp_lds RG_CTRL_TICKS_ARG);
             max_sweeps = sw > max_sweeps ? sw : max_sweeps;
             const float dtv = k.dt * v, dtw = k.dt * w;
             float sd, cd;
@@ -691,20 +744,41 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                 {
                     constexpr int SPAN0 = C - 1 < 2 ? C - 1 : 2;
                     const int t0 = SPAN0 == 0 ? thr_pre : SPAN0 == 1 ? thr_s1 : thr_s2;
-                    dmin_u[0] = pair_min(q[0]);
-                    sparse_hit = sparse_hit | (dmin_u[0] <= t0);
-                    if constexpr (C >= 4) {
+                    if constexpr (SPAN && C >= 4) {
+                        // the group tests sub-step 0, its replica sub-step 3; the wave's vote below ORs the two halves' hits,
+                        // and each half's minimum goes across only if the chunk goes on to the dense pre-test
                         const int t3 = C == 4 ? thr_pre : thr_s1;
-                        dmin_u[3] = pair_min(q[3]);
-                        sparse_hit = sparse_hit | (dmin_u[3] <= t3);
+                        const int dm = pair_min(helper ? q[3] : q[0]);
+                        sparse_hit = sparse_hit | (dm <= (helper ? t3 : t0));
+                        dmin_u[0] = dmin_u[3] = dm;
+                    } else {
+                        dmin_u[0] = pair_min(q[0]);
+                        sparse_hit = sparse_hit | (dmin_u[0] <= t0);
+                        if constexpr (C >= 4) {
+                            const int t3 = C == 4 ? thr_pre : thr_s1;
+                            dmin_u[3] = pair_min(q[3]);
+                            sparse_hit = sparse_hit | (dmin_u[3] <= t3);
+                        }
                     }
                 }
                 if (penalize && __any(sparse_hit | bnd_any)) {
                 RG_CHUNK_DENSE_BEGIN()
-                static_for<1, C>([&](auto UU) {
-                    constexpr int u = decltype(UU)::value;
-                    if constexpr (u != 3) dmin_u[u] = pair_min(q[u]);
-                });
+                if constexpr (SPAN && C >= 4) {  // sub-step 0's minimum from the group, 3's from the replica, into both halves
+                    const int mine = dmin_u[0], other = xor_lane_i<8>(mine);
+                    dmin_u[0] = helper ? other : mine;
+                    dmin_u[3] = helper ? mine : other;
+                }
+                if constexpr (SPAN && C >= 3) {  // sub-steps 1 and 2 side by side in the two halves; 4 (C = 5) in both
+                    const int mine = pair_min(helper ? q[2] : q[1]), other = xor_lane_i<8>(mine);
+                    if constexpr (C == 5) dmin_u[4] = pair_min(q[4]);
+                    dmin_u[1] = helper ? other : mine;
+                    dmin_u[2] = helper ? mine : other;
+                } else {
+                    static_for<1, C>([&](auto UU) {
+                        constexpr int u = decltype(UU)::value;
+                        if constexpr (u != 3) dmin_u[u] = pair_min(q[u]);
+                    });
+                }
                 int dmin = dmin_u[0];
                 static_for<1, C>([&](auto UU) { dmin = dmin_u[decltype(UU)::value] < dmin ? dmin_u[decltype(UU)::value] : dmin; });
                 RG_CHUNK_DENSE_END(dmin)
@@ -811,7 +885,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     RG_LATE(nx_tag);
     const bool have_next = ahead & (nx_tag == rc_raw);  // the block holds exactly the episode that would start now
     const bool next_early = env_ok & have_next & ((viol != 0) | (steps > p.max_episode_steps));
-    if constexpr (AHEAD) load_next(next_early);
+    if constexpr (AHEAD) load_next(next_early & !helper);
 
     if constexpr (SCN == RG_SCN_PREDATOR_CAPTURE_PREY) {
         const int P = q_P;
@@ -873,7 +947,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                 c_b = group_or<GW>(c_b);
                 nsen_lo = sen_lo | (s_b & ~cap_lo);            // sensed: any agent in range, prey not yet captured
                 ncap_lo = cap_lo | (nsen_lo & c_b & ~cap_lo);  // captured: sensed and a 'no_action' agent in range
-                if (env_ok && ag < P) {
+                if (env_st && ag < P) {
                     a.st.prey_sensed[static_cast<size_t>(e) * P + ag] = (nsen_lo >> ag) & 1u;
                     a.st.prey_captured[static_cast<size_t>(e) * P + ag] = (ncap_lo >> ag) & 1u;
                 }
@@ -914,7 +988,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                 nsen_hi = sen_hi | (s_hi & ~cap_hi);
                 ncap_hi = cap_hi | (nsen_hi & c_hi & ~cap_hi);
             }
-            if (env_ok) {
+            if (env_st) {
                 for (int i = ag; i < P; i += GW) {
                     const uint32_t sw_ = i < 32 ? nsen_lo >> i : nsen_hi >> (i - 32);
                     const uint32_t cw_ = i < 32 ? ncap_lo >> i : ncap_hi >> (i - 32);
@@ -947,14 +1021,14 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         lds.own[lane][5] = cr;
         Sync::sync();
         if (od == 6) {
-            if (lane_ok) {
+            if (lane_st) {
 #pragma unroll
                 for (int cc = 0; cc < 6; ++cc) obs_row[cc] = lds.own[lane][cc];
             }
-            write_neighbour_obs<GW, 6, NT>(lds, N, p.num_neighbors, ag, gbase, lane_ok, x, y, obs_row);
+            write_neighbour_obs<GW, 6, NT>(lds, N, p.num_neighbors, ag, gbase, lane_st, x, y, obs_row);
         } else {
-            if (lane_ok) out_store4(obs_row, x, y, qx, qy);
-            write_neighbour_obs<GW, 4, NT>(lds, N, p.num_neighbors, ag, gbase, lane_ok, x, y, obs_row);
+            if (lane_st) out_store4(obs_row, x, y, qx, qy);
+            write_neighbour_obs<GW, 4, NT>(lds, N, p.num_neighbors, ag, gbase, lane_st, x, y, obs_row);
         }
         RG_STAMP_E(1);  // observations written
         if constexpr (!OBS_ONLY) {  // a14 reward / termination (PredatorCapturePrey.py:155-176, 209-216)
@@ -981,12 +1055,12 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         lds.own[lane][1] = y;
         lds.own[lane][2] = loaded ? 1.0f : 0.0f;
         Sync::sync();
-        if (lane_ok) {
+        if (lane_st) {
             obs_row[0] = x;
             obs_row[1] = y;
             obs_row[2] = loaded ? 1.0f : 0.0f;
         }
-        write_neighbour_obs<GW, 3, NT>(lds, N, p.num_neighbors, ag, gbase, lane_ok, x, y, obs_row);
+        write_neighbour_obs<GW, 3, NT>(lds, N, p.num_neighbors, ag, gbase, lane_st, x, y, obs_row);
         if constexpr (!OBS_ONLY) {
             if (viol) {
                 reward = p.violation_reward;
@@ -1005,20 +1079,20 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                     }
                 }
                 done = steps > p.max_episode_steps;
-                if (lane_ok) a.st.loaded[eN + ag] = static_cast<uint8_t>(loaded);
+                if (lane_st) a.st.loaded[eN + ag] = static_cast<uint8_t>(loaded);
             }
         }
     } else if constexpr (SCN == RG_SCN_SIMPLE) {  // scenarios/Simple/simple.py:155-225
         lds.own[lane][0] = x;
         lds.own[lane][1] = y;
         Sync::sync();
-        if (lane_ok) {
+        if (lane_st) {
             obs_row[0] = x;
             obs_row[1] = y;
             obs_row[2 * N] = goal_x;
             obs_row[2 * N + 1] = goal_y;
         }
-        write_neighbour_obs<GW, 2, NT>(lds, N, N - 1, ag, gbase, lane_ok, x, y, obs_row);  // all others, index order
+        write_neighbour_obs<GW, 2, NT>(lds, N, N - 1, ag, gbase, lane_st, x, y, obs_row);  // all others, index order
         if constexpr (!OBS_ONLY) {
             if (viol) {
                 reward = p.violation_reward;
@@ -1124,7 +1198,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             if (!OBS_ONLY && i < N) msg[i] = msg[i] % 4;  // MaterialTransport.py:119-120
         }
         if constexpr (TEAM) RG_LATE(tq_raw);
-        if (lane_ok) {
+        if (lane_st) {
             obs_row[0] = x;
             obs_row[1] = y;
             obs_row[2] = static_cast<float>(load);
@@ -1199,12 +1273,12 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                 for (int j = 0; j < N; ++j) total += lds.aload[gbase + j];
             }
             if (done) remaining = zone0 + zone1 + total;
-            if (lane_ok) a.st.load[eN + ag] = load;
-            if (lane_ok && ag == 0) {
+            if (lane_st) a.st.load[eN + ag] = load;
+            if (lane_st && ag == 0) {
                 a.st.zone_load[2 * e] = zone0;
                 a.st.zone_load[2 * e + 1] = zone1;
             }
-            if (lane_ok && ag < 4) a.st.messages[4 * e + ag] = msg[ag == 0 ? 0 : ag == 1 ? 1 : ag == 2 ? 2 : 3];
+            if (lane_st && ag < 4) a.st.messages[4 * e + ag] = msg[ag == 0 ? 0 : ag == 1 ? 1 : ag == 2 ? 2 : 3];
         }
     }
 
@@ -1229,7 +1303,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             for (int j = 0; j < N; ++j) rsum = rsum + lds.ax[gbase + j];
         }
         // ---- stores
-        if (lane_ok) {
+        if (lane_st) {
             float *X = a.st.poses + eN * 3;
             X[ag] = x;
             X[N + ag] = y;
@@ -1277,9 +1351,9 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         // an env whose block holds exactly the episode that starts now copies it; any other runs the sampler
         if (a.auto_reset && __any(env_ok & ended)) {
             Sync::sync();  // the wave's state stores are issued before the resetting lanes rewrite them
-            if constexpr (AHEAD) load_next(env_ok & ended & have_next & !next_early);  // ended some other way: fetched late
-            if (__any(env_ok & ended & !have_next)) reset_group<SCN, GW, Sync>(a, lds, e, g, ag, env_ok & ended & !have_next, rc_raw);
-            if (env_ok & ended & have_next) {  // the same stores reset_group makes with commit = true
+            if constexpr (AHEAD) load_next(env_st & ended & have_next & !next_early);  // ended some other way: fetched late
+            if (__any(env_ok & ended & !have_next)) reset_group<SCN, GW, Sync>(a, lds, e, g, ag, env_st & ended & !have_next, rc_raw);
+            if (env_st & ended & have_next) {  // the same stores reset_group makes with commit = true
                 if (ag < N) {
                     float *X = a.st.poses + eN * 3;
                     X[ag] = nx_pose[0];
@@ -1334,7 +1408,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         // replayed -- leaves the draw to a later launch (an env that finishes before it happened runs the sampler as
         // before): the draw must not lengthen the waves the launch is waiting for.
         if (AHEAD && ahead && !(replayed | __any(max_sweeps > 2)) && __any(env_ok & !ended & !have_next)) {
-            const bool need = env_ok & !ended & !have_next;
+            const bool need = env_st & !ended & !have_next;
             Sync::sync();  // (LDS scratch of a reset above is free again)
             reset_group<SCN, GW, Sync>(a, lds, e, g, ag, need, rc_raw, reset_dst_next(a, e));
             if (need && ag == 0) a.st.next_episode[e] = rc_raw;
@@ -1351,8 +1425,8 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
 // 313 VGPRs) and would slow the single-step launch down.
 // QPM = RG_QP_CVXOPT: the certificate's QP by the interior-point iteration of ipm_qp.h.  Its own instantiations (generic agent
 // count): the launch is then dominated by that iteration (about ten times the rest of the step), and it needs one wave per SIMD.
-template <int SCN, int GW, bool OBS_ONLY, int NT, bool ROLLOUT, bool GYM = false, int QPM = 0>
-__global__ __launch_bounds__(WAVE) void step_kernel(const KernelArgs a) {
+template <int SCN, int GW, bool OBS_ONLY, int NT, bool ROLLOUT, bool GYM, int QPM, bool SPAN>
+__device__ __forceinline__ void step_kernel_body(const KernelArgs &a) {
     __shared__ Lds<GW> lds;
     const int N = NT > 0 ? NT : a.p.n_agents;
     if constexpr (QPM == RG_QP_CVXOPT) {
@@ -1366,6 +1440,9 @@ __global__ __launch_bounds__(WAVE) void step_kernel(const KernelArgs a) {
                 step_once<SCN, GW, OBS_ONLY, NT, false, false, QPM>(a, lds, step_view(a, t, N, a.p.obs_dim), &qp_lds);
             }
         }
+    } else if constexpr (SPAN) {
+        static_assert(!ROLLOUT && !OBS_ONLY, "the 16-lane rows: the single-step launch");
+        step_once<SCN, GW, false, NT, true, GYM, QPM, void, WgSync, false, false, true>(a, lds, step_view(a, 0, N, a.p.obs_dim));
     } else if constexpr (!ROLLOUT) {
         step_once<SCN, GW, OBS_ONLY, NT, true, GYM, QPM>(a, lds, step_view(a, 0, N, a.p.obs_dim), static_cast<void *>(nullptr));
     } else {
@@ -1374,6 +1451,17 @@ __global__ __launch_bounds__(WAVE) void step_kernel(const KernelArgs a) {
             step_once<SCN, GW, OBS_ONLY, NT, false, false, QPM>(a, lds, step_view(a, t, N, a.p.obs_dim), static_cast<void *>(nullptr));
         }
     }
+}
+
+template <int SCN, int GW, bool OBS_ONLY, int NT, bool ROLLOUT, bool GYM = false, int QPM = 0>
+__global__ __launch_bounds__(WAVE) void step_kernel(const KernelArgs a) {
+    step_kernel_body<SCN, GW, OBS_ONLY, NT, ROLLOUT, GYM, QPM, false>(a);
+}
+// ROW = 16: one env per 16-lane row (step_once SPAN), 4 envs per wave; the single-step exact-mode launch with GW = 8 only
+// (step_kernel<SCN, 8, false, NT, false, 16>).  A template of its own, so that every existing instantiation keeps its name.
+template <int SCN, int GW, bool OBS_ONLY, int NT, bool ROLLOUT, int ROW, std::enable_if_t<ROW == 16, int> = 0>
+__global__ __launch_bounds__(WAVE) void step_kernel(const KernelArgs a) {
+    step_kernel_body<SCN, GW, OBS_ONLY, NT, ROLLOUT, false, 0, true>(a);
 }
 
 template <int SCN, int GW>
@@ -1432,6 +1520,20 @@ static hipError_t launch_step_scn(const KernelArgs &a_in, hipStream_t stream) {
             if (gw == 4) hipLaunchKernelGGL((step_kernel<SCN, 4, false, 0, false, true>), dim3(grid), dim3(WAVE), 0, stream, a);
             else if (gw == 16) hipLaunchKernelGGL((step_kernel<SCN, 16, false, 0, false, true>), dim3(grid), dim3(WAVE), 0, stream, a);
             else hipLaunchKernelGGL((step_kernel<SCN, 8, false, 0, false, true>), dim3(grid), dim3(WAVE), 0, stream, a);
+            return hipGetLastError();
+        }
+    }
+    if constexpr (!OBS_ONLY && !ROLLOUT && !kStampsBuild) {
+        // at most 4 envs per wave (batches up to 4096 envs): each env on a 16-lane row, the upper half a replica that takes over
+        // part of the order-free work (step_once SPAN).  A negative envs_per_wave on entry (rg_step under RG_STEP_SPAN=0, rg_create)
+        // keeps 8-lane groups.
+        if (a_in.envs_per_wave >= 0 && gw == 8 && epw <= 4) {
+            switch (a.p.n_agents) {
+                case 5: hipLaunchKernelGGL((step_kernel<SCN, 8, false, 5, false, 16>), dim3(grid), dim3(WAVE), 0, stream, a); break;
+                case 6: hipLaunchKernelGGL((step_kernel<SCN, 8, false, 6, false, 16>), dim3(grid), dim3(WAVE), 0, stream, a); break;
+                case 7: hipLaunchKernelGGL((step_kernel<SCN, 8, false, 7, false, 16>), dim3(grid), dim3(WAVE), 0, stream, a); break;
+                default: hipLaunchKernelGGL((step_kernel<SCN, 8, false, 8, false, 16>), dim3(grid), dim3(WAVE), 0, stream, a); break;
+            }
             return hipGetLastError();
         }
     }
