@@ -29,7 +29,8 @@ extern "C" {
 
 /* 7: + rg_policy_rollout() and rg_policy_io (T actor steps and env steps in one launch), rg_sizeof_policy_io(); later, purely
  * additive (no existing layout or entry point changed): + rg_set_lidar(), rg_lidar_params, rg_sizeof_lidar_params(); + rg_set_teams(),
- * rg_team_params, rg_sizeof_team_params().
+ * rg_team_params, rg_sizeof_team_params(); + rg_actor_forward_sample(), rg_policy_rollout_sample(), rg_policy_sample,
+ * rg_sizeof_policy_sample() (soft-policies action sampling).
  * 6 (round 5): rg_scenario_params ends in the barrier-QP solver selection (qp_mode + cvxopt's options): RG_QP_CVXOPT computes the
  * interior-point iterate the reference's stack computes (utilities/controller.py:13-16,23) instead of the exact projection;
  * rg_step_io.zero_obs_on_end; + rg_actor_forward_explore(), rg_actor_pack_gru_f16x2() and rg_actor_weights.gru_packed == 3.
@@ -343,6 +344,17 @@ int rg_actor_forward(const rg_actor_weights *w, int32_t num_envs, int32_t n_agen
 int rg_actor_forward_explore(const rg_actor_weights *w, int32_t num_envs, int32_t n_agents, const float *obs,
                              int32_t obs_dim, int32_t append_agent_id, const uint8_t *restart, float *hidden, float *q,
                              int32_t *actions, const float *explore_u, float epsilon, void *hip_stream);
+/* The same launch with the soft-policies selection of EPyMARL's action selectors (SoftPoliciesSelector, external to the reference:
+ * what the zoo's MAPPO checkpoints collect data with: "action_selector": "soft_policies", "agent_output_type": "pi_logits") folded
+ * in: the action is SAMPLED from softmax(q) and prob [E][N] (or NULL) receives the probability it had.  sample_u [E][N] holds one
+ * uniform draw in [0, 1) per agent.  The rule, in binary32, per agent row: m = the row maximum of q as written; e_c =
+ * soft_exp(q_c - m), an explicit sequence of IEEE operations (csrc/actor_common.h states it; no library or hardware exponential);
+ * c_k = the partial sums of ((e_0 + e_1) + e_2) + ... in column order, Z the last; the action is the first k with u * Z < c_k, or
+ * the last k with e_k > 0 if there is none; prob = e_action / Z.  A row whose maximum is not finite (a NaN, +inf, all -inf) takes
+ * the greedy action and prob = NaN.  q and hidden are what rg_actor_forward writes.  sample_u and actions must not be NULL (-12). */
+int rg_actor_forward_sample(const rg_actor_weights *w, int32_t num_envs, int32_t n_agents, const float *obs,
+                            int32_t obs_dim, int32_t append_agent_id, const uint8_t *restart, float *hidden, float *q,
+                            int32_t *actions, const float *sample_u, float *prob, void *hip_stream);
 /* Optional, once per actor: reorder a GRU weight array ([S][3H][H], torch layout) into the order the
  * kernel streams it (1 KB per load instruction instead of 64 scattered 16-byte pieces).  dst: a device
  * buffer of the same size; use it as wih / whh with gru_packed = 1. */
@@ -398,6 +410,17 @@ int rg_sizeof_policy_io(void);
  * with the lidar on (-49), a handle with a team pool (-39). */
 int rg_policy_rollout(rg_handle *h, const rg_actor_weights *w, int32_t num_steps, const rg_policy_io *pio, const rg_step_io *io,
                       int32_t auto_reset, uint64_t seed);
+
+/* rg_policy_rollout with the soft-policies selection of rg_actor_forward_sample at every time step (the sampled action feeds the
+ * env step of the same time step inside the launch).  Bit-identical to alternating rg_actor_forward_sample and the env step launch.
+ * pio->explore_u must be NULL (-56); sample and sample->sample_u must not be (-55); every refusal of rg_policy_rollout applies. */
+typedef struct rg_policy_sample {
+    const float *sample_u;     /* [T][E][N]: one uniform draw in [0, 1) per agent and time step */
+    float *prob;               /* [T][E][N] or NULL: the probability the stored action had */
+} rg_policy_sample;
+int rg_sizeof_policy_sample(void);
+int rg_policy_rollout_sample(rg_handle *h, const rg_actor_weights *w, int32_t num_steps, const rg_policy_io *pio,
+                             const rg_policy_sample *sample, const rg_step_io *io, int32_t auto_reset, uint64_t seed);
 
 #ifdef __cplusplus
 }

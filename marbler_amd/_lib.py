@@ -86,6 +86,10 @@ class RgPolicyIO(C.Structure):
                 ("reward_sum", C.c_void_p), ("ended", C.c_void_p), ("dist_sum", C.c_void_p)]
 
 
+class RgPolicySample(C.Structure):
+    _fields_ = [("sample_u", C.c_void_p), ("prob", C.c_void_p)]
+
+
 LIDAR_MAX_RAYS = 32
 
 
@@ -107,7 +111,8 @@ EXPORTS = ("rg_abi_version", "rg_last_error", "rg_sizeof_params", "rg_sizeof_sta
            "rg_create", "rg_destroy", "rg_bind_state", "rg_set_stream", "rg_reset", "rg_step", "rg_rollout", "rg_get_obs", "rg_step_kernel",
            "rg_actor_forward", "rg_actor_forward_explore", "rg_actor_pack_gru", "rg_actor_pack_gru_bf16x3", "rg_actor_pack_gru_f16x2", "rg_actor_last_error",
            "rg_sizeof_policy_io", "rg_policy_rollout", "rg_sizeof_lidar_params", "rg_set_lidar",
-           "rg_sizeof_team_params", "rg_set_teams")
+           "rg_sizeof_team_params", "rg_set_teams",
+           "rg_actor_forward_sample", "rg_sizeof_policy_sample", "rg_policy_rollout_sample")
 
 _lib = None
 
@@ -150,6 +155,9 @@ def load():
     lib.rg_actor_forward_explore.argtypes = [C.POINTER(RgActorWeights), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
     lib.rg_actor_forward_explore.restype = C.c_int
+    lib.rg_actor_forward_sample.argtypes = [C.POINTER(RgActorWeights), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rg_actor_forward_sample.restype = C.c_int
     lib.rg_actor_pack_gru.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.rg_actor_pack_gru.restype = C.c_int
     lib.rg_actor_pack_gru_bf16x3.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
@@ -161,6 +169,10 @@ def load():
                                       C.c_int32, C.c_uint64]
     lib.rg_policy_rollout.restype = C.c_int
     lib.rg_sizeof_policy_io.restype = C.c_int
+    lib.rg_policy_rollout_sample.argtypes = [C.c_void_p, C.POINTER(RgActorWeights), C.c_int32, C.POINTER(RgPolicyIO),
+                                             C.POINTER(RgPolicySample), C.POINTER(RgStepIO), C.c_int32, C.c_uint64]
+    lib.rg_policy_rollout_sample.restype = C.c_int
+    lib.rg_sizeof_policy_sample.restype = C.c_int
     lib.rg_set_lidar.argtypes = [C.c_void_p, C.POINTER(RgLidarParams)]
     lib.rg_set_lidar.restype = C.c_int
     lib.rg_sizeof_lidar_params.restype = C.c_int
@@ -174,6 +186,7 @@ def load():
         raise RobogymError(f"ABI version {lib.rg_abi_version()} != {ABI_VERSION}; rebuild the library")
     if (lib.rg_sizeof_params() != C.sizeof(RgScenarioParams) or lib.rg_sizeof_state() != C.sizeof(RgState)
             or lib.rg_sizeof_step_io() != C.sizeof(RgStepIO) or lib.rg_sizeof_policy_io() != C.sizeof(RgPolicyIO)
+            or lib.rg_sizeof_policy_sample() != C.sizeof(RgPolicySample)
             or lib.rg_sizeof_lidar_params() != C.sizeof(RgLidarParams) or lib.rg_sizeof_team_params() != C.sizeof(RgTeamParams)):
         raise RobogymError("struct layout of the binding differs from the compiled library; rebuild")
     _lib = lib

@@ -16,11 +16,11 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librobogym_hip.so")
 SOURCES = ["robogym_kernels.hip", "robogym_rollout_group.hip", "robogym_kernels_ipm.hip", "robogym_rollout_group_ipm.hip",
            "robogym_tpe.hip", "robogym_rollout_tpe.hip", "robogym_capi.hip", "actor_mfma.hip", "robogym_policy_h64.hip",
-           "robogym_policy_h128.hip", "robogym_lidar.hip", "robogym_lidar_rollout.hip", "robogym_lidar_ipm.hip",
+           "robogym_policy_h128.hip", "robogym_policy_sample_h64.hip", "robogym_policy_sample_h128.hip", "robogym_lidar.hip", "robogym_lidar_rollout.hip", "robogym_lidar_ipm.hip",
            "robogym_lidar_rollout_ipm.hip", "robogym_team.hip", "robogym_team_rollout.hip", "robogym_team_ipm.hip",
            "robogym_team_rollout_ipm.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("sim_math.h", "kernel_args.h", "device_common.h", "step_group.h", "step_tpe.h", "step_tpe_ipm.h", "ipm_qp.h",
-                                           "actor_common.h", "actor_body.inc", "policy_rollout.h", "lidar.h", "lidar_kernels.h", "team.h", "team_kernels.h", os.path.join("probes", "diag.h"), os.path.join("probes", "actor_diag.h"))
+                                           "actor_common.h", "actor_body.inc", "policy_rollout.h", "policy_body.inc", "lidar.h", "lidar_kernels.h", "team.h", "team_kernels.h", os.path.join("probes", "diag.h"), os.path.join("probes", "actor_diag.h"))
                                            if os.path.exists(os.path.join(CSRC, h))] + \
           [os.path.join(HERE, "..", "include", "robogym.h")]
 ARCH = "gfx950"
@@ -57,6 +57,7 @@ FILE_FLAGS = {"robogym_tpe.hip": ["-fno-slp-vectorize"], "robogym_rollout_tpe.hi
               "robogym_kernels.hip": GROUP_SLP, "robogym_rollout_group.hip": GROUP_SLP,
               "robogym_kernels_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_rollout_group_ipm.hip": GROUP_SLP + IPM_SCHED,
               "robogym_policy_h64.hip": GROUP_SLP, "robogym_policy_h128.hip": GROUP_SLP,
+              "robogym_policy_sample_h64.hip": GROUP_SLP, "robogym_policy_sample_h128.hip": GROUP_SLP,
               # the lidar kernels (lidar_kernels.h): lane-group kernels, with the flags of their mode
               "robogym_lidar.hip": GROUP_SLP, "robogym_lidar_rollout.hip": GROUP_SLP,
               "robogym_lidar_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_lidar_rollout_ipm.hip": GROUP_SLP + IPM_SCHED,
@@ -146,9 +147,10 @@ def build_host_sanitized(out=None):
     out = out or os.path.join(HERE, "build", "librobogym_capi_asan.so")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     stubs = os.path.join(HERE, "..", "tests", "sanitize", "launch_stubs.cpp")
+    stubs_sample = os.path.join(HERE, "..", "tests", "sanitize", "launch_stubs_sample.cpp")   # rg_actor_forward_sample
     cmd = [hipcc_path(), "-x", "hip", "--offload-host-only", "-O1", "-g", "-fno-omit-frame-pointer",
            "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fPIC", "-shared", "-std=c++17",
-           "-I", CSRC, os.path.join(CSRC, "robogym_capi.hip"), stubs, "-o", out]
+           "-I", CSRC, os.path.join(CSRC, "robogym_capi.hip"), stubs, stubs_sample, "-o", out]
     subprocess.check_call(cmd)
     return out
 

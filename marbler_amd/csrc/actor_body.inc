@@ -6,9 +6,17 @@
 //   RG_ACTOR_LOCATE(shared, E, set, base)  -- assigns the tile's weight set and first row (shared: flat row of [E*N]; otherwise env)
 //   RG_ACTOR_HIDDEN_LOAD(r, k4)            -- float4 k4 of the old hidden state of flat row r (r = 0 for rows outside the tile)
 //   RG_ACTOR_HIDDEN_STORE(r, j, v)         -- the new hidden state's column j of flat row r
+//   RG_ACTOR_SAMPLING(a)                   -- whether the epilogue samples the action (soft policies: a.sample_u is set).  The
+//                                             greedy / epsilon-greedy kernels pass `false` and keep their code; the sampling
+//                                             kernels (actor_sample_kernel, policy_rollout_sample_kernel) `true`.  Optional:
+//                                             an includer that does not define it gets `false`
 // Rows are valid while (shared ? base + i < E * N : base + i < E): a caller that owns part of the batch passes the end of its part
 // as a.E.  Textual inclusion keeps actor_kernel's instruction stream exactly what it was before the tile computation had a
 // second user (a device-function boundary changes how the kernel-argument loads are scheduled).
+#ifndef RG_ACTOR_SAMPLING   // an includer that knows the three hooks above only: greedy / epsilon-greedy
+#define RG_ACTOR_SAMPLING(a) false
+#define RG_ACTOR_SAMPLING_DEFAULTED
+#endif
     RG_ASTAMP_BEGIN();
     constexpr int NW = H / 32;  // wavefronts per tile
     constexpr int NTHREADS = 64 * NW;
@@ -507,15 +515,20 @@
         // (the first NaN wins); a row of -inf only keeps the sentinel and is given column 0 below.  The index is always in [0, A).
         float best = -__builtin_huge_valf();
         int arg = 0x7FFFFFFF;
+        const bool sampling = RG_ACTOR_SAMPLING(a);
+        const float su = sampling ? a.sample_u[r] : 0.0f;   // (every lane of the row; asked for ahead of the LDS reads)
+        float vq[CPT];   // the row's finished logits of this lane, for the sampling rule
 #pragma unroll
         for (int c_ = 0; c_ < CPT; ++c_) {
             const int c = sub * CPT + c_;
+            vq[c_] = 0.0f;
             if (c < A) {
                 float v = 0.0f;
 #pragma unroll
                 for (int wv = 0; wv < NW; ++wv) v = v + Y[wv * (TM * 32) + i * 32 + c];
                 v = v + b2v[c_];
                 if (ok && a.q) a.q[static_cast<size_t>(r) * A + c] = v;
+                vq[c_] = v;
                 if (v > best || (v != v && best == best)) {  // first maximum, like torch.argmax
                     best = v;
                     arg = c;
@@ -533,7 +546,14 @@
             }
         }
         arg = static_cast<unsigned>(arg) >= static_cast<unsigned>(A) ? 0 : arg;
-        if (ok && sub == 0 && a.actions) {
+        if (sampling) {   // soft policies (actor_common.h soft_select_row): `best` is the row's maximum on every lane of the row
+            float pr;
+            soft_select_row<TPR, CPT>(vq, best, sub, A, su, arg, arg, pr);
+            if (ok && sub == 0) {
+                a.actions[r] = arg;
+                if (a.prob) a.prob[r] = pr;
+            }
+        } else if (ok && sub == 0 && a.actions) {
             if (a.explore_u) {  // u < epsilon  <=>  u * (A / epsilon) < A: that product's integer part is the uniform action
                 const int k = static_cast<int>(a.explore_u[r] * a.explore_scale);
                 if (static_cast<unsigned>(k) < static_cast<unsigned>(A)) arg = k;
@@ -542,3 +562,7 @@
         }
     }
     RG_ASTAMP_END(a, E, N, A, H, cb, lane);
+#ifdef RG_ACTOR_SAMPLING_DEFAULTED
+#undef RG_ACTOR_SAMPLING
+#undef RG_ACTOR_SAMPLING_DEFAULTED
+#endif

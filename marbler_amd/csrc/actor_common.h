@@ -77,6 +77,8 @@ struct ActorArgs {
     const float *explore_u; // [E][N] uniforms in [0, 1) or NULL: epsilon-greedy selection (rg_actor_forward_explore)
     float explore_scale;    // n_actions / epsilon
     int32_t E, N, D, append_agent_id, ip;  // ip = padded input width
+    const float *sample_u;  // [E][N] uniforms in [0, 1) or NULL: soft-policies sampling (rg_actor_forward_sample; soft_select_row below)
+    float *prob;            // [E][N] or NULL: the probability the sampled action had
 };
 
 // gate nonlinearities on the hardware exponential (v_exp_f32, ~1 ulp on 2^t): absolute error ~1e-7 on
@@ -86,6 +88,91 @@ struct ActorArgs {
 __device__ __forceinline__ float relu_(float x) { return x < 0.0f ? 0.0f : x; }
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ __forceinline__ float tanhf_(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
+
+// ---- soft policies: the action is SAMPLED from softmax(logits) (EPyMARL's SoftPoliciesSelector, external to the reference: what
+// its MAPPO / IPPO / MAA2C checkpoints collect data with) and the probability it had is reported.  The rule is a float32 SPEC, as
+// explore_select is: this file, marbler_amd.evaluate.soft_select (torch) and tests/soft_twin.py (numpy) give the same action and
+// the same `prob` word for the same (q, u).  Per agent row, from the logits q[0..A) as the launch writes them and ONE uniform u:
+//   m = the row maximum; e_c = soft_exp(q_c - m); c_k = the partial sums of ((e_0 + e_1) + e_2) + ... in ascending column order,
+//   Z = c_{A-1}; t = u * Z; the action is the first k with t < c_k, or, if there is none, the last k with e_k > 0 (for u below 1
+//   the float32 product u * Z stays below Z: only u = 1, outside sample_u's range, gets there -- and still lands inside the row's
+//   support); prob = e_action / Z (one correctly rounded division).  A column with e_k = 0 (a -inf logit, underflow) is never
+//   chosen.  A row whose maximum is not finite (a NaN anywhere, +inf, all -inf) takes the greedy action and prob = NaN.
+// soft_exp(x), x <= 0, is NOT v_exp_f32 or libm (neither promises the same bits as a CPU twin): with this file compiled
+// -ffp-contract=off every line is one correctly rounded IEEE operation --
+//   k = rint(x * LOG2E) (to nearest even); r = (x - k * LN2_HI) - k * LN2_LO (LN2_HI = 355 / 512: k * LN2_HI is exact);
+//   p = ((((P0 r + P1) r + P2) r + P3) r + P4) r + P5, every multiply and add its own operation; y = ((p * (r * r)) + r) + 1;
+//   the result is y with k added to its exponent field; 0 for x < SOFT_CUT = -87.336 (below it exp(x) < 1.001 x 2^-126, the edge of
+//   the normal float32 range; at and above it k >= -126 and y >= 1, so the exponent field never leaves the normal range).
+// Constants: LOG2E = 0x3FB8AA3B, LN2_HI = 0.693359375, LN2_LO = -2.12194440e-4 and the Cephes expf coefficients 1.9875691500e-4,
+// 1.3981999507e-3, 8.3334519073e-3, 4.1665795894e-2, 1.6666665459e-1, 5.0000001201e-1.  Measured against binary64 exp on 2^24
+// random arguments in [SOFT_CUT, 0] and every reduction boundary: at most 1.37 x 2^-24 relative (tests/test_soft_select.py).
+constexpr float SOFT_LOG2E = 1.4426950408889634f, SOFT_LN2_HI = 0.693359375f, SOFT_LN2_LO = -2.12194440e-4f, SOFT_CUT = -87.336f;
+__device__ __forceinline__ float soft_exp(float x) {
+    const bool live = x >= SOFT_CUT;           // (false for -inf and NaN)
+    const float xc = live ? x : 0.0f;
+    const float k = __builtin_rintf(xc * SOFT_LOG2E);
+    const float r = (xc - k * SOFT_LN2_HI) - k * SOFT_LN2_LO;
+    float p = 1.9875691500e-4f;
+    p = p * r + 1.3981999507e-3f;
+    p = p * r + 8.3334519073e-3f;
+    p = p * r + 4.1665795894e-2f;
+    p = p * r + 1.6666665459e-1f;
+    p = p * r + 5.0000001201e-1f;
+    const float y = ((p * (r * r)) + r) + 1.0f;
+    const int32_t bits = __builtin_bit_cast(int32_t, y) + (static_cast<int32_t>(k) << 23);
+    return live ? __builtin_bit_cast(float, bits) : 0.0f;
+}
+// Where the ordered sum runs.  After fc2 a row's A logits sit on TPR neighbouring lanes, CPT consecutive columns each (the layout
+// of the arg-max pass).  The CPT exponentials of a lane are independent and run on all lanes at once; the chain of additions is
+// walked lane by lane in column order: in round s every lane continues the chain from the carry over its own columns, the lane
+// with sub == s keeps its partial sums, and its running value is the next round's carry (one __shfl of width TPR) -- the spec's
+// additions in the spec's order, TPR x CPT = 32 adds and TPR shuffles per lane, no LDS traffic and no barrier.  (Republishing
+// the logits in LDS for ONE lane of the row to walk would put all 32 exponentials, ~20 dependent operations each, on a 1 / TPR
+// occupied wave behind an LDS round trip; here the exponentials use every lane.)  Padding columns (c >= A) carry e = 0: x + 0 is
+// x, they change nothing in the chain.  The first crossing and the last positive column are then reduced over the row's lanes
+// with the same xor butterfly as the arg-max.  `sub` = the lane's position in its row, m = the row's maximum on every lane.
+template <int TPR, int CPT>
+__device__ __forceinline__ void soft_select_row(const float (&v)[CPT], float m, int sub, int A, float u, int greedy, int &action,
+                                                float &prob) {
+    float e[CPT], cs[CPT];
+#pragma unroll
+    for (int c_ = 0; c_ < CPT; ++c_) {
+        e[c_] = sub * CPT + c_ < A ? soft_exp(v[c_] - m) : 0.0f;
+        cs[c_] = 0.0f;
+    }
+    float carry = 0.0f;
+#pragma unroll
+    for (int s = 0; s < TPR; ++s) {
+        float run = carry;
+#pragma unroll
+        for (int c_ = 0; c_ < CPT; ++c_) {
+            run = run + e[c_];
+            cs[c_] = sub == s ? run : cs[c_];
+        }
+        carry = __shfl(run, s, TPR);
+    }
+    const float Z = carry, t = u * Z;
+    int hit = 0x7FFFFFFF, last = -1;
+    float ehit = 0.0f, elast = 0.0f;
+#pragma unroll
+    for (int c_ = 0; c_ < CPT; ++c_) {
+        const int c = sub * CPT + c_;
+        if (e[c_] > 0.0f) last = c, elast = e[c_];
+        if (c < A && t < cs[c_] && hit == 0x7FFFFFFF) hit = c, ehit = e[c_];
+    }
+#pragma unroll
+    for (int d = 1; d < TPR; d <<= 1) {
+        const int oh = __shfl_xor(hit, d), ol = __shfl_xor(last, d);
+        const float oeh = __shfl_xor(ehit, d), oel = __shfl_xor(elast, d);
+        if (oh < hit) hit = oh, ehit = oeh;
+        if (ol > last) last = ol, elast = oel;
+    }
+    const bool none = hit == 0x7FFFFFFF;
+    const bool finite = (__builtin_bit_cast(uint32_t, m) & 0x7F800000u) != 0x7F800000u;
+    action = finite ? (none ? last : hit) : greedy;
+    prob = finite ? (none ? elast : ehit) / Z : __builtin_nanf("");
+}
 
 
 // Two [TM][H] images in LDS with pitch exactly H.  Bank conflicts are avoided by an XOR swizzle of the 16-byte block index

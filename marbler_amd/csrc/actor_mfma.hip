@@ -40,9 +40,6 @@
 
 namespace rg {
 
-template <int H, int SPLIT>   // SPLIT: the GRU's products on 1: three bfloat16 planes (gru_packed == 2), 2: two binary16 planes (gru_packed == 3)
-__attribute__((amdgpu_waves_per_eu(2, 2)))   // 256 registers (VGPR + AGPR): two tiles per CU, one's serial phases under the other's MFMAs
-__global__ __launch_bounds__(64 * (H / 32)) void actor_kernel(const ActorArgs a) {
 // tile blockIdx.x of the whole batch (shared: rows 32 b .. 32 b + 31 of the flat [E*N] row space; otherwise agent
 // b / tiles_per_agent, envs 32 (b % tiles_per_agent) ..), the hidden state read and written in memory
 #define RG_ACTOR_LOCATE(shared, E, set, base)                 \
@@ -55,11 +52,28 @@ __global__ __launch_bounds__(64 * (H / 32)) void actor_kernel(const ActorArgs a)
     }
 #define RG_ACTOR_HIDDEN_LOAD(r, k4) *reinterpret_cast<const float4 *>(a.hidden + static_cast<size_t>(r) * H + 4 * (k4))
 #define RG_ACTOR_HIDDEN_STORE(r, j, v) a.hidden[static_cast<size_t>(r) * H + (j)] = (v)
+
+template <int H, int SPLIT>   // SPLIT: the GRU's products on 1: three bfloat16 planes (gru_packed == 2), 2: two binary16 planes (gru_packed == 3)
+__attribute__((amdgpu_waves_per_eu(2, 2)))   // 256 registers (VGPR + AGPR): two tiles per CU, one's serial phases under the other's MFMAs
+__global__ __launch_bounds__(64 * (H / 32)) void actor_kernel(const ActorArgs a) {
+#define RG_ACTOR_SAMPLING(a) false
 #include "actor_body.inc"
+#undef RG_ACTOR_SAMPLING
+}
+
+// The same tile computation with the soft-policies epilogue (rg_actor_forward_sample; actor_common.h soft_select_row).  A kernel of
+// its own, not a run-time branch in actor_kernel: the selector is a compile-time constant of the body, so the greedy /
+// epsilon-greedy kernels keep the instruction stream they had before the rule existed.
+template <int H, int SPLIT>
+__attribute__((amdgpu_waves_per_eu(2, 2)))
+__global__ __launch_bounds__(64 * (H / 32)) void actor_sample_kernel(const ActorArgs a) {
+#define RG_ACTOR_SAMPLING(a) true
+#include "actor_body.inc"
+#undef RG_ACTOR_SAMPLING
+}
 #undef RG_ACTOR_LOCATE
 #undef RG_ACTOR_HIDDEN_LOAD
 #undef RG_ACTOR_HIDDEN_STORE
-}
 
 // torch layout [S][3H][H] -> the kernel's streaming order [S][cb][chunk][gate][q4][lane = (half, col)][4]
 __global__ void pack_gru_kernel(const float *src, float *dst, int n_sets, int H) {
@@ -184,7 +198,8 @@ RG_ACTOR_DIAG_ENTRY   // (diagnostic builds: rg_actor_occupancy)
 
 static int actor_forward(const rg_actor_weights *w, int32_t num_envs, int32_t n_agents, const float *obs,
                          int32_t obs_dim, int32_t append_agent_id, const uint8_t *restart, float *hidden,
-                         float *q, int32_t *actions, const float *explore_u, float epsilon, void *hip_stream) {
+                         float *q, int32_t *actions, const float *explore_u, float epsilon, void *hip_stream,
+                         const float *sample_u = nullptr, float *prob = nullptr) {
     auto fail = [](int code, const char *msg) {
         snprintf(g_actor_err, sizeof(g_actor_err), "%s", msg);
         return code;
@@ -215,6 +230,8 @@ static int actor_forward(const rg_actor_weights *w, int32_t num_envs, int32_t n_
     a.actions = actions;
     a.explore_u = explore_u;
     a.explore_scale = explore_u ? static_cast<float>(w->n_actions) / epsilon : 0.0f;
+    a.sample_u = sample_u;
+    a.prob = prob;
     a.E = num_envs;
     a.N = n_agents;
     a.D = obs_dim;
@@ -224,7 +241,17 @@ static int actor_forward(const rg_actor_weights *w, int32_t num_envs, int32_t n_
                                      : n_agents * ((num_envs + rg::TM - 1) / rg::TM);
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const int split = !w->use_rnn ? 0 : w->gru_packed == 2 ? 1 : w->gru_packed == 3 ? 2 : 0;
-    if (w->hidden_dim == 64) {
+    if (sample_u) {
+        if (w->hidden_dim == 64) {
+            if (split == 2) hipLaunchKernelGGL((rg::actor_sample_kernel<64, 2>), dim3(tiles), dim3(128), 0, stream, a);
+            else if (split == 1) hipLaunchKernelGGL((rg::actor_sample_kernel<64, 1>), dim3(tiles), dim3(128), 0, stream, a);
+            else hipLaunchKernelGGL((rg::actor_sample_kernel<64, 0>), dim3(tiles), dim3(128), 0, stream, a);
+        } else {
+            if (split == 2) hipLaunchKernelGGL((rg::actor_sample_kernel<128, 2>), dim3(tiles), dim3(256), 0, stream, a);
+            else if (split == 1) hipLaunchKernelGGL((rg::actor_sample_kernel<128, 1>), dim3(tiles), dim3(256), 0, stream, a);
+            else hipLaunchKernelGGL((rg::actor_sample_kernel<128, 0>), dim3(tiles), dim3(256), 0, stream, a);
+        }
+    } else if (w->hidden_dim == 64) {
         if (split == 2) hipLaunchKernelGGL((rg::actor_kernel<64, 2>), dim3(tiles), dim3(128), 0, stream, a);
         else if (split == 1) hipLaunchKernelGGL((rg::actor_kernel<64, 1>), dim3(tiles), dim3(128), 0, stream, a);
         else hipLaunchKernelGGL((rg::actor_kernel<64, 0>), dim3(tiles), dim3(128), 0, stream, a);
@@ -251,4 +278,19 @@ extern "C" int rg_actor_forward_explore(const rg_actor_weights *w, int32_t num_e
                                         void *hip_stream) {
     return actor_forward(w, num_envs, n_agents, obs, obs_dim, append_agent_id, restart, hidden, q, actions, explore_u, epsilon,
                          hip_stream);
+}
+
+extern "C" int rg_actor_forward_sample(const rg_actor_weights *w, int32_t num_envs, int32_t n_agents, const float *obs,
+                                       int32_t obs_dim, int32_t append_agent_id, const uint8_t *restart, float *hidden,
+                                       float *q, int32_t *actions, const float *sample_u, float *prob, void *hip_stream) {
+    if (!sample_u) {
+        snprintf(g_actor_err, sizeof(g_actor_err), "rg_actor_forward_sample: sample_u is NULL");
+        return -12;
+    }
+    if (!actions) {
+        snprintf(g_actor_err, sizeof(g_actor_err), "rg_actor_forward_sample: sample_u without an actions array");
+        return -12;
+    }
+    return actor_forward(w, num_envs, n_agents, obs, obs_dim, append_agent_id, restart, hidden, q, actions, nullptr, 0.0f,
+                         hip_stream, sample_u, prob);
 }

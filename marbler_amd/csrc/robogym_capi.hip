@@ -140,6 +140,10 @@ hipError_t launch_policy_rollout_h64(const KernelArgs &, const rg_actor_weights 
     __attribute__((weak));
 hipError_t launch_policy_rollout_h128(const KernelArgs &, const rg_actor_weights &, const rg_policy_io &, int32_t, hipStream_t)
     __attribute__((weak));
+hipError_t launch_policy_rollout_sample_h64(const KernelArgs &, const rg_actor_weights &, const rg_policy_io &, const rg_policy_sample &,
+                                            int32_t, hipStream_t) __attribute__((weak));
+hipError_t launch_policy_rollout_sample_h128(const KernelArgs &, const rg_actor_weights &, const rg_policy_io &, const rg_policy_sample &,
+                                             int32_t, hipStream_t) __attribute__((weak));
 // The lidar kernels (lidar_kernels.h) live in their own translation units; weak for the same reason.
 #define RG_LIDAR_LAUNCH(name) hipError_t name(const KernelArgs &, const rg_lidar_params &, hipStream_t) __attribute__((weak));
 RG_LIDAR_LAUNCH(launch_lidar_step)
@@ -181,6 +185,7 @@ int rg_sizeof_params(void) { return static_cast<int>(sizeof(rg_scenario_params))
 int rg_sizeof_state(void) { return static_cast<int>(sizeof(rg_state)); }
 int rg_sizeof_step_io(void) { return static_cast<int>(sizeof(rg_step_io)); }
 int rg_sizeof_policy_io(void) { return static_cast<int>(sizeof(rg_policy_io)); }
+int rg_sizeof_policy_sample(void) { return static_cast<int>(sizeof(rg_policy_sample)); }
 int rg_sizeof_lidar_params(void) { return static_cast<int>(sizeof(rg_lidar_params)); }
 int rg_sizeof_team_params(void) { return static_cast<int>(sizeof(rg_team_params)); }
 int rg_next_init_stride(const rg_scenario_params *params) {
@@ -431,8 +436,9 @@ int rg_rollout(rg_handle *h, const int32_t *actions, int32_t num_steps, const rg
     return 0;
 }
 
-int rg_policy_rollout(rg_handle *h, const rg_actor_weights *w, int32_t num_steps, const rg_policy_io *pio, const rg_step_io *io,
-                      int32_t auto_reset, uint64_t seed) {
+// rg_policy_rollout (sample == NULL) and rg_policy_rollout_sample: the same checks, in the same order
+static int policy_rollout(rg_handle *h, const rg_actor_weights *w, int32_t num_steps, const rg_policy_io *pio,
+                          const rg_policy_sample *sample, bool sampling, const rg_step_io *io, int32_t auto_reset, uint64_t seed) {
     rg::KernelArgs a;
     if (int rc = fill_args(h, a)) return rc;
     if (!w || !pio || !io) return fail(-23, "weights, policy io or step io is NULL");
@@ -458,14 +464,29 @@ int rg_policy_rollout(rg_handle *h, const rg_actor_weights *w, int32_t num_steps
     if (!io->elapsed) return fail(-29, "rg_policy_rollout: the step io must carry the gymma block (elapsed, truncated, ended, reward_sum)");
     if (int rc = check_io(io)) return rc;
     auto launch = w->hidden_dim == 64 ? rg::launch_policy_rollout_h64 : rg::launch_policy_rollout_h128;
-    if (!launch) return fail(-100, "rg_policy_rollout: this build has no device code");
+    auto launch_sample = w->hidden_dim == 64 ? rg::launch_policy_rollout_sample_h64 : rg::launch_policy_rollout_sample_h128;
+    if (sampling ? !launch_sample : !launch) return fail(-100, "rg_policy_rollout: this build has no device code");
     a.io = *io;
     a.auto_reset = auto_reset;
     a.seed = seed;
     a.next_stride = 0;   // AHEAD = false inside the launch, as in rg_rollout
     RG_ON_DEVICE(h);
     if (int rc = sync_seed(h, seed)) return rc;
+    if (sampling) return launched(launch_sample(a, *w, *pio, *sample, num_steps, h->stream));
     return launched(launch(a, *w, *pio, num_steps, h->stream));
+}
+
+int rg_policy_rollout(rg_handle *h, const rg_actor_weights *w, int32_t num_steps, const rg_policy_io *pio, const rg_step_io *io,
+                      int32_t auto_reset, uint64_t seed) {
+    return policy_rollout(h, w, num_steps, pio, nullptr, false, io, auto_reset, seed);
+}
+
+int rg_policy_rollout_sample(rg_handle *h, const rg_actor_weights *w, int32_t num_steps, const rg_policy_io *pio,
+                             const rg_policy_sample *sample, const rg_step_io *io, int32_t auto_reset, uint64_t seed) {
+    // the selector's own arguments first (they need no handle), then every check of rg_policy_rollout
+    if (!sample || !sample->sample_u) return fail(-55, "rg_policy_rollout_sample: sample or its sample_u is NULL");
+    if (pio && pio->explore_u) return fail(-56, "rg_policy_rollout_sample: sample_u and explore_u do not combine (explore_u must be NULL)");
+    return policy_rollout(h, w, num_steps, pio, sample, true, io, auto_reset, seed);
 }
 
 int rg_set_teams(rg_handle *h, const rg_team_params *tp) {

@@ -117,12 +117,14 @@ class BatchedActor(object):
         return self._ws
 
     def forward_fused(self, obs, hidden, append_agent_id=True, restart=None, q_out=None, actions_out=None, stream=None,
-                      explore_u=None, epsilon=0.0):
+                      explore_u=None, epsilon=0.0, sample_u=None, prob_out=None):
         """One actor step for all E x N agents in one launch (rg_actor_forward: the matrix cores; GRU on bfloat16 planes unless pack_gru says otherwise).
         obs [E,N,D] f32; hidden [E,N,H] f32 updated IN PLACE; restart [E] uint8 (nonzero = start that
         env's hidden state from zero) or None; stream: a torch.cuda.Stream (default: the device's current stream).
         explore_u [E,N] f32 uniforms in [0, 1) with epsilon > 0: epsilon-greedy actions (rg_actor_forward_explore; the rule is
-        `explore_select` below).  Returns (q [E,N,A], actions [E,N] int32)."""
+        `explore_select` below).  sample_u [E,N] f32 uniforms in [0, 1): soft-policies actions, SAMPLED from softmax(q)
+        (rg_actor_forward_sample; the rule is `soft_select` below), and prob_out [E,N] f32 (or None) receives the probability of the
+        sampled action; not together with explore_u.  Returns (q [E,N,A], actions [E,N] int32)."""
         import ctypes as C
         from . import _lib
         lib = _lib.load()
@@ -140,7 +142,20 @@ class BatchedActor(object):
                 self._pack_done = None
             else:
                 stream.wait_event(ev)
-        if explore_u is not None:
+        if sample_u is not None and explore_u is not None:
+            raise ValueError("sample_u (soft policies) and explore_u (epsilon-greedy) do not combine")
+        if prob_out is not None and sample_u is None:
+            raise ValueError("prob_out needs sample_u")
+        if sample_u is not None:
+            if sample_u.shape != (E, N) or sample_u.dtype != torch.float32 or not sample_u.is_contiguous():
+                raise ValueError("sample_u must be a contiguous float32 [E, N] tensor")
+            if prob_out is not None and (prob_out.shape != (E, N) or prob_out.dtype != torch.float32 or not prob_out.is_contiguous()):
+                raise ValueError("prob_out must be a contiguous float32 [E, N] tensor")
+            rc = lib.rg_actor_forward_sample(C.byref(ws), E, N, obs.data_ptr(), D, 1 if append_agent_id else 0,
+                                             restart.data_ptr() if restart is not None else None, hidden.data_ptr(),
+                                             q_out.data_ptr(), actions_out.data_ptr(), sample_u.data_ptr(),
+                                             prob_out.data_ptr() if prob_out is not None else None, C.c_void_p(stream.cuda_stream))
+        elif explore_u is not None:
             if explore_u.shape != (E, N) or explore_u.dtype != torch.float32 or not explore_u.is_contiguous():
                 raise ValueError("explore_u must be a contiguous float32 [E, N] tensor")
             rc = lib.rg_actor_forward_explore(C.byref(ws), E, N, obs.data_ptr(), D, 1 if append_agent_id else 0,
@@ -157,10 +172,12 @@ class BatchedActor(object):
 
 
 def policy_rollout(env, actor, T, io, hidden, actions, restart=None, append_agent_id=True, restart_on_done=False, explore_u=None,
-                   epsilon=0.0, obs=None, reward_sum=None, ended=None, dist_sum=None):
+                   epsilon=0.0, obs=None, reward_sum=None, ended=None, dist_sum=None, sample_u=None, prob=None):
     """rg_policy_rollout: T time steps of actor -> action -> env step in ONE launch on the env's handle (csrc/policy_rollout.h).
     env: a VecRobotariumEnv; io: the rg_step_io it steps with (it must carry the gymma block); the tensors are device tensors in
-    the layouts of include/robogym.h rg_policy_io (None = NULL).  Raises ValueError for a configuration the launch refuses."""
+    the layouts of include/robogym.h rg_policy_io (None = NULL).  sample_u [T, E, N] f32 uniforms: soft-policies actions
+    (rg_policy_rollout_sample), prob [T, E, N] f32 or None the probability each had; not together with explore_u.
+    Raises ValueError for a configuration the launch refuses."""
     import ctypes as C
     from . import _lib
     lib = _lib.load()
@@ -180,6 +197,13 @@ def policy_rollout(env, actor, T, io, hidden, actions, restart=None, append_agen
     ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
     if explore_u is not None and (explore_u.dtype != torch.float32 or not explore_u.is_contiguous()):
         raise ValueError("explore_u must be a contiguous float32 [T, E, N] tensor")
+    if sample_u is not None and explore_u is not None:
+        raise ValueError("sample_u (soft policies) and explore_u (epsilon-greedy) do not combine")
+    if prob is not None and sample_u is None:
+        raise ValueError("prob needs sample_u")
+    for name, t in (("sample_u", sample_u), ("prob", prob)):
+        if t is not None and (tuple(t.shape) != (int(T), env.E, env.N) or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous float32 [T, E, N] tensor")
     env._sync_stream()   # the handle launches on torch's current stream
     ws = actor._weights_struct()
     ev = getattr(actor, "_pack_done", None)
@@ -190,7 +214,12 @@ def policy_rollout(env, actor, T, io, hidden, actions, restart=None, append_agen
             torch.cuda.current_stream(env.device).wait_event(ev)
     pio = _lib.RgPolicyIO(ptr(hidden), ptr(restart), 1 if append_agent_id else 0, 1 if restart_on_done else 0, ptr(explore_u),
                           float(epsilon), ptr(actions), ptr(obs), ptr(reward_sum), ptr(ended), ptr(dist_sum))
-    rc = lib.rg_policy_rollout(env._h, C.byref(ws), int(T), C.byref(pio), C.byref(io), 1 if env.auto_reset else 0, env.seed)
+    if sample_u is not None:
+        ps = _lib.RgPolicySample(ptr(sample_u), ptr(prob))
+        rc = lib.rg_policy_rollout_sample(env._h, C.byref(ws), int(T), C.byref(pio), C.byref(ps), C.byref(io),
+                                          1 if env.auto_reset else 0, env.seed)
+    else:
+        rc = lib.rg_policy_rollout(env._h, C.byref(ws), int(T), C.byref(pio), C.byref(io), 1 if env.auto_reset else 0, env.seed)
     if rc != 0:
         msg = f"rg_policy_rollout ({rc}): {lib.rg_last_error().decode()}"
         raise (_lib.RobogymError if rc <= -30 and rc > -40 or rc == -100 else ValueError)(msg)
@@ -203,6 +232,68 @@ def explore_select(greedy, u, epsilon, n_actions, out=None):
     scale = float(np.float32(n_actions) / np.float32(epsilon))
     k = (u * torch.tensor(scale, dtype=torch.float32, device=u.device)).to(torch.int32)
     return torch.where(k < n_actions, k, greedy, out=out)
+
+
+# soft_exp's constants (csrc/actor_common.h states them once; tests/soft_twin.py is the numpy twin)
+_SOFT_LOG2E, _SOFT_LN2_HI, _SOFT_LN2_LO, _SOFT_CUT = 1.4426950408889634, 0.693359375, -2.12194440e-4, -87.336
+_SOFT_POLY = (1.9875691500e-4, 1.3981999507e-3, 8.3334519073e-3, 4.1665795894e-2, 1.6666665459e-1, 5.0000001201e-1)
+
+
+def soft_exp(x):
+    """exp(x) for float32 x <= 0 as the explicit float32 operation sequence of csrc/actor_common.h `soft_exp` (no library or
+    hardware exponential: each torch op below is one correctly rounded IEEE operation); 0 below the underflow cut."""
+    f = lambda v: torch.tensor(v, dtype=torch.float32, device=x.device)  # noqa: E731
+    k = torch.round(x * f(_SOFT_LOG2E))                       # round to nearest even
+    r = (x - k * f(_SOFT_LN2_HI)) - k * f(_SOFT_LN2_LO)
+    p = f(_SOFT_POLY[0])
+    for c in _SOFT_POLY[1:]:
+        p = p * r + f(c)
+    y = ((p * (r * r)) + r) + f(1.0)
+    live = x >= f(_SOFT_CUT)
+    ki = torch.where(live, k, f(0.0)).to(torch.int32)
+    scaled = (y.view(torch.int32) + (ki << 23)).view(torch.float32)   # 2^k through the exponent field
+    return torch.where(live, scaled, f(0.0))
+
+
+def soft_select(q, u, out_actions=None, out_prob=None):
+    """The soft-policies rule of rg_actor_forward_sample in torch elementwise ops (the composed runner path and the tests use it;
+    CPU or GPU tensors): q [..., A] float32 logits, u [...] float32 uniforms in [0, 1).  With m the row maximum,
+    e_c = soft_exp(q_c - m), the partial sums c_k of ((e_0 + e_1) + e_2) + ... and Z the last of them, the action is the first k
+    with u * Z < c_k (none: the last k with e_k > 0) and prob = e_action / Z.  A row whose maximum is not finite takes
+    torch.argmax's action and prob = NaN.  Returns (actions int32 [...], prob float32 [...])."""
+    A = q.shape[-1]
+    m = q.max(dim=-1).values                                  # (a NaN anywhere gives NaN)
+    ok = torch.isfinite(m)
+    e = soft_exp(q - m.unsqueeze(-1))
+    run = torch.zeros_like(m)
+    cs = []
+    for k in range(A):                                        # the ordered sum (0 + e_0 is e_0)
+        run = run + e[..., k]
+        cs.append(run)
+    t = u * run
+    act = torch.full(m.shape, -1, dtype=torch.int32, device=q.device)
+    e_act = torch.zeros_like(m)
+    last = torch.zeros_like(act)
+    e_last = torch.zeros_like(m)
+    for k in range(A):
+        hit = (t < cs[k]) & (act < 0)
+        act = torch.where(hit, k, act)
+        e_act = torch.where(hit, e[..., k], e_act)
+        pos = e[..., k] > 0
+        last = torch.where(pos, k, last)
+        e_last = torch.where(pos, e[..., k], e_last)
+    none = act < 0
+    act = torch.where(none, last, act)
+    e_act = torch.where(none, e_last, e_act)
+    act = torch.where(ok, act, q.argmax(dim=-1).to(torch.int32))
+    prob = torch.where(ok, e_act / run, torch.tensor(float("nan"), dtype=torch.float32, device=q.device))
+    if out_actions is not None:
+        out_actions.copy_(act)
+        act = out_actions
+    if out_prob is not None:
+        out_prob.copy_(prob)
+        prob = out_prob
+    return act, prob
 
 
 def load_actor(model_file, model_config, n_agents, device="cuda:0"):

@@ -21,7 +21,7 @@ single-env form with EPyMARL's Python types, for dropping into an unmodified EPy
 import numpy as np
 import torch
 
-from .evaluate import explore_select, policy_rollout
+from .evaluate import explore_select, policy_rollout, soft_select
 from .vec_env import VecRobotariumEnv
 
 N_ACTIONS = {"PredatorCapturePrey": 5, "Warehouse": 5, "MaterialTransport": 20, "Simple": 5, "ArcticTransport": 5}
@@ -236,9 +236,23 @@ class BatchedRunner(object):
     tensors EPyMARL stores per time step -- obs, state, avail_actions, actions, reward, terminated -- come
     back time-major with a leading [T] axis, all on the device.  Envs that finish restart inside the
     rollout (the hidden state of their agents restarts at zero), so there is no padding to an episode
-    limit: `terminated[t, e]` marks episode ends, `episode_start[t, e]` the first step of an episode."""
+    limit: `terminated[t, e]` marks episode ends, `episode_start[t, e]` the first step of an episode.
+    action_selector: "epsilon_greedy" (the default) or "soft_policies" -- EPyMARL's SoftPoliciesSelector, what the zoo's MAPPO
+    checkpoints collect data with (sacred config: "action_selector": "soft_policies"): the action is sampled from
+    softmax(actor output) (evaluate.soft_select is the rule) and `prob` [T, E, N] -- the probability the behaviour policy gave the
+    stored action, what a PPO / actor-critic learner needs -- joins the returned dict.  test_mode=True is that selector's test
+    mode: the greedy action, no `prob`.  soft_policies does not combine with epsilon > 0."""
 
-    def __init__(self, venv, actor, epsilon=0.0, obs_agent_id=True, seed=0):
+    SELECTORS = ("epsilon_greedy", "soft_policies")
+
+    def __init__(self, venv, actor, epsilon=0.0, obs_agent_id=True, seed=0, action_selector="epsilon_greedy", test_mode=False):
+        # (argument errors first: nothing below has touched the env or the device yet)
+        if action_selector not in self.SELECTORS:
+            raise ValueError(f"action_selector must be one of {self.SELECTORS}, not {action_selector!r}")
+        if action_selector == "soft_policies" and float(epsilon) > 0.0:
+            raise ValueError("action_selector='soft_policies' samples from the policy itself: it does not combine with epsilon > 0")
+        self.action_selector = action_selector
+        self.test_mode = bool(test_mode)
         self.venv, self.actor = venv, actor
         self.epsilon = float(epsilon)
         self.obs_agent_id = bool(obs_agent_id)
@@ -276,6 +290,11 @@ class BatchedRunner(object):
         eps = self.epsilon
         # exploration: ONE uniform per agent and time step, drawn for the whole call in one launch (evaluate.explore_select is the rule)
         u_all = torch.rand(T, E, N, generator=self.gen, device=dev) if eps > 0.0 else None
+        # soft policies: likewise ONE uniform per agent and time step (evaluate.soft_select is the rule); test mode is the greedy path
+        soft = self.action_selector == "soft_policies" and not self.test_mode
+        s_all = torch.rand(T, E, N, generator=self.gen, device=dev) if soft else None
+        if soft:
+            out["prob"] = torch.empty(T, E, N, device=dev)
         if one_launch and getattr(env, "teams", None) is not None:
             raise ValueError("one_launch: an env with a team pool (teams) is not supported; run(T) collects it on the two-launch path")
         if one_launch and env.lidar is not None:
@@ -293,13 +312,13 @@ class BatchedRunner(object):
             if one_launch:
                 policy_rollout(env, self.actor, T, env._io_into, self.hidden, out["actions"], restart=self._restart,
                                append_agent_id=self.obs_agent_id, explore_u=u_all, epsilon=eps, obs=out["obs"],
-                               reward_sum=out["reward"], ended=term_u8)
+                               reward_sum=out["reward"], ended=term_u8, sample_u=s_all, prob=out["prob"] if soft else None)
             for t in range(0 if one_launch else T):
                 obs = out["obs"][t]
                 restart = self._restart if t == 0 else term_u8[t - 1]
                 self.actor.forward_fused(obs, self.hidden, append_agent_id=self.obs_agent_id, restart=restart, q_out=self._q,
                                          actions_out=out["actions"][t], explore_u=None if u_all is None else u_all[t],
-                                         epsilon=eps)
+                                         epsilon=eps, sample_u=s_all[t] if soft else None, prob_out=out["prob"][t] if soft else None)
                 rc = env.step_into(out["actions"][t].data_ptr(), out["obs"][t + 1].data_ptr(), out["reward"][t].data_ptr(),
                                    term_u8[t].data_ptr())
                 if rc != 0:
@@ -318,7 +337,7 @@ class BatchedRunner(object):
             out["state"][t] = obs.reshape(E, N * D)
             out["episode_start"][t] = self._restart.view(torch.bool)
             if fused:
-                greedy = out["actions"][t] if self.epsilon <= 0.0 else None
+                greedy = out["actions"][t] if self.epsilon <= 0.0 and not soft else None
                 _, greedy = self.actor.forward_fused(obs.contiguous(), self.hidden, append_agent_id=self.obs_agent_id,
                                                      restart=self._restart, q_out=self._q, actions_out=greedy)
             else:
@@ -326,7 +345,11 @@ class BatchedRunner(object):
                 q, h = self.actor.forward(torch.cat([obs, eye], dim=2) if self.obs_agent_id else obs, h_in)
                 self.hidden.copy_(h)
                 greedy = q.argmax(dim=2).to(torch.int32)
-            if eps > 0.0:
+                if soft:
+                    self._q.copy_(q)
+            if soft:   # the rule of the sampled launches, composed from torch ops on the logits the actor wrote
+                soft_select(self._q, s_all[t], out_actions=out["actions"][t], out_prob=out["prob"][t])
+            elif eps > 0.0:
                 explore_select(greedy, u_all[t], eps, A, out=out["actions"][t])
             elif not fused:
                 out["actions"][t] = greedy

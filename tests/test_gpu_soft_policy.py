@@ -1,0 +1,338 @@
+"""Soft-policies sampling on the GPU: the sampled actor launch against the numpy twin fed with the launch's own logits (actions and
+`prob` bit for bit; `q` and the hidden state bit for bit what the greedy launch writes), one rg_policy_rollout_sample launch
+against the two-launch loop, and BatchedRunner(action_selector="soft_policies") on its three paths.
+
+Weights: tests/golden/zoo_mappo_pcp.npz holds the tensors of the reference zoo's PredatorCapturePrey `mappo` checkpoint (shared GRU,
+hidden 128, 16 + 4 inputs: the scenario's default four agents; plain float32 arrays under `sd_<state-dict key>`, written with
+np.savez_compressed, 382 428 bytes); the committed actor_*_h64.npz fixtures (shared and per-agent GRU,
+hidden 64) have the same input width and run on the same scenario.  The other scenarios' input widths fit none of the committed
+weight fixtures, so they run seeded random weights of the zoo's shapes (hidden 128 shared; ArcticTransport also per agent)."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import soft_twin
+from test_gpu_actor import _random_actor
+
+pytestmark = pytest.mark.gpu
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+DEV = "cuda:0"
+
+
+def _bits(t):
+    return t.detach().cpu().numpy().view(np.uint32)
+
+
+def _fixture_sd(name):
+    g = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
+    return {k[3:]: torch.from_numpy(g[k]) for k in g.files if k.startswith("sd_")}
+
+
+# ---------------------------------------------------------------------------------------------- 8. the sampled actor launch
+@pytest.mark.parametrize("restart_flags", [False, True])
+@pytest.mark.parametrize("shared,H,E,N,D,A,use_rnn,pack", [
+    (True, 128, 301, 5, 16, 5, True, True),        # two binary16 planes (the default); 1505 rows: the last tile holds one
+    (True, 128, 77, 5, 16, 7, True, "bf16x3"),
+    (True, 128, 70, 3, 16, 32, True, "f32"),
+    (True, 128, 45, 4, 9, 5, True, False),         # torch-layout GRU weights
+    (True, 128, 33, 8, 18, 32, False, True),       # use_rnn = 0
+    (False, 128, 41, 4, 30, 7, True, True),        # per-agent weights: a tile per agent index, 41 envs = one full tile + 9 rows
+    (False, 128, 50, 4, 9, 20, False, False),
+    (True, 64, 77, 4, 9, 32, True, True),
+    (True, 64, 130, 5, 16, 5, True, "bf16x3"),
+    (True, 64, 67, 3, 16, 7, True, "f32"),
+    (False, 64, 65, 3, 32, 7, True, True),
+    (False, 64, 35, 5, 16, 32, True, False),
+    (True, 64, 33, 6, 12, 5, False, True),
+])
+def test_sampled_launch_matches_the_twin(shared, H, E, N, D, A, use_rnn, pack, restart_flags):
+    from marbler_amd.evaluate import BatchedActor, soft_select
+    sd = _random_actor(1 if shared else N, D + N, H, A, use_rnn, seed=H + E + A)
+    for k in sd:   # logits a few units apart (the random heads alone give near-uniform rows), one column that can never be chosen
+        if k.endswith("fc2.weight"):
+            sd[k] = sd[k] * 12.0
+        if k.endswith("fc2.bias") and A >= 7:
+            sd[k][1] = float("-inf")
+    actor = BatchedActor(sd, N, use_rnn=use_rnn, device=DEV, pack_gru=pack)
+    g = torch.Generator(device=DEV).manual_seed(E)
+    hidden = torch.rand(E, N, H, generator=g, device=DEV) * 2 - 1
+    h_greedy = hidden.clone()
+    restart = (torch.rand(E, generator=g, device=DEV) < 0.3).to(torch.uint8) if restart_flags else None
+    if restart_flags:
+        restart[E // 2] = 0                        # (the env that gets the NaN observation below keeps it)
+    for step in range(3):
+        obs = torch.rand(E, N, D, generator=g, device=DEV) * 2 - 1
+        if step == 1:
+            obs[E // 2, 0, 0] = float("nan")       # a row of NaN logits: the greedy action, prob = NaN
+        u = torch.rand(E, N, generator=g, device=DEV)
+        u[0, 0], u[-1, -1] = 0.0, float(np.nextafter(np.float32(1), np.float32(0)))
+        prob = torch.full((E, N), -1.0, device=DEV)
+        q, act = actor.forward_fused(obs, hidden, restart=restart, sample_u=u, prob_out=prob)
+        q0, act0 = actor.forward_fused(obs, h_greedy, restart=restart)
+        torch.cuda.synchronize()
+        # the selector changes the action only
+        assert np.array_equal(_bits(q), _bits(q0)) and np.array_equal(_bits(hidden), _bits(h_greedy))
+        ta, tp = soft_twin.soft_select(q.cpu().numpy(), u.cpu().numpy())
+        assert np.array_equal(act.cpu().numpy(), ta)
+        assert np.array_equal(_bits(prob), tp.view(np.uint32))
+        # ... and the torch restatement on the device says the same
+        sa, sp = soft_select(q, u)
+        assert torch.equal(sa, act) and np.array_equal(_bits(sp), _bits(prob))
+        bad = ~np.isfinite(q.cpu().numpy().max(-1))
+        assert np.array_equal(act.cpu().numpy()[bad], act0.cpu().numpy()[bad]) and np.isnan(prob.cpu().numpy()[bad]).all()
+        if step == 1:
+            assert bad.any()
+        if A >= 7:
+            assert not (act == 1).any()
+        assert (act.cpu().numpy()[~bad] != act0.cpu().numpy()[~bad]).any()      # it does sample
+
+
+def test_python_argument_checks_on_the_device():
+    from marbler_amd.evaluate import BatchedActor
+    actor = BatchedActor(_random_actor(1, 13, 64, 5, True, seed=1), 4, device=DEV)
+    obs, hidden = torch.zeros(3, 4, 9, device=DEV), torch.zeros(3, 4, 64, device=DEV)
+    u = torch.zeros(3, 4, device=DEV)
+    with pytest.raises(ValueError, match="do not combine"):
+        actor.forward_fused(obs, hidden, sample_u=u, explore_u=u, epsilon=0.1)
+    with pytest.raises(ValueError, match="prob_out needs sample_u"):
+        actor.forward_fused(obs, hidden, prob_out=u)
+    for bad in (torch.zeros(3, 5, device=DEV), u.double(), torch.zeros(4, 3, device=DEV).t()):
+        with pytest.raises(ValueError, match="sample_u must be"):
+            actor.forward_fused(obs, hidden, sample_u=bad)
+    with pytest.raises(ValueError, match="prob_out must be"):
+        actor.forward_fused(obs, hidden, sample_u=u, prob_out=torch.zeros(3, 4, 1, device=DEV))
+
+
+# ---------------------------------------------------------------------------------------------- 9. one launch against two
+PCP5 = {"predator": 3, "capture": 2, "n_agents": 5}
+CASES = [  # id, key, overrides, weights (fixture name or ("random", shared, hidden))
+    ("pcp4-mappo", "robotarium_gym:PredatorCapturePrey-v0", None, "zoo_mappo_pcp"),
+    ("pcp4-shared-h64", "robotarium_gym:PredatorCapturePrey-v0", None, "actor_shared_gru_h64"),
+    ("pcp4-ns-h64", "robotarium_gym:PredatorCapturePrey-v0", None, "actor_ns_gru_h64"),
+    ("pcp5", "robotarium_gym:PredatorCapturePrey-v0", PCP5, ("random", True, 128)),
+    ("warehouse", "robotarium_gym:Warehouse-v0", None, ("random", True, 128)),
+    ("material", "robotarium_gym:MaterialTransport-v0", None, ("random", True, 128)),
+    ("arctic", "robotarium_gym:ArcticTransport-v0", None, ("random", True, 128)),
+    ("arctic-ns", "robotarium_gym:ArcticTransport-v0", None, ("random", False, 64)),
+]
+
+
+def _actor_for(weights, v):
+    from marbler_amd.evaluate import BatchedActor
+    N = v.n_agents
+    if isinstance(weights, str):
+        sd = _fixture_sd(weights)
+    else:
+        _, shared, H = weights
+        sd = _random_actor(1 if shared else N, v.obs_size + N, H, v.n_actions, True, seed=4)
+        for k in sd:
+            if k.endswith("fc2.weight"):
+                sd[k] = sd[k] * 8.0
+    return BatchedActor(sd, N, device=v.env.device)
+
+
+def _runner(key, ov, weights, E, selector="soft_policies", limit=12, seed=9, **kw):
+    from marbler_amd.gymma import BatchedRunner, GymmaVecEnv
+    v = GymmaVecEnv(key, E, time_limit=limit, seed=5, overrides=ov)
+    return v, BatchedRunner(v, _actor_for(weights, v), seed=seed, action_selector=selector, **kw)
+
+
+def _assert_same_dict(x, y):
+    assert x.keys() == y.keys()
+    for k in x:
+        if x[k].dtype == torch.float32:
+            assert np.array_equal(_bits(x[k]), _bits(y[k])), k
+        else:
+            assert torch.equal(x[k], y[k]), k
+
+
+def _assert_same_state(r1, r2):
+    (v1, a), (v2, b) = r1, r2
+    torch.cuda.synchronize()
+    assert torch.equal(a.hidden, b.hidden) and torch.equal(a._restart, b._restart)
+    assert torch.equal(v1.get_obs(), v2.get_obs()) and torch.equal(v1._ended, v2._ended)
+    assert v1.get_stats() == v2.get_stats()
+    s1, s2 = v1.env.state_dict(), v2.env.state_dict()
+    for k in s1:
+        assert torch.equal(s1[k], s2[k]), k
+
+
+@pytest.mark.parametrize("name,key,ov,weights", CASES, ids=[c[0] for c in CASES])
+def test_one_sampled_launch_equals_two_launch_loop(name, key, ov, weights):
+    """restart_on_done = 0 (a gymma runner restarts after `ended`), auto-reset on: 64 sampled steps."""
+    E, T = 100, 64
+    (v1, a), (v2, b) = _runner(key, ov, weights, E), _runner(key, ov, weights, E)
+    x, y = a.run(T), b.run(T, one_launch=True)
+    assert "prob" in x and x["prob"].shape == (T, E, v1.n_agents)
+    _assert_same_dict(x, y)
+    assert int(x["terminated"].sum()) > 0
+    _assert_same_state((v1, a), (v2, b))
+    p = x["prob"]
+    assert bool(((p > 0) & (p <= 1)).all())
+
+
+@pytest.mark.parametrize("name,key,ov,weights", CASES, ids=[c[0] for c in CASES])
+def test_one_sampled_launch_restart_on_done(name, key, ov, weights):
+    """restart_on_done = 1 (run_eval's loop: the actor restarts after the scenario's own `done`), auto-reset on: 64 sampled steps
+    through rg_actor_forward_sample + the env step against ONE rg_policy_rollout_sample launch."""
+    from marbler_amd import _lib
+    from marbler_amd.evaluate import policy_rollout
+    from marbler_amd.vec_env import VecRobotariumEnv
+    scenario = key.split(":")[1][:-3]
+    E, T = 100, 64
+    envs = [VecRobotariumEnv(scenario, E, overrides=ov, device=DEV, seed=3) for _ in range(2)]
+    N = envs[0].N
+    stub = type("V", (), {"n_agents": N, "obs_size": envs[0].D, "n_actions": {"MaterialTransport": 20}.get(scenario, 5), "env": envs[0]})
+    actor = _actor_for(weights, stub)
+    g = torch.Generator(device=DEV).manual_seed(21)
+    u = torch.rand(T, E, N, generator=g, device=DEV)
+    out = []
+    for which, env in enumerate(envs):
+        env.reset()
+        hidden = actor.init_hidden(E)
+        act = torch.empty(T, E, N, dtype=torch.int32, device=DEV)
+        prob = torch.empty(T, E, N, device=DEV)
+        dist = torch.zeros(E, N, device=DEV)
+        if which == 0:
+            q = torch.empty(E, N, actor.n_actions, device=DEV)
+            for t in range(T):
+                actor.forward_fused(env.obs, hidden, restart=env.done_u8, q_out=q, actions_out=act[t], sample_u=u[t], prob_out=prob[t])
+                env.step(act[t])
+                dist.add_(env.dist_travelled)
+        else:   # the launch always runs the gymma block: a TimeLimit that never fires (as run_eval does)
+            io = _lib.RgStepIO.from_buffer_copy(env._io)
+            scratch = [torch.zeros(E, dtype=torch.int32, device=DEV), torch.zeros(E, dtype=torch.uint8, device=DEV),
+                       torch.zeros(E, dtype=torch.uint8, device=DEV), torch.zeros(E, device=DEV)]
+            io.elapsed, io.truncated, io.ended, io.reward_sum = (t.data_ptr() for t in scratch)
+            io.time_limit = 2 ** 31 - 1
+            policy_rollout(env, actor, T, io, hidden, act, restart=env.done_u8, restart_on_done=True, dist_sum=dist, sample_u=u,
+                           prob=prob)
+        torch.cuda.synchronize()
+        out.append((act, prob, hidden, dist, env.obs.clone(), env.reward.clone(), env.done_u8.clone(), env.state_dict(),
+                    [float(s) for s in env.episode_stats()]))
+    for i, (p, q_) in enumerate(zip(out[0][:7], out[1][:7])):
+        assert np.array_equal(p.cpu().numpy().view(np.uint8), q_.cpu().numpy().view(np.uint8)), i
+    for k in out[0][7]:
+        assert torch.equal(out[0][7][k], out[1][7][k]), k
+    assert out[0][8] == out[1][8]                           # the episode statistics
+
+
+def test_policy_rollout_sample_refusals_with_a_handle():
+    from marbler_amd import _lib
+    from marbler_amd.evaluate import BatchedActor
+    from marbler_amd.gymma import GymmaVecEnv
+    lib = _lib.load()
+    v = GymmaVecEnv("robotarium_gym:PredatorCapturePrey-v0", 8, time_limit=10, seed=1)
+    env, N, T = v.env, v.n_agents, 2
+    u = torch.rand(T, 8, N, device=DEV)
+    act = torch.zeros(T, 8, N, dtype=torch.int32, device=DEV)
+
+    def call(actor, explore=None, sample=True, io=None, T_=T):
+        ws = actor._weights_struct()
+        hidden = actor.init_hidden(8)
+        pio = _lib.RgPolicyIO(hidden.data_ptr(), None, 1, 0, explore, 0.1, act.data_ptr(), None, None, None, None)
+        ps = _lib.RgPolicySample(u.data_ptr() if sample else None, None)
+        rc = lib.rg_policy_rollout_sample(env._h, C.byref(ws), T_, C.byref(pio), C.byref(ps), C.byref(io or env._io_into), 1, 0)
+        torch.cuda.synchronize()
+        return rc, lib.rg_last_error().decode()
+
+    good = BatchedActor(_random_actor(1, v.obs_size + N, 64, 5, True, seed=2), N, device=DEV)
+    assert call(good)[0] == 0
+    assert call(good, sample=False)[0] == -55
+    rc, msg = call(good, explore=u.data_ptr())
+    assert rc == -56 and "explore_u" in msg
+    assert call(good, T_=0)[0] == -27
+    rc, msg = call(BatchedActor(_random_actor(1, v.obs_size + N, 64, 5, True, seed=2), N, device=DEV, pack_gru="bf16x3"))
+    assert rc == -41 and "gru_packed == 3" in msg
+    assert call(BatchedActor(_random_actor(1, v.obs_size + N, 64, 5, False, seed=2), N, use_rnn=False, device=DEV))[0] == -41
+    assert call(BatchedActor(_random_actor(1, v.obs_size + N + 1, 64, 5, True, seed=2), N, device=DEV))[0] == -44
+    rc, msg = call(good, io=_lib.RgStepIO.from_buffer_copy(VecRobotariumEnvIO(env)))
+    assert rc == -29 and "gymma block" in msg
+    ipm = GymmaVecEnv("robotarium_gym:PredatorCapturePrey-v0", 8, time_limit=10, seed=1, overrides={"barrier_solver": "cvxopt"})
+    env = ipm.env
+    rc, msg = call(good)
+    assert rc == -40 and "interior-point" in msg
+
+
+def VecRobotariumEnvIO(env):
+    """The env's step io without the gymma block."""
+    from marbler_amd import _lib
+    io = _lib.RgStepIO.from_buffer_copy(env._io_into)
+    io.elapsed = io.truncated = io.ended = io.reward_sum = None
+    return io
+
+
+# ---------------------------------------------------------------------------------------------- 10. / 11. the runner
+def test_runner_three_paths_agree_and_prob_is_the_twins():
+    key, T, E = "robotarium_gym:PredatorCapturePrey-v0", 40, 90
+    (v1, a), (v2, b) = (_runner(key, None, "zoo_mappo_pcp", E) for _ in range(2))
+    v3, c = _composed_runner(key, None, "zoo_mappo_pcp", E)     # fused=False env: the fused actor, soft_select and v.step from torch ops
+    x, y, z = a.run(T), b.run(T, one_launch=True), c.run(T)
+    _assert_same_dict(x, y)
+    for k in x:
+        if k != "state":
+            assert (np.array_equal(_bits(x[k]), _bits(z[k])) if x[k].dtype == torch.float32 else torch.equal(x[k], z[k])), k
+    assert torch.equal(x["state"], z["state"])
+    # prob[t, e, n] is the twin's softmax of the replayed q at the stored action
+    actor = _actor_for("zoo_mappo_pcp", v1)
+    hidden = actor.init_hidden(E)
+    logp, ent_gap = [], []
+    for t in range(T):
+        restart = x["episode_start"][t].to(torch.uint8)
+        q, _ = actor.forward_fused(x["obs"][t].contiguous(), hidden, restart=restart)
+        qn = q.cpu().numpy()
+        m = qn.max(-1, keepdims=True)
+        e = soft_twin.soft_exp(qn - m)
+        run = np.zeros(qn.shape[:-1], np.float32)
+        for k in range(qn.shape[-1]):
+            run = run + e[..., k]
+        stored = x["actions"][t].cpu().numpy().astype(np.int64)
+        want = np.take_along_axis(e, stored[..., None], -1)[..., 0] / run
+        assert np.array_equal(want.view(np.uint32), _bits(x["prob"][t]))
+        p64 = soft_twin.softmax64(qn)
+        lp = np.log(np.maximum(p64, 1e-300))
+        mean = (p64 * lp).sum(-1)                                    # E[log p(a)] = -entropy
+        var = (p64 * lp ** 2).sum(-1) - mean ** 2
+        logp.append((np.log(x["prob"][t].cpu().numpy().astype(np.float64)) - mean).ravel())
+        ent_gap.append(var.ravel())
+    d, var = np.concatenate(logp), np.concatenate(ent_gap)
+    stderr = np.sqrt(var.sum()) / d.size
+    print(f"mean log prob - expectation: {d.mean():.3e}, standard error {stderr:.3e}, {d.size} draws")
+    assert abs(d.mean()) < 5 * stderr
+
+
+def _composed_runner(key, ov, weights, E, **kw):
+    from marbler_amd.gymma import BatchedRunner, GymmaVecEnv
+    v = GymmaVecEnv(key, E, time_limit=12, seed=5, overrides=ov, fused=False)
+    return v, BatchedRunner(v, _actor_for(weights, v), seed=9, action_selector="soft_policies", **kw)
+
+
+def test_default_selector_is_unchanged_and_test_mode_is_greedy():
+    from marbler_amd.gymma import BatchedRunner, GymmaVecEnv
+    key, T, E = "robotarium_gym:Warehouse-v0", 30, 70
+    w = ("random", True, 128)
+
+    def plain(**kw):   # the existing path: the constructor as every caller wrote it before the selector existed
+        v = GymmaVecEnv(key, E, time_limit=12, seed=5)
+        return v, BatchedRunner(v, _actor_for(w, v), seed=9, **kw)
+
+    for one in (False, True):
+        (v0, g), (v1, d), (v2, tm) = plain(), _runner(key, None, w, E, selector="epsilon_greedy"), _runner(key, None, w, E, test_mode=True)
+        x, y, z = g.run(T, one_launch=one), d.run(T, one_launch=one), tm.run(T, one_launch=one)
+        assert "prob" not in x and "prob" not in y and "prob" not in z
+        _assert_same_dict(x, y)
+        _assert_same_dict(x, z)
+        _assert_same_state((v0, g), (v1, d))
+        _assert_same_state((v0, g), (v2, tm))
+    (v0, g), (v1, d) = plain(epsilon=0.1), _runner(key, None, w, E, selector="epsilon_greedy", epsilon=0.1)
+    _assert_same_dict(g.run(T), d.run(T, one_launch=True))
+    # sampling draws from the runner's generator exactly as the epsilon path does: a second call continues the stream
+    (v3, s1), (v4, s2) = _runner(key, None, w, E), _runner(key, None, w, E)
+    a1, a2 = s1.run(T), s1.run(T)
+    b1, b2 = s2.run(T, one_launch=True), s2.run(T)
+    _assert_same_dict(a1, b1)
+    _assert_same_dict(a2, b2)
+    assert not torch.equal(a1["actions"], a2["actions"])
