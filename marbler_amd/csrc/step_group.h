@@ -244,14 +244,32 @@ __device__ __forceinline__ int controller(const rg_scenario_params &p, const Con
             }
         }
     };
-    while (__any(active)) {
-        sweep(std::integral_constant<int, 1>{});
-        if (!__any(active)) break;
-        sweep(std::integral_constant<int, 2>{});
-        if (!__any(active)) break;
-        sweep(std::integral_constant<int, 3>{});
-        if (!__any(active)) break;
-        sweep(std::integral_constant<int, 0>{});
+    if constexpr (SPAN) {
+        // The rows' loop is a DIVERGENT one: an env leaves it with its own verdict, and the sweeps that follow run for the envs still
+        // in it.  The verdict's compare is then the exec mask of the next sweep -- one scalar and, one saveexec, one branch on "no
+        // env left" -- where the wave-uniform loop below makes the compiler turn the flags into a register and back twice per
+        // sweep and copy the multipliers from sweep to sweep.  The envs of a wave still step through the phases together (an env
+        // that has left is masked, not behind), so `sweeps` stays the wave's count and every env sees the sweeps, the restarts
+        // and the cap it saw before.
+        while (active) {
+            sweep(std::integral_constant<int, 1>{});
+            if (!active) break;
+            sweep(std::integral_constant<int, 2>{});
+            if (!active) break;
+            sweep(std::integral_constant<int, 3>{});
+            if (!active) break;
+            sweep(std::integral_constant<int, 0>{});
+        }
+    } else {
+        while (__any(active)) {
+            sweep(std::integral_constant<int, 1>{});
+            if (!__any(active)) break;
+            sweep(std::integral_constant<int, 2>{});
+            if (!__any(active)) break;
+            sweep(std::integral_constant<int, 3>{});
+            if (!__any(active)) break;
+            sweep(std::integral_constant<int, 0>{});
+        }
     }
     if constexpr (SPAN) {
         ux = to_upper_half(ux);
