@@ -6,6 +6,7 @@ hipcc cross-compiles without a GPU.  -ffp-contract=off: the kernels' float arith
 explicit sequence of IEEE operations (csrc/sim_math.h) that the CPU oracle reproduces bit for
 bit; implicit fma contraction would break that.
 """
+import glob
 import os
 import shutil
 import subprocess
@@ -19,9 +20,8 @@ SOURCES = ["robogym_kernels.hip", "robogym_rollout_group.hip", "robogym_kernels_
            "robogym_policy_h128.hip", "robogym_policy_sample_h64.hip", "robogym_policy_sample_h128.hip", "robogym_lidar.hip", "robogym_lidar_rollout.hip", "robogym_lidar_ipm.hip",
            "robogym_lidar_rollout_ipm.hip", "robogym_team.hip", "robogym_team_rollout.hip", "robogym_team_ipm.hip",
            "robogym_team_rollout_ipm.hip"]
-HEADERS = [os.path.join(CSRC, h) for h in ("sim_math.h", "kernel_args.h", "device_common.h", "step_group.h", "step_tpe.h", "step_tpe_ipm.h", "ipm_qp.h",
-                                           "actor_common.h", "actor_body.inc", "policy_rollout.h", "policy_body.inc", "lidar.h", "lidar_kernels.h", "team.h", "team_kernels.h", os.path.join("probes", "diag.h"), os.path.join("probes", "actor_diag.h"))
-                                           if os.path.exists(os.path.join(CSRC, h))] + \
+# every header of csrc/ (a forgotten one would mean a stale library), and the C ABI's
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(CSRC, "probes", "*.h"))) + \
           [os.path.join(HERE, "..", "include", "robogym.h")]
 ARCH = "gfx950"
 # Per-file flags (results are bit-identical either way: the same IEEE operations; tools/ab_job.sh measured them).
@@ -58,10 +58,10 @@ FILE_FLAGS = {"robogym_tpe.hip": ["-fno-slp-vectorize"], "robogym_rollout_tpe.hi
               "robogym_kernels_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_rollout_group_ipm.hip": GROUP_SLP + IPM_SCHED,
               "robogym_policy_h64.hip": GROUP_SLP, "robogym_policy_h128.hip": GROUP_SLP,
               "robogym_policy_sample_h64.hip": GROUP_SLP, "robogym_policy_sample_h128.hip": GROUP_SLP,
-              # the lidar kernels (lidar_kernels.h): lane-group kernels, with the flags of their mode
+              # the lidar kernels (step_group.h lidar_step_kernel): lane-group kernels, with the flags of their mode
               "robogym_lidar.hip": GROUP_SLP, "robogym_lidar_rollout.hip": GROUP_SLP,
               "robogym_lidar_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_lidar_rollout_ipm.hip": GROUP_SLP + IPM_SCHED,
-              # the team kernels (team_kernels.h): lane-group kernels, with the flags of their mode
+              # the team kernels (step_group.h team_step_kernel): lane-group kernels, with the flags of their mode
               "robogym_team.hip": GROUP_SLP, "robogym_team_rollout.hip": GROUP_SLP,
               "robogym_team_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_team_rollout_ipm.hip": GROUP_SLP + IPM_SCHED}
 BASE_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]

@@ -207,6 +207,20 @@ struct WaveSync {
     }
 };
 
+#ifndef RG_HOST_SIM
+// A kernel's argument block (its only argument, at offset 0) through an address the compiler cannot see through: an opaque copy
+// of the kernel-argument segment's address.  A loop that re-addresses the block this way every iteration keeps the compiler from
+// hoisting the argument loads out of the loop and holding them across its whole body (step_group.h, policy_body.inc).
+// (Not the address of the argument itself: taking that makes the compiler copy the block to scratch.)
+template <typename T>
+__device__ __forceinline__ const __attribute__((address_space(4))) T *kernarg_block() {
+    typedef const __attribute__((address_space(4))) T *ArgPtr;
+    ArgPtr pp = (ArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(pp));
+    return pp;
+}
+#endif
+
 // ------------------------------------------------------------------ LDS scratch (one wavefront)
 // The step's scratch and the reset sampler's are never live together (the fused reset runs after the step's last LDS
 // read, an explicit reset runs alone), so they share the block: 7.5 KB instead of 13.5 KB per one-wave workgroup --

@@ -4,6 +4,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/robogym.h"
 
 namespace rg {
@@ -77,7 +79,7 @@ struct KernelArgs {
     const int32_t *actions;
     const uint8_t *reset_mask;
     int32_t E;
-    int32_t envs_per_wave; // lane-group kernel: env slots used per wavefront (0 = all 64/GW; fewer for small batches, see launch_step_scn)
+    int32_t envs_per_wave; // lane-group kernel: env slots used per wavefront (0 = all 64/GW; fewer for small batches, see wave_fill)
     int32_t num_steps;  // env steps per launch (rg_step: 1); io and actions carry a leading dimension of this size
     int32_t auto_reset;
     int32_t reset_flags;  // rg_reset: RG_RESET_*
@@ -95,8 +97,52 @@ inline int next_init_stride(const rg_scenario_params &p) {
     return (w + 3) & ~3;
 }
 
-hipError_t launch_step(const KernelArgs &a, bool obs_only, hipStream_t stream);
+// f(std::integral_constant<int, SCN>()) for the scenario id `scn`: where a launch turns the scenario into a template argument
+template <typename F>
+inline hipError_t for_scenario(int scn, F &&f) {
+    switch (scn) {
+        case RG_SCN_PREDATOR_CAPTURE_PREY: return f(std::integral_constant<int, RG_SCN_PREDATOR_CAPTURE_PREY>());
+        case RG_SCN_WAREHOUSE: return f(std::integral_constant<int, RG_SCN_WAREHOUSE>());
+        case RG_SCN_MATERIAL_TRANSPORT: return f(std::integral_constant<int, RG_SCN_MATERIAL_TRANSPORT>());
+        case RG_SCN_SIMPLE: return f(std::integral_constant<int, RG_SCN_SIMPLE>());
+        case RG_SCN_ARCTIC_TRANSPORT: return f(std::integral_constant<int, RG_SCN_ARCTIC_TRANSPORT>());
+        default: return hipErrorInvalidValue;
+    }
+}
+
 hipError_t launch_reset(const KernelArgs &a, hipStream_t stream);
+
+// The lane-group step kernels (step_group.h) come in three families -- plain, with the lidar block (rg_set_lidar), with a team
+// pool (rg_set_teams) -- and every (family, solver mode, launch kind) has a translation unit of its own with ONE entry, so that
+// they compile side by side and each gets its mode's flags (build.py FILE_FLAGS).  The list: X(entry, family, qp_mode, kind).
+// An observation-only launch (rg_get_obs) runs no controller: it exists in the exact mode only and serves both.
+enum GroupFamily { GROUP_PLAIN, GROUP_LIDAR, GROUP_TEAM };
+enum GroupKind { GROUP_STEP, GROUP_ROLLOUT, GROUP_OBS };
+#define RG_GROUP_ENTRIES(X)                                              \
+    X(launch_step, GROUP_PLAIN, RG_QP_EXACT, GROUP_STEP)                 \
+    X(launch_obs, GROUP_PLAIN, RG_QP_EXACT, GROUP_OBS)                   \
+    X(launch_rollout, GROUP_PLAIN, RG_QP_EXACT, GROUP_ROLLOUT)           \
+    X(launch_step_ipm, GROUP_PLAIN, RG_QP_CVXOPT, GROUP_STEP)            \
+    X(launch_rollout_ipm, GROUP_PLAIN, RG_QP_CVXOPT, GROUP_ROLLOUT)      \
+    X(launch_lidar_step, GROUP_LIDAR, RG_QP_EXACT, GROUP_STEP)           \
+    X(launch_lidar_obs, GROUP_LIDAR, RG_QP_EXACT, GROUP_OBS)             \
+    X(launch_lidar_rollout, GROUP_LIDAR, RG_QP_EXACT, GROUP_ROLLOUT)     \
+    X(launch_lidar_step_ipm, GROUP_LIDAR, RG_QP_CVXOPT, GROUP_STEP)      \
+    X(launch_lidar_rollout_ipm, GROUP_LIDAR, RG_QP_CVXOPT, GROUP_ROLLOUT) \
+    X(launch_team_step, GROUP_TEAM, RG_QP_EXACT, GROUP_STEP)             \
+    X(launch_team_obs, GROUP_TEAM, RG_QP_EXACT, GROUP_OBS)               \
+    X(launch_team_rollout, GROUP_TEAM, RG_QP_EXACT, GROUP_ROLLOUT)       \
+    X(launch_team_step_ipm, GROUP_TEAM, RG_QP_CVXOPT, GROUP_STEP)        \
+    X(launch_team_rollout_ipm, GROUP_TEAM, RG_QP_CVXOPT, GROUP_ROLLOUT)
+// what a family's kernels take next to the KernelArgs: the handle's lidar and pool blocks (the plain family reads neither)
+struct GroupSide {
+    const rg_lidar_params *lidar;
+    const rg_team_params *teams;
+};
+typedef hipError_t GroupLaunch(const KernelArgs &a, const GroupSide &side, hipStream_t stream);
+#define RG_X(entry, family, mode, kind) GroupLaunch entry;
+RG_GROUP_ENTRIES(RG_X)
+#undef RG_X
 
 // the k-th step's slice of the action and output arrays
 struct StepView {
@@ -125,12 +171,7 @@ __host__ __device__ inline StepView step_view(const KernelArgs &a, int k, int n_
 // thread-per-env step kernel (robogym_tpe.hip): same results, chosen by the host for large batches
 bool tpe_supported(const rg_scenario_params &p);
 hipError_t launch_step_tpe(const KernelArgs &a, hipStream_t stream);
-// rg_rollout: num_steps env steps per launch (robogym_rollout_group.hip, robogym_rollout_tpe.hip)
-hipError_t launch_rollout(const KernelArgs &a, hipStream_t stream);
+// rg_rollout: num_steps env steps per launch (robogym_rollout_tpe.hip)
 hipError_t launch_rollout_tpe(const KernelArgs &a, hipStream_t stream);
-// the lane-group kernels of the interior-point mode (robogym_kernels_ipm.hip, robogym_rollout_group_ipm.hip); a.envs_per_wave and
-// the grid as launch_step_scn computed them
-hipError_t launch_step_ipm(const KernelArgs &a, int grid, hipStream_t stream);
-hipError_t launch_rollout_ipm(const KernelArgs &a, int grid, hipStream_t stream);
 
 }  // namespace rg

@@ -25,14 +25,10 @@
     __syncthreads();
 
     for (int t = 0; t < T; ++t) {
-        // The argument block is re-addressed every time step (an opaque copy of the kernel-argument segment's address; the block is
-        // the kernel's only argument, at offset 0): left loop-invariant, the compiler hoists every kernel-argument load of the actor
-        // AND of the env step out of the time loop and holds all of them across both phases -- the whole register file and hundreds
-        // of spilled values.  (Not `&pa_in`: taking the argument's address makes the compiler copy it to scratch.)
-        typedef const __attribute__((address_space(4))) PolicyArgs *ArgPtr;
-        ArgPtr pp = (ArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(pp));
-        const PolicyArgs &pa = *(const PolicyArgs *)pp;
+        // The argument block is re-addressed every time step (device_common.h kernarg_block): left loop-invariant, the compiler
+        // hoists every kernel-argument load of the actor AND of the env step out of the time loop and holds all of them across
+        // both phases -- the whole register file and hundreds of spilled values.
+        const PolicyArgs &pa = *(const PolicyArgs *)kernarg_block<PolicyArgs>();
         const KernelArgs &a = pa.k;
         const rg_policy_io &io = pa.io;
         int32_t *act_t = io.actions + static_cast<size_t>(t) * EN;

@@ -109,14 +109,7 @@ static hipError_t launch_policy_h(const KernelArgs &k, const rg_actor_weights &w
     pa.act.explore_scale = io.explore_u ? static_cast<float>(w.n_actions) / io.epsilon : 0.0f;
     pa.act.sample_u = sample ? sample->sample_u : nullptr;
     pa.act.prob = sample ? sample->prob : nullptr;
-    switch (k.p.scenario) {
-        case RG_SCN_PREDATOR_CAPTURE_PREY: return launch_policy_scn<RG_SCN_PREDATOR_CAPTURE_PREY, H, SAMPLE>(pa, stream);
-        case RG_SCN_WAREHOUSE: return launch_policy_scn<RG_SCN_WAREHOUSE, H, SAMPLE>(pa, stream);
-        case RG_SCN_MATERIAL_TRANSPORT: return launch_policy_scn<RG_SCN_MATERIAL_TRANSPORT, H, SAMPLE>(pa, stream);
-        case RG_SCN_SIMPLE: return launch_policy_scn<RG_SCN_SIMPLE, H, SAMPLE>(pa, stream);
-        case RG_SCN_ARCTIC_TRANSPORT: return launch_policy_scn<RG_SCN_ARCTIC_TRANSPORT, H, SAMPLE>(pa, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return for_scenario(k.p.scenario, [&](auto scn) { return launch_policy_scn<decltype(scn)::value, H, SAMPLE>(pa, stream); });
 }
 
 }  // namespace rg

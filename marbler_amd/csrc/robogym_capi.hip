@@ -144,23 +144,12 @@ hipError_t launch_policy_rollout_sample_h64(const KernelArgs &, const rg_actor_w
                                             int32_t, hipStream_t) __attribute__((weak));
 hipError_t launch_policy_rollout_sample_h128(const KernelArgs &, const rg_actor_weights &, const rg_policy_io &, const rg_policy_sample &,
                                              int32_t, hipStream_t) __attribute__((weak));
-// The lidar kernels (lidar_kernels.h) live in their own translation units; weak for the same reason.
-#define RG_LIDAR_LAUNCH(name) hipError_t name(const KernelArgs &, const rg_lidar_params &, hipStream_t) __attribute__((weak));
-RG_LIDAR_LAUNCH(launch_lidar_step)
-RG_LIDAR_LAUNCH(launch_lidar_obs)
-RG_LIDAR_LAUNCH(launch_lidar_rollout)
-RG_LIDAR_LAUNCH(launch_lidar_step_ipm)
-RG_LIDAR_LAUNCH(launch_lidar_rollout_ipm)
-#undef RG_LIDAR_LAUNCH
-// The team kernels (team_kernels.h) likewise.
-#define RG_TEAM_LAUNCH(name) hipError_t name(const KernelArgs &, const rg_team_params &, hipStream_t) __attribute__((weak));
-RG_TEAM_LAUNCH(launch_team_step)
-RG_TEAM_LAUNCH(launch_team_obs)
-RG_TEAM_LAUNCH(launch_team_rollout)
-RG_TEAM_LAUNCH(launch_team_step_ipm)
-RG_TEAM_LAUNCH(launch_team_rollout_ipm)
-RG_TEAM_LAUNCH(launch_team_index)
-#undef RG_TEAM_LAUNCH
+// The lane-group step kernels' entries (kernel_args.h RG_GROUP_ENTRIES: one translation unit each), and the team pool's index
+// writer next to them: weak for the same reason.
+#define RG_X(entry, family, mode, kind) GroupLaunch entry __attribute__((weak));
+RG_GROUP_ENTRIES(RG_X)
+#undef RG_X
+hipError_t launch_team_index(const KernelArgs &, const rg_team_params &, hipStream_t) __attribute__((weak));
 }  // namespace rg
 
 // The scenario's own observation width: the columns its builder writes (the lidar block may start at or after it).
@@ -173,6 +162,23 @@ static int own_obs_width(const rg_scenario_params &p) {
         case RG_SCN_ARCTIC_TRANSPORT: return 30;
         default: return p.capability_aware ? 11 : 9;
     }
+}
+
+// The entry of every (family, solver mode, launch kind) of the lane-group step kernels.
+static const struct GroupEntry {
+    rg::GroupLaunch *launch;
+    int family, mode, kind;
+} g_group[] = {
+#define RG_X(entry, family, mode, kind) {rg::entry, rg::family, mode, rg::kind},
+    RG_GROUP_ENTRIES(RG_X)
+#undef RG_X
+};
+
+// does this build hold every kernel of the family?  (The host-only sanitizer build holds none.)
+static bool group_family_built(int family) {
+    for (const GroupEntry &g : g_group)
+        if (g.family == family && !g.launch) return false;
+    return true;
 }
 
 extern "C" {
@@ -207,6 +213,10 @@ rg_handle *rg_create(const rg_scenario_params *params, int32_t num_envs, int64_t
     }
     if (device < 0 || device >= count) {
         fail(-13, "device index out of range");
+        return nullptr;
+    }
+    if (!group_family_built(rg::GROUP_PLAIN)) {   // (a library that lacks one of its translation units)
+        fail(-100, "rg_create: this build has no lane-group step kernels");
         return nullptr;
     }
     rg_handle *h = new (std::nothrow) rg_handle();
@@ -254,9 +264,7 @@ int rg_set_lidar(rg_handle *h, const rg_lidar_params *lp) {
     if (lp->offset < own_obs_width(h->params))
         return fail(-52, "rg_set_lidar: offset lies inside the scenario's own observation columns");
     if (!(lp->range > 0.0f && lp->range <= 3.402823466e38f)) return fail(-53, "rg_set_lidar: range must be positive and finite");
-    if (!rg::launch_lidar_step || !rg::launch_lidar_obs || !rg::launch_lidar_rollout || !rg::launch_lidar_step_ipm ||
-        !rg::launch_lidar_rollout_ipm)
-        return fail(-100, "rg_set_lidar: this build has no lidar kernels");
+    if (!group_family_built(rg::GROUP_LIDAR)) return fail(-100, "rg_set_lidar: this build has no lidar kernels");
     h->lidar = *lp;
     h->use_tpe = false;   // the lidar is built into the lane-group kernel only
     return 0;
@@ -356,6 +364,17 @@ static int launched(hipError_t err) {
     return 0;
 }
 
+// The lane-group launch of a handle: the family its side blocks select (a pool and the lidar exclude each other), the handle's
+// solver mode -- an observation-only launch runs no controller and uses the exact mode's kernel in either -- and the launch kind.
+static int launch_group_entry(const rg_handle *h, const rg::KernelArgs &a, int kind) {
+    const int family = h->teams.n_sets ? rg::GROUP_TEAM : h->lidar.rays ? rg::GROUP_LIDAR : rg::GROUP_PLAIN;
+    const int mode = kind == rg::GROUP_OBS ? RG_QP_EXACT : h->params.qp_mode;
+    const rg::GroupSide side = {&h->lidar, &h->teams};
+    for (const GroupEntry &g : g_group)
+        if (g.family == family && g.mode == mode && g.kind == kind && g.launch) return launched(g.launch(a, side, h->stream));
+    return fail(-100, "this build has no lane-group step kernels");
+}
+
 #define RG_ON_DEVICE(h)                                                                           \
     DeviceGuard guard_((h)->device);                                                              \
     if (guard_.err != hipSuccess) return fail(-31, "cannot select the handle's device: %s", hipGetErrorString(guard_.err))
@@ -385,14 +404,10 @@ int rg_step(rg_handle *h, const int32_t *actions, const rg_step_io *io, int32_t 
     a.seed = seed;
     RG_ON_DEVICE(h);
     if (int rc = sync_seed(h, seed)) return rc;
-    if (h->teams.n_sets)
-        return launched(h->params.qp_mode == RG_QP_CVXOPT ? rg::launch_team_step_ipm(a, h->teams, h->stream)
-                                                          : rg::launch_team_step(a, h->teams, h->stream));
-    if (h->lidar.rays)
-        return launched(h->params.qp_mode == RG_QP_CVXOPT ? rg::launch_lidar_step_ipm(a, h->lidar, h->stream)
-                                                          : rg::launch_lidar_step(a, h->lidar, h->stream));
-    if (!h->span) a.envs_per_wave = -1;   // asks launch_step for 8-lane groups throughout (it sets the real value itself)
-    return launched(h->use_tpe ? rg::launch_step_tpe(a, h->stream) : rg::launch_step(a, false, h->stream));
+    // (asks the plain family's dispatcher for 8-lane groups throughout: it sets the real value itself)
+    if (!h->span && !h->teams.n_sets && !h->lidar.rays) a.envs_per_wave = -1;
+    if (h->use_tpe) return launched(rg::launch_step_tpe(a, h->stream));
+    return launch_group_entry(h, a, rg::GROUP_STEP);
 }
 
 int rg_rollout(rg_handle *h, const int32_t *actions, int32_t num_steps, const rg_step_io *io, int32_t auto_reset,
@@ -414,13 +429,7 @@ int rg_rollout(rg_handle *h, const int32_t *actions, int32_t num_steps, const rg
     a.seed = seed;
     RG_ON_DEVICE(h);
     if (int rc = sync_seed(h, seed)) return rc;
-    if (h->teams.n_sets)
-        return launched(h->params.qp_mode == RG_QP_CVXOPT ? rg::launch_team_rollout_ipm(a, h->teams, h->stream)
-                                                          : rg::launch_team_rollout(a, h->teams, h->stream));
-    if (h->lidar.rays)
-        return launched(h->params.qp_mode == RG_QP_CVXOPT ? rg::launch_lidar_rollout_ipm(a, h->lidar, h->stream)
-                                                          : rg::launch_lidar_rollout(a, h->lidar, h->stream));
-    if (!h->use_tpe) return launched(rg::launch_rollout(a, h->stream));
+    if (!h->use_tpe) return launch_group_entry(h, a, rg::GROUP_ROLLOUT);
     // thread-per-env: the multi-step kernel holds more values live (313 VGPRs at N = 5: one wave per
     // SIMD); it pays while the batch is at most one wave per SIMD (the latency regime), beyond that
     // num_steps single-step launches are faster (measured at 524288 envs: 166 vs 197 us per step)
@@ -507,9 +516,7 @@ int rg_set_teams(rg_handle *h, const rg_team_params *tp) {
         (sc == RG_SCN_MATERIAL_TRANSPORT && !tp->torque))
         return fail(-64, "rg_set_teams: team_index, agent_step and the scenario's other tables (PredatorCapturePrey: sensing_radius, "
                          "capture_radius; MaterialTransport: torque) are required");
-    if (!rg::launch_team_step || !rg::launch_team_obs || !rg::launch_team_rollout || !rg::launch_team_step_ipm ||
-        !rg::launch_team_rollout_ipm || !rg::launch_team_index)
-        return fail(-100, "rg_set_teams: this build has no team kernels");
+    if (!group_family_built(rg::GROUP_TEAM) || !rg::launch_team_index) return fail(-100, "rg_set_teams: this build has no team kernels");
     if (tp->mode == RG_TEAM_FIXED) {   // the index of every env for the handle's life: env_offset + e mod C
         rg::KernelArgs a;
         if (int rc = fill_args(h, a)) return rc;
@@ -533,9 +540,7 @@ int rg_get_obs(rg_handle *h, float *obs) {
     if (reinterpret_cast<uintptr_t>(obs) & 15u) return fail(-26, "obs must be 16-byte aligned");
     a.io.obs = obs;
     RG_ON_DEVICE(h);
-    if (h->teams.n_sets) return launched(rg::launch_team_obs(a, h->teams, h->stream));
-    if (h->lidar.rays) return launched(rg::launch_lidar_obs(a, h->lidar, h->stream));
-    return launched(rg::launch_step(a, true, h->stream));
+    return launch_group_entry(h, a, rg::GROUP_OBS);
 }
 
 }  // extern "C"

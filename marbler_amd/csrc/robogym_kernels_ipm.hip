@@ -6,6 +6,8 @@
 
 namespace rg {
 
-hipError_t launch_step_ipm(const KernelArgs &a, int grid, hipStream_t stream) { return launch_ipm_group<false>(a, grid, stream); }
+hipError_t launch_step_ipm(const KernelArgs &a, const GroupSide &side, hipStream_t stream) {
+    return launch_group<PlainFamily, false, false, RG_QP_CVXOPT>(a, side, stream);
+}
 
 }  // namespace rg

@@ -4,6 +4,8 @@
 
 namespace rg {
 
-hipError_t launch_rollout(const KernelArgs &a, hipStream_t stream) { return launch_step_group<false, true>(a, stream); }
+hipError_t launch_rollout(const KernelArgs &a, const GroupSide &side, hipStream_t stream) {
+    return launch_group<PlainFamily, false, true, RG_QP_EXACT>(a, side, stream);
+}
 
 }  // namespace rg

@@ -3,6 +3,8 @@
 
 namespace rg {
 
-hipError_t launch_rollout_ipm(const KernelArgs &a, int grid, hipStream_t stream) { return launch_ipm_group<true>(a, grid, stream); }
+hipError_t launch_rollout_ipm(const KernelArgs &a, const GroupSide &side, hipStream_t stream) {
+    return launch_group<PlainFamily, false, true, RG_QP_CVXOPT>(a, side, stream);
+}
 
 }  // namespace rg

@@ -1,15 +1,15 @@
-// robogym_team.hip -- the team kernels (team_kernels.h) of the exact mode for one env step per launch (rg_step, plain and with
+// robogym_team.hip -- the team kernels (step_group.h) of the exact mode for one env step per launch (rg_step, plain and with
 // the gymma block) and for rg_get_obs, and the index writer of rg_reset / rg_set_teams.
-#include "team_kernels.h"
+#include "step_group.h"
 
 namespace rg {
 
-hipError_t launch_team_step(const KernelArgs &a, const rg_team_params &tp, hipStream_t stream) {
-    return launch_team_group<false, false, RG_QP_EXACT>(a, tp, stream);
+hipError_t launch_team_step(const KernelArgs &a, const GroupSide &side, hipStream_t stream) {
+    return launch_group<TeamFamily, false, false, RG_QP_EXACT>(a, side, stream);
 }
 
-hipError_t launch_team_obs(const KernelArgs &a, const rg_team_params &tp, hipStream_t stream) {
-    return launch_team_group<true, false, RG_QP_EXACT>(a, tp, stream);
+hipError_t launch_team_obs(const KernelArgs &a, const GroupSide &side, hipStream_t stream) {
+    return launch_group<TeamFamily, true, false, RG_QP_EXACT>(a, side, stream);
 }
 
 // One lane per env: the team index of the episode each (masked) env has just started -- rg_reset advanced reset_count, so that

@@ -1,6 +1,7 @@
 // step_group.h -- the fused env-step kernel for gfx950 (MI355X, CDNA4), lane-group mapping.
-// (Templates only; instantiated by robogym_kernels.hip for rg_step / rg_get_obs / rg_reset and by
-// robogym_rollout_group.hip for rg_rollout.)
+// (Templates only: the step, its kernels in three families -- plain, lidar, team pool -- and their one launch dispatcher.
+// Instantiated by robogym_kernels*.hip / robogym_rollout_group*.hip, robogym_lidar*.hip and robogym_team*.hip, one translation
+// unit per (family, solver mode, launch kind): kernel_args.h RG_GROUP_ENTRIES.)
 //
 // One launch = one env step for E envs: goal generation, U sim sub-iterations (controller with
 // the barrier-certificate QP every 15th, collision/boundary validation, Euler integration),
@@ -378,9 +379,9 @@ __device__ __forceinline__ void write_neighbour_obs(Lds<GW> &lds, int N, int Knb
 // count, single-step launch): the benchmark kernels carry none of it.
 // Sync: how the wave's lanes meet (device_common.h): WgSync in the step kernels (one-wave workgroups), WaveSync where the step
 // runs on one wave of a larger workgroup (policy_rollout.h): every barrier below sits under the wave's own control flow.
-// LIDAR: the range block of `lid` (lidar.h) goes after the scenario's own columns.  Its own instantiations (lidar_kernels.h).
+// LIDAR: the range block of `lid` (lidar.h) goes after the scenario's own columns.  Its own instantiations (lidar_step_kernel).
 // TEAM: the agents' capabilities come from set team_index[e] of the pool `tm` (team.h), and an episode that starts here draws
-// the env's next index.  Its own instantiations (team_kernels.h).
+// the env's next index.  Its own instantiations (team_step_kernel).
 // SPAN: an env owns a whole 16-lane DPP row (GW = 8): lanes 8..15 of the row (the "helper" half) run a bit-identical replica of
 // lanes 0..7 -- same loads, same code, same votes -- and take over part of the env's order-free work (the sparse and dense
 // collision pre-tests, whose result is a minimum over pairs and sub-steps); they make no global store.  Every DPP exchange and
@@ -1436,6 +1437,47 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     }
 }
 
+// ------------------------------------------------------------------ the step kernels: three families, one body
+// The step comes in three families of kernels: plain; with the lidar on (rg_set_lidar: the range block of lidar.h written at the
+// end of the observation phase); with a team pool (rg_set_teams: the agents' capabilities from set team_index[e] of team.h, and
+// the index of every episode the step starts).  Neither of the last two has a thread-per-env form: such a handle always runs
+// these.  A family is described by its argument block (the step's own KernelArgs, and the side block next to it that the other
+// kernels never see), by what it hands step_once, and by whether a rollout re-addresses the block every step.
+struct PlainFamily {
+    using Args = KernelArgs;
+    static constexpr bool LIDAR = false, TEAM = false, READDRESS = false;
+    static Args args(const KernelArgs &a, const GroupSide &) { return a; }
+    __device__ __forceinline__ static const KernelArgs &kernel_args(const Args &x) { return x; }
+    __device__ __forceinline__ static const rg_lidar_params *lidar(const Args &) { return nullptr; }
+    __device__ __forceinline__ static const rg_team_params *teams(const Args &) { return nullptr; }
+};
+struct LidarFamily {
+    using Args = LidarArgs;
+    static constexpr bool LIDAR = true, TEAM = false, READDRESS = true;
+    static Args args(const KernelArgs &a, const GroupSide &side) { return Args{a, *side.lidar}; }
+    __device__ __forceinline__ static const KernelArgs &kernel_args(const Args &x) { return x.k; }
+    __device__ __forceinline__ static const rg_lidar_params *lidar(const Args &x) { return &x.lid; }
+    __device__ __forceinline__ static const rg_team_params *teams(const Args &) { return nullptr; }
+};
+struct TeamFamily {
+    using Args = TeamArgs;
+    static constexpr bool LIDAR = false, TEAM = true, READDRESS = true;
+    static Args args(const KernelArgs &a, const GroupSide &side) { return Args{a, *side.teams}; }
+    __device__ __forceinline__ static const KernelArgs &kernel_args(const Args &x) { return x.k; }
+    __device__ __forceinline__ static const rg_lidar_params *lidar(const Args &) { return nullptr; }
+    __device__ __forceinline__ static const rg_team_params *teams(const Args &x) { return &x.tp; }
+};
+
+// The argument block of a rollout's next step.  READDRESS: through an opaque copy of the kernel-argument segment's address
+// (device_common.h kernarg_block).  Left loop-invariant, the compiler hoists the block's loads out of the step loop and holds
+// them across the whole step -- the lidar rollout of PredatorCapturePrey GW 4: 273 VGPRs + 17 AGPRs and 148 bytes of scratch,
+// against 169 and none.  The plain rollout keeps the block it was given (its code predates the finding and is left as it is).
+template <class F>
+__device__ __forceinline__ const typename F::Args &rollout_step_args(const typename F::Args &args) {
+    if constexpr (F::READDRESS) return *(const typename F::Args *)kernarg_block<typename F::Args>();
+    else return args;
+}
+
 // ROLLOUT = false: one env step per launch (rg_step, rg_get_obs).  ROLLOUT = true (rg_rollout): the
 // wave's envs advance num_steps times with no device-wide synchronisation between steps; state
 // round-trips through this CU's caches (workgroup-scope visibility after the barrier).  Separate
@@ -1443,43 +1485,56 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
 // 313 VGPRs) and would slow the single-step launch down.
 // QPM = RG_QP_CVXOPT: the certificate's QP by the interior-point iteration of ipm_qp.h.  Its own instantiations (generic agent
 // count): the launch is then dominated by that iteration (about ten times the rest of the step), and it needs one wave per SIMD.
-template <int SCN, int GW, bool OBS_ONLY, int NT, bool ROLLOUT, bool GYM, int QPM, bool SPAN>
-__device__ __forceinline__ void step_kernel_body(const KernelArgs &a) {
+// SPAN: one env per 16-lane row (step_once).
+template <class F, int SCN, int GW, bool OBS_ONLY, int NT, bool ROLLOUT, bool GYM, int QPM, bool SPAN = false>
+__device__ __forceinline__ void step_kernel_body(const typename F::Args &args) {
+    constexpr bool IPM = QPM == RG_QP_CVXOPT;
+    static_assert(!IPM || GW == 4 || GW == 8, "the interior-point mode admits n_agents <= 8");
+    static_assert(!IPM || !OBS_ONLY, "an observation-only launch runs no controller");
+    static_assert(!SPAN || (!ROLLOUT && !OBS_ONLY), "the 16-lane rows: the single-step launch");
     __shared__ Lds<GW> lds;
+    using Q = std::conditional_t<IPM, ipm::GroupLds<GW>, void>;
+    Q *qp_lds = nullptr;
+    if constexpr (IPM) {
+        __shared__ Q qp_block;   // records + one workspace per env (ipm_qp.h): these instantiations only
+        qp_lds = &qp_block;
+    }
+    const KernelArgs &a = F::kernel_args(args);
     const int N = NT > 0 ? NT : a.p.n_agents;
-    if constexpr (QPM == RG_QP_CVXOPT) {
-        static_assert(GW == 4 || GW == 8, "the interior-point mode admits n_agents <= 8");
-        __shared__ ipm::GroupLds<GW> qp_lds;   // records + one workspace per env (ipm_qp.h): these instantiations only
-        if constexpr (!ROLLOUT) {
-            step_once<SCN, GW, OBS_ONLY, NT, true, GYM, QPM>(a, lds, step_view(a, 0, N, a.p.obs_dim), &qp_lds);
-        } else {
-            for (int t = 0; t < a.num_steps; ++t) {
-                if (t) __syncthreads();
-                step_once<SCN, GW, OBS_ONLY, NT, false, false, QPM>(a, lds, step_view(a, t, N, a.p.obs_dim), &qp_lds);
-            }
-        }
-    } else if constexpr (SPAN) {
-        static_assert(!ROLLOUT && !OBS_ONLY, "the 16-lane rows: the single-step launch");
-        step_once<SCN, GW, false, NT, true, GYM, QPM, void, WgSync, false, false, true>(a, lds, step_view(a, 0, N, a.p.obs_dim));
-    } else if constexpr (!ROLLOUT) {
-        step_once<SCN, GW, OBS_ONLY, NT, true, GYM, QPM>(a, lds, step_view(a, 0, N, a.p.obs_dim), static_cast<void *>(nullptr));
+    if constexpr (!ROLLOUT) {
+        step_once<SCN, GW, OBS_ONLY, NT, true, GYM, QPM, Q, WgSync, F::LIDAR, F::TEAM, SPAN>(a, lds, step_view(a, 0, N, a.p.obs_dim), qp_lds,
+                                                                                           F::lidar(args), F::teams(args));
     } else {
         for (int t = 0; t < a.num_steps; ++t) {
             if (t) __syncthreads();
-            step_once<SCN, GW, OBS_ONLY, NT, false, false, QPM>(a, lds, step_view(a, t, N, a.p.obs_dim), static_cast<void *>(nullptr));
+            const typename F::Args &now = rollout_step_args<F>(args);
+            const KernelArgs &at = F::kernel_args(now);
+            step_once<SCN, GW, OBS_ONLY, NT, false, false, QPM, Q, WgSync, F::LIDAR, F::TEAM>(at, lds, step_view(at, t, N, at.p.obs_dim), qp_lds,
+                                                                                             F::lidar(now), F::teams(now));
         }
     }
 }
 
+// The __global__ templates: one per family.  Their names, template parameter lists and argument types are an interface (the
+// mangled names are matched by bench.py, the resource tests and the profile tools).
 template <int SCN, int GW, bool OBS_ONLY, int NT, bool ROLLOUT, bool GYM = false, int QPM = 0>
 __global__ __launch_bounds__(WAVE) void step_kernel(const KernelArgs a) {
-    step_kernel_body<SCN, GW, OBS_ONLY, NT, ROLLOUT, GYM, QPM, false>(a);
+    step_kernel_body<PlainFamily, SCN, GW, OBS_ONLY, NT, ROLLOUT, GYM, QPM>(a);
 }
 // ROW = 16: one env per 16-lane row (step_once SPAN), 4 envs per wave; the single-step exact-mode launch with GW = 8 only
 // (step_kernel<SCN, 8, false, NT, false, 16>).  A template of its own, so that every existing instantiation keeps its name.
 template <int SCN, int GW, bool OBS_ONLY, int NT, bool ROLLOUT, int ROW, std::enable_if_t<ROW == 16, int> = 0>
 __global__ __launch_bounds__(WAVE) void step_kernel(const KernelArgs a) {
-    step_kernel_body<SCN, GW, OBS_ONLY, NT, ROLLOUT, false, 0, true>(a);
+    step_kernel_body<PlainFamily, SCN, GW, OBS_ONLY, NT, ROLLOUT, false, 0, true>(a);
+}
+// generic agent count (NT = 0) throughout
+template <int SCN, int GW, bool OBS_ONLY, bool ROLLOUT, bool GYM, int QPM>
+__global__ __launch_bounds__(WAVE) void lidar_step_kernel(const LidarArgs la) {
+    step_kernel_body<LidarFamily, SCN, GW, OBS_ONLY, 0, ROLLOUT, GYM, QPM>(la);
+}
+template <int SCN, int GW, bool OBS_ONLY, int NT, bool ROLLOUT, bool GYM, int QPM>
+__global__ __launch_bounds__(WAVE) void team_step_kernel(const TeamArgs ta) {
+    step_kernel_body<TeamFamily, SCN, GW, OBS_ONLY, NT, ROLLOUT, GYM, QPM>(ta);
 }
 
 template <int SCN, int GW>
@@ -1516,115 +1571,95 @@ namespace rg {
 
 inline int group_width(int N) { return N <= 4 ? 4 : N <= 8 ? 8 : 16; }
 
-template <int SCN, bool OBS_ONLY, bool ROLLOUT>
-static hipError_t launch_step_scn(const KernelArgs &a_in, hipStream_t stream) {
-    const int gw = group_width(a_in.p.n_agents);
-    // A batch that leaves SIMDs idle with full wavefronts runs with partly filled ones instead (more
-    // waves, each carrying fewer envs, as long as there is at most one wave per SIMD: 1024): a wave's
-    // time is the maximum over its envs (QP sweeps, replays, resets), and the idle SIMDs are free.
-    KernelArgs a = a_in;
+// A batch that leaves SIMDs idle with full wavefronts runs with partly filled ones instead (more
+// waves, each carrying fewer envs, as long as there is at most one wave per SIMD: 1024): a wave's
+// time is the maximum over its envs (QP sweeps, replays, resets), and the idle SIMDs are free.
+// (A stamps build keeps full waves: its eight slots are the wave's first eight envs.)
+struct WaveFill {
+    int epw, grid;   // env slots used per wave, waves
+};
+inline WaveFill wave_fill(int E, int gw) {
     int epw = WAVE / gw;
-    if constexpr (!kStampsBuild) {   // (a stamps build keeps full waves: its eight slots are the wave's first eight envs)
-        while (epw >= 2 && (a.E + epw / 2 - 1) / (epw / 2) <= RG_MAX_WAVES) epw /= 2;
-        a.envs_per_wave = epw;
+    if constexpr (!kStampsBuild) {
+        while (epw >= 2 && (E + epw / 2 - 1) / (epw / 2) <= RG_MAX_WAVES) epw /= 2;
     }
-    const int grid = (a.E + epw - 1) / epw;
-    if constexpr (!OBS_ONLY) {
-        // the interior-point mode's kernels live in their own translation units (robogym_kernels_ipm.hip, robogym_rollout_group_ipm.hip)
-        if (a.p.qp_mode == RG_QP_CVXOPT) return ROLLOUT ? launch_rollout_ipm(a, grid, stream) : launch_step_ipm(a, grid, stream);
-    }
-    if constexpr (!OBS_ONLY && !ROLLOUT) {
-        if (a.io.elapsed) {  // gymma block: its own instantiations (generic agent count)
-            if (gw == 4) hipLaunchKernelGGL((step_kernel<SCN, 4, false, 0, false, true>), dim3(grid), dim3(WAVE), 0, stream, a);
-            else if (gw == 16) hipLaunchKernelGGL((step_kernel<SCN, 16, false, 0, false, true>), dim3(grid), dim3(WAVE), 0, stream, a);
-            else hipLaunchKernelGGL((step_kernel<SCN, 8, false, 0, false, true>), dim3(grid), dim3(WAVE), 0, stream, a);
-            return hipGetLastError();
-        }
-    }
-    if constexpr (!OBS_ONLY && !ROLLOUT && !kStampsBuild) {
-        // at most 4 envs per wave (batches up to 4096 envs): each env on a 16-lane row, the upper half a replica that takes over
-        // part of the order-free work (step_once SPAN).  A negative envs_per_wave on entry (rg_step under RG_STEP_SPAN=0, rg_create)
-        // keeps 8-lane groups.
-        if (a_in.envs_per_wave >= 0 && gw == 8 && epw <= 4) {
-            switch (a.p.n_agents) {
-                case 5: hipLaunchKernelGGL((step_kernel<SCN, 8, false, 5, false, 16>), dim3(grid), dim3(WAVE), 0, stream, a); break;
-                case 6: hipLaunchKernelGGL((step_kernel<SCN, 8, false, 6, false, 16>), dim3(grid), dim3(WAVE), 0, stream, a); break;
-                case 7: hipLaunchKernelGGL((step_kernel<SCN, 8, false, 7, false, 16>), dim3(grid), dim3(WAVE), 0, stream, a); break;
-                default: hipLaunchKernelGGL((step_kernel<SCN, 8, false, 8, false, 16>), dim3(grid), dim3(WAVE), 0, stream, a); break;
+    return {epw, (E + epw - 1) / epw};
+}
+
+// one launch of family F's __global__ template (ROWS: the plain family's 16-lane-row overload)
+template <class F, int SCN, int GW, bool OBS_ONLY, int NT, bool ROLLOUT, bool GYM, int QPM, bool ROWS = false>
+static void launch_kernel(const typename F::Args &args, int grid, hipStream_t stream) {
+    if constexpr (ROWS) hipLaunchKernelGGL((step_kernel<SCN, GW, OBS_ONLY, NT, ROLLOUT, 16>), dim3(grid), dim3(WAVE), 0, stream, args);
+    else if constexpr (F::LIDAR) hipLaunchKernelGGL((lidar_step_kernel<SCN, GW, OBS_ONLY, ROLLOUT, GYM, QPM>), dim3(grid), dim3(WAVE), 0, stream, args);
+    else if constexpr (F::TEAM) hipLaunchKernelGGL((team_step_kernel<SCN, GW, OBS_ONLY, NT, ROLLOUT, GYM, QPM>), dim3(grid), dim3(WAVE), 0, stream, args);
+    else hipLaunchKernelGGL((step_kernel<SCN, GW, OBS_ONLY, NT, ROLLOUT, GYM, QPM>), dim3(grid), dim3(WAVE), 0, stream, args);
+}
+
+// The kernel of (family, scenario, launch kind, mode) at group width gw.  Generic agent count (NT = 0), except GW 8 of the exact
+// mode's step and rollout in the plain and team families: bodies specialised for the agent count (NT = N, 5..8).  The gymma
+// block's, the observation-only, the interior-point and every lidar kernel are generic.  rows: the 16-lane-row kernel instead.
+template <class F, int SCN, bool OBS_ONLY, bool ROLLOUT, bool GYM, int QPM>
+static hipError_t launch_gw(const typename F::Args &args, int gw, int n, bool rows, int grid, hipStream_t stream) {
+    constexpr bool EXACT = QPM == RG_QP_EXACT;
+    constexpr bool BY_N = EXACT && !OBS_ONLY && !GYM && !F::LIDAR;
+    constexpr bool ROWS = BY_N && !ROLLOUT && !F::TEAM && !kStampsBuild;
+    if (gw == 4) {
+        launch_kernel<F, SCN, 4, OBS_ONLY, 0, ROLLOUT, GYM, QPM>(args, grid, stream);
+    } else if constexpr (SCN == RG_SCN_ARCTIC_TRANSPORT) {
+        return hipErrorInvalidValue;   // (rg_create admits exactly 4 agents)
+    } else if (gw == 16) {
+        if constexpr (EXACT) launch_kernel<F, SCN, 16, OBS_ONLY, 0, ROLLOUT, GYM, QPM>(args, grid, stream);
+        else return hipErrorInvalidValue;   // (rg_create admits n_agents <= 8 in the interior-point mode)
+    } else if constexpr (BY_N) {
+        auto by_n = [&](auto rows_c) {
+            constexpr bool R = decltype(rows_c)::value;
+            switch (n) {
+                case 5: launch_kernel<F, SCN, 8, false, 5, ROLLOUT, false, QPM, R>(args, grid, stream); break;
+                case 6: launch_kernel<F, SCN, 8, false, 6, ROLLOUT, false, QPM, R>(args, grid, stream); break;
+                case 7: launch_kernel<F, SCN, 8, false, 7, ROLLOUT, false, QPM, R>(args, grid, stream); break;
+                default: launch_kernel<F, SCN, 8, false, 8, ROLLOUT, false, QPM, R>(args, grid, stream); break;
             }
-            return hipGetLastError();
-        }
+        };
+        if (ROWS && rows) by_n(std::integral_constant<bool, ROWS>());
+        else by_n(std::false_type());
+    } else {
+        launch_kernel<F, SCN, 8, OBS_ONLY, 0, ROLLOUT, GYM, QPM>(args, grid, stream);
     }
-    if (gw == 4) hipLaunchKernelGGL((step_kernel<SCN, 4, OBS_ONLY, 0, ROLLOUT>), dim3(grid), dim3(WAVE), 0, stream, a);
-    else if (gw == 16) hipLaunchKernelGGL((step_kernel<SCN, 16, OBS_ONLY, 0, ROLLOUT>), dim3(grid), dim3(WAVE), 0, stream, a);
-    else if constexpr (OBS_ONLY) hipLaunchKernelGGL((step_kernel<SCN, 8, true, 0, false>), dim3(grid), dim3(WAVE), 0, stream, a);
-    else if (a.p.n_agents == 5) hipLaunchKernelGGL((step_kernel<SCN, 8, false, 5, ROLLOUT>), dim3(grid), dim3(WAVE), 0, stream, a);
-    else if (a.p.n_agents == 6) hipLaunchKernelGGL((step_kernel<SCN, 8, false, 6, ROLLOUT>), dim3(grid), dim3(WAVE), 0, stream, a);
-    else if (a.p.n_agents == 7) hipLaunchKernelGGL((step_kernel<SCN, 8, false, 7, ROLLOUT>), dim3(grid), dim3(WAVE), 0, stream, a);
-    else hipLaunchKernelGGL((step_kernel<SCN, 8, false, 8, ROLLOUT>), dim3(grid), dim3(WAVE), 0, stream, a);
     return hipGetLastError();
 }
 
-// the lane-group step for every scenario; OBS_ONLY exists for ROLLOUT = false only
-template <bool OBS_ONLY, bool ROLLOUT>
-static hipError_t launch_step_group(const KernelArgs &a, hipStream_t stream) {
-    static_assert(!(OBS_ONLY && ROLLOUT), "rg_get_obs is a single launch");
-    switch (a.p.scenario) {
-        case RG_SCN_PREDATOR_CAPTURE_PREY:
-            return launch_step_scn<RG_SCN_PREDATOR_CAPTURE_PREY, OBS_ONLY, ROLLOUT>(a, stream);
-        case RG_SCN_WAREHOUSE:
-            return launch_step_scn<RG_SCN_WAREHOUSE, OBS_ONLY, ROLLOUT>(a, stream);
-        case RG_SCN_MATERIAL_TRANSPORT:
-            return launch_step_scn<RG_SCN_MATERIAL_TRANSPORT, OBS_ONLY, ROLLOUT>(a, stream);
-        case RG_SCN_SIMPLE:
-            return launch_step_scn<RG_SCN_SIMPLE, OBS_ONLY, ROLLOUT>(a, stream);
-        case RG_SCN_ARCTIC_TRANSPORT:
-            if constexpr (!OBS_ONLY) {
-                if (a.p.qp_mode == RG_QP_CVXOPT)
-                    return ROLLOUT ? launch_rollout_ipm(a, (a.E + 15) / 16, stream) : launch_step_ipm(a, (a.E + 15) / 16, stream);
+// The lane-group launch of family F: every translation unit's entry is one instantiation of this (OBS_ONLY exists for the single
+// launch of the exact mode only: an observation runs no controller).
+template <class F, bool OBS_ONLY, bool ROLLOUT, int QPM>
+static hipError_t launch_group(const KernelArgs &a_in, const GroupSide &side, hipStream_t stream) {
+    static_assert(!OBS_ONLY || (!ROLLOUT && QPM == RG_QP_EXACT), "rg_get_obs is a single launch of the exact mode's kernel");
+    return for_scenario(a_in.p.scenario, [&](auto scn) -> hipError_t {
+        constexpr int SCN = decltype(scn)::value;
+        constexpr bool ARCTIC = SCN == RG_SCN_ARCTIC_TRANSPORT;
+        if constexpr (ARCTIC && F::TEAM) {
+            return hipErrorInvalidValue;   // refused by rg_set_teams: the scenario fixes its agent types
+        } else {
+            KernelArgs a = a_in;
+            // ArcticTransport: four agents, full waves, envs_per_wave as it came
+            int gw = 4;
+            WaveFill wf = {WAVE / 4, (a.E + 15) / 16};
+            if constexpr (!ARCTIC) {
+                gw = group_width(a.p.n_agents);
+                wf = wave_fill(a.E, gw);
+                if constexpr (!kStampsBuild) a.envs_per_wave = wf.epw;
             }
+            const typename F::Args args = F::args(a, side);
             if constexpr (!OBS_ONLY && !ROLLOUT) {
-                if (a.io.elapsed) {
-                    hipLaunchKernelGGL((step_kernel<RG_SCN_ARCTIC_TRANSPORT, 4, false, 0, false, true>), dim3((a.E + 15) / 16),
-                                       dim3(WAVE), 0, stream, a);
-                    return hipGetLastError();
-                }
+                if (a.io.elapsed)   // gymma block: its own instantiations
+                    return launch_gw<F, SCN, false, false, true, QPM>(args, gw, a.p.n_agents, false, wf.grid, stream);
             }
-            hipLaunchKernelGGL((step_kernel<RG_SCN_ARCTIC_TRANSPORT, 4, OBS_ONLY, 0, ROLLOUT>), dim3((a.E + 15) / 16), dim3(WAVE), 0,
-                               stream, a);
-            return hipGetLastError();
-        default:
-            return hipErrorInvalidValue;
-    }
-}
-
-// QPM = RG_QP_CVXOPT: launch dispatch of the interior-point mode's kernels (rg_create admits n_agents <= 8 in this mode).  Called
-// from the translation units that instantiate them, compiled with their own scheduler flag (build.py FILE_FLAGS).
-template <int SCN, bool ROLLOUT>
-static hipError_t launch_ipm_scn(const KernelArgs &a, int grid, hipStream_t stream) {
-    constexpr int Q = RG_QP_CVXOPT;
-    const int gw = SCN == RG_SCN_ARCTIC_TRANSPORT ? 4 : group_width(a.p.n_agents);
-    if constexpr (!ROLLOUT) {
-        if (a.io.elapsed) {   // gymma block
-            if (gw == 4) hipLaunchKernelGGL((step_kernel<SCN, 4, false, 0, false, true, Q>), dim3(grid), dim3(WAVE), 0, stream, a);
-            else if constexpr (SCN != RG_SCN_ARCTIC_TRANSPORT) hipLaunchKernelGGL((step_kernel<SCN, 8, false, 0, false, true, Q>), dim3(grid), dim3(WAVE), 0, stream, a);
-            return hipGetLastError();
+            // at most 4 envs per wave (batches up to 4096 envs): each env on a 16-lane row, the upper half a replica that takes
+            // over part of the order-free work (step_once SPAN; the plain family's exact single step at GW 8).  A negative
+            // envs_per_wave on entry (rg_step under RG_STEP_SPAN=0, rg_create) keeps 8-lane groups.
+            const bool rows = a_in.envs_per_wave >= 0 && wf.epw <= 4;
+            return launch_gw<F, SCN, OBS_ONLY, ROLLOUT, false, QPM>(args, gw, a.p.n_agents, rows, wf.grid, stream);
         }
-    }
-    if (gw == 4) hipLaunchKernelGGL((step_kernel<SCN, 4, false, 0, ROLLOUT, false, Q>), dim3(grid), dim3(WAVE), 0, stream, a);
-    else if constexpr (SCN != RG_SCN_ARCTIC_TRANSPORT) hipLaunchKernelGGL((step_kernel<SCN, 8, false, 0, ROLLOUT, false, Q>), dim3(grid), dim3(WAVE), 0, stream, a);
-    return hipGetLastError();
-}
-template <bool ROLLOUT>
-static hipError_t launch_ipm_group(const KernelArgs &a, int grid, hipStream_t stream) {
-    switch (a.p.scenario) {
-        case RG_SCN_PREDATOR_CAPTURE_PREY: return launch_ipm_scn<RG_SCN_PREDATOR_CAPTURE_PREY, ROLLOUT>(a, grid, stream);
-        case RG_SCN_WAREHOUSE: return launch_ipm_scn<RG_SCN_WAREHOUSE, ROLLOUT>(a, grid, stream);
-        case RG_SCN_MATERIAL_TRANSPORT: return launch_ipm_scn<RG_SCN_MATERIAL_TRANSPORT, ROLLOUT>(a, grid, stream);
-        case RG_SCN_SIMPLE: return launch_ipm_scn<RG_SCN_SIMPLE, ROLLOUT>(a, grid, stream);
-        case RG_SCN_ARCTIC_TRANSPORT: return launch_ipm_scn<RG_SCN_ARCTIC_TRANSPORT, ROLLOUT>(a, grid, stream);
-        default: return hipErrorInvalidValue;
-    }
+    });
 }
 
 }  // namespace rg

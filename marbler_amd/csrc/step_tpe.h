@@ -1157,26 +1157,19 @@ static hipError_t launch_scn(const KernelArgs &a, hipStream_t stream) {
 
 template <bool ROLLOUT>
 static hipError_t launch_tpe(const KernelArgs &a, hipStream_t stream) {
-    switch (a.p.scenario) {
-        case RG_SCN_PREDATOR_CAPTURE_PREY:
-            return tpe::launch_scn<RG_SCN_PREDATOR_CAPTURE_PREY, ROLLOUT>(a, stream);
-        case RG_SCN_WAREHOUSE:
-            return tpe::launch_scn<RG_SCN_WAREHOUSE, ROLLOUT>(a, stream);
-        case RG_SCN_MATERIAL_TRANSPORT:
-            return tpe::launch_scn<RG_SCN_MATERIAL_TRANSPORT, ROLLOUT>(a, stream);
-        case RG_SCN_SIMPLE:
-            return tpe::launch_scn<RG_SCN_SIMPLE, ROLLOUT>(a, stream);
-        case RG_SCN_ARCTIC_TRANSPORT: {
+    return for_scenario(a.p.scenario, [&](auto scn) -> hipError_t {
+        constexpr int SCN = decltype(scn)::value;
+        if constexpr (SCN != RG_SCN_ARCTIC_TRANSPORT) {
+            return tpe::launch_scn<SCN, ROLLOUT>(a, stream);
+        } else {
             const int grid = (a.E + WAVE - 1) / WAVE;
             if (a.p.qp_mode == RG_QP_CVXOPT)
-                hipLaunchKernelGGL((tpe::step_kernel<RG_SCN_ARCTIC_TRANSPORT, 4, ROLLOUT, RG_QP_CVXOPT>), dim3(grid), dim3(WAVE), 0, stream, a);
+                hipLaunchKernelGGL((tpe::step_kernel<SCN, 4, ROLLOUT, RG_QP_CVXOPT>), dim3(grid), dim3(WAVE), 0, stream, a);
             else
-                hipLaunchKernelGGL((tpe::step_kernel<RG_SCN_ARCTIC_TRANSPORT, 4, ROLLOUT>), dim3(grid), dim3(WAVE), 0, stream, a);
+                hipLaunchKernelGGL((tpe::step_kernel<SCN, 4, ROLLOUT>), dim3(grid), dim3(WAVE), 0, stream, a);
             return hipGetLastError();
         }
-        default:
-            return hipErrorInvalidValue;
-    }
+    });
 }
 
 }  // namespace rg
