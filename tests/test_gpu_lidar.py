@@ -55,7 +55,11 @@ def _check_against_twin(obs, poses, env, L=1.0, max_degenerate=1e-3, exact_zero=
 @pytest.mark.parametrize("R", [4, 16, 32])
 @pytest.mark.parametrize("scenario", sorted(SCN_OV))
 def test_ranges_match_the_float64_twin(scenario, R):
-    env = _env(scenario, 256, R, seed=3, auto_reset=False)
+    ranges_vs_twin(scenario, R)
+
+
+def ranges_vs_twin(scenario, R, E=256, T=4, ov=None):
+    env = _env(scenario, E, R, ov, seed=3, auto_reset=False)
     assert env.D == env.lidar.offset + R and env.step_kernel == "group"
     env.reset()
     # random headings: the reset's are axis-aligned, and robots on the grid row y = 0 then sit exactly L = 1 m from the side
@@ -64,13 +68,13 @@ def test_ranges_match_the_float64_twin(scenario, R):
     g = torch.Generator(device="cpu").manual_seed(R)
     sd["poses"][:, 2, :] = (torch.rand(env.E, env.N, generator=g) * 2.0 - 1.0) * 3.14159
     env.load_state_dict(sd)
-    acts = _actions(env, 4, seed=11)
+    acts = _actions(env, T, seed=11)
     compared = 0
-    for t in range(4):
+    for t in range(T):
         obs, _, _, _ = env.step(acts[t])
         torch.cuda.synchronize()
         compared += _check_against_twin(obs, env.poses, env)
-    assert compared > 0.99 * 4 * env.E * env.N * R
+    assert compared > 0.99 * T * env.E * env.N * R
 
 
 def test_hand_placed_states():
@@ -134,7 +138,12 @@ def _run_pair(scenario, ov, R, solver, T=25, E=96):
 @pytest.mark.parametrize("scenario,ov,solver", [(s, o, m) for s, o in PAIRS for m in ("exact", "cvxopt")
                                                  if m == "exact" or int(o["n_agents"]) <= 8])   # (cvxopt: n_agents <= 8)
 def test_lidar_changes_nothing_else(scenario, ov, solver):
-    (off, o0, s_off, sd_off), (on, n0, s_on, sd_on) = _run_pair(scenario, ov, 16, solver)
+    lidar_changes_nothing_else(scenario, ov, solver)
+
+
+def lidar_changes_nothing_else(scenario, ov, solver, **run):
+    """run: _run_pair's T and E."""
+    (off, o0, s_off, sd_off), (on, n0, s_on, sd_on) = _run_pair(scenario, ov, 16, solver, **run)
     own = off.D
     assert on.D == own + 16
     assert torch.equal(o0, n0[..., :own]) and not n0.any()

@@ -127,8 +127,13 @@ def _load_oracle(orc, env, state, t):
 
 @pytest.mark.parametrize("scenario,ov,solver", ORACLE_CASES)
 def test_mixed_teams_are_bit_exact_against_the_float32_oracle(scenario, ov, solver, oracle_lib):
-    E, T = 256, 80
-    ov = dict(ov, barrier_solver=solver, max_episode_steps=15)
+    mixed_teams_vs_oracle(scenario, ov, solver, oracle_lib, 256, 80, 15)
+
+
+def mixed_teams_vs_oracle(scenario, ov, solver, oracle_lib, E, T, episode_steps, before_first_step=None, threads=1):
+    """Four oracles, one per set of `_pool4`, each loaded with the GPU's state before every step; env e is held to the oracle of
+    its own set.  before_first_step(env): called after the reset, for what a caller asserts about the draw.  threads: the oracles'."""
+    ov = dict(ov, barrier_solver=solver, max_episode_steps=episode_steps)
     N = int(dict(SCN_OV[scenario], **ov).get("n_agents", 4))
     env = _env(scenario, E, ov, teams=_pool4(scenario, N), seed=11, auto_reset=False, collect_qp_stats=True)
     cfg = dict(env.cfg)
@@ -136,6 +141,8 @@ def test_mixed_teams_are_bit_exact_against_the_float32_oracle(scenario, ov, solv
     cfg.pop("team_sampling")
     orcs = [oracle_lib.OracleVecEnv(scenario, cfg, E, dtype=np.float32) for _ in range(4)]
     env.reset()
+    if before_first_step is not None:
+        before_first_step(env)
     acts = _actions(env, T, seed=3).cpu().numpy()
     changes, seen = 0, set()
     for step in range(T):
@@ -153,7 +160,7 @@ def test_mixed_teams_are_bit_exact_against_the_float32_oracle(scenario, ov, solv
             rows = np.nonzero(team == t)[0]
             if rows.size == 0:
                 continue
-            o_obs, o_rew, o_done, o_info = orcs[t].step(acts[step])
+            o_obs, o_rew, o_done, o_info = orcs[t].step(acts[step], threads=threads)
             msg = (step, t)
             assert np.array_equal(g["obs"][rows].view(np.uint32), o_obs[rows].view(np.uint32)), msg
             assert np.array_equal(g["reward"][rows].view(np.uint32), o_rew[rows].view(np.uint32)), msg
@@ -170,6 +177,7 @@ def test_mixed_teams_are_bit_exact_against_the_float32_oracle(scenario, ov, solv
             env.reset(mask=done)
             changes += int((env.team_index != before).sum())
     assert seen == {0, 1, 2, 3} and changes > 0
+    env.close()
 
 
 # ---------------------------------------------------------------- 3. the draw

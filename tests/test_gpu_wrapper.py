@@ -223,10 +223,14 @@ def test_fused_time_limit_equals_the_composed_gymma_step(kernel, key, ov, n_act,
     """gym's TimeLimit and the gymma reductions inside the step launch (rg_step_io's gymma block) against the same
     contract composed from torch ops around the plain step: rewards, terminated / truncated flags, the observations a
     consumer sees next, the episode statistics and the env state, step after step through truncations and resets."""
+    monkeypatch.setenv("RG_STEP_KERNEL", kernel)
+    fused_time_limit_vs_composed(key, ov, n_act, limit, 256, 90)
+
+
+def fused_time_limit_vs_composed(key, ov, n_act, limit, E, steps):
+    """(RG_STEP_KERNEL is the caller's business.)"""
     import torch
     from marbler_amd.gymma import GymmaVecEnv
-    monkeypatch.setenv("RG_STEP_KERNEL", kernel)
-    E = 256
     a = GymmaVecEnv(key, E, time_limit=limit, overrides=ov, seed=5, fused=True)
     b = GymmaVecEnv(key, E, time_limit=limit, overrides=ov, seed=5, fused=False)
     assert a.env.time_limit == limit and b.env.time_limit == 0
@@ -235,7 +239,7 @@ def test_fused_time_limit_equals_the_composed_gymma_step(kernel, key, ov, n_act,
     g = torch.Generator(device=a.env.device)
     g.manual_seed(3)
     n_trunc = n_done = 0
-    for t in range(90):
+    for t in range(steps):
         act = torch.randint(0, n_act, (E, a.n_agents), generator=g, device=a.env.device, dtype=torch.int32)
         ra, ta, ia = a.step(act)
         rb, tb, ib = b.step(act)
