@@ -302,33 +302,46 @@ __device__ __forceinline__ int controller(const rg_scenario_params &p, const Con
 // controller -- the partners need not be the XOR partners: agent a visits (a + r) mod N, r = 1..N-1.
 // With the agent count a compile-time constant (NT) that is N-1 slots and (N-1)(N-2)/2 comparisons
 // instead of GW-1 and (GW-1)(GW-2)/2 (N = 5 in groups of 8: 4 and 6 instead of 7 and 21).
-template <int GW, int OD, int NT>
+// SPAN (16-lane rows; `lane_ok` then covers both halves of the row, and `gbase` is the row's first lane): the M partner slots
+// are split between the halves -- the group half owns r < S = (M + 1) / 2, the replica the rest (with M odd its last slot is
+// absent).  Each half reads and keys its own partners, fetches the other half's keys across the row (row_ror:8, one move per
+// word), ranks its own slots against all M keys and stores only its own slots' rows: the replica stores into the agent's obs_row.
+// A slot's rank is the number of keys below its own, whichever half holds them, so every row lands where the one-half form puts it.
+template <int GW, int OD, int NT, bool SPAN = false>
 __device__ __forceinline__ void write_neighbour_obs(Lds<GW> &lds, int N, int Knb, int ag, int gbase, bool lane_ok,
                                                     float x, float y, float *obs_row) {
     constexpr int M = NT > 0 ? NT - 1 : GW - 1;  // partner slots
+    constexpr int S = SPAN ? (M + 1) / 2 : M;    // ... of this lane: slots r0 .. r0 + S - 1 (SPAN: r0 = S in the replica)
+    const int r0 = SPAN && (threadIdx.x & GW) != 0 ? S : 0;
     // 64-bit sort keys: (bits of the squared distance, partner index) -- non-negative floats order
     // like their bit patterns, so one unsigned 64-bit compare is the (distance, index) lexicographic
     // test.  Absent partners get keys above every real one.
-    unsigned long long key[M > 0 ? M : 1];
-    bool ok[M > 0 ? M : 1];
-    int rank[M > 0 ? M : 1], who[M > 0 ? M : 1];
-    static_for<0, M>([&](auto RR) {
-        constexpr int r = decltype(RR)::value;
+    unsigned long long key[S > 0 ? S : 1], okey[S > 0 ? S : 1];  // okey (SPAN): the other half's keys
+    bool ok[S > 0 ? S : 1];
+    int rank[S > 0 ? S : 1], who[S > 0 ? S : 1];
+    static_for<0, S>([&](auto RR) {
+        constexpr int l = decltype(RR)::value;
+        const int r = r0 + l;
         int j = ag + r + 1;
         j = j >= N ? j - N : j;
-        j = j & (GW - 1);  // idle lanes (ag >= N) stay inside the group's rows
-        who[r] = j;
+        j = j & (GW - 1);  // idle lanes (ag >= N) and the replica's absent slot stay inside the group's rows
+        who[l] = j;
         const float2 pxy = *reinterpret_cast<const float2 *>(&lds.own[gbase + j][0]);  // partner's (x, y)
         const float dx = pxy.x - x, dy = pxy.y - y;
         const float d2 = dx * dx + dy * dy;
-        ok[r] = lane_ok & (r + 1 < N);
-        const unsigned int hi = ok[r] ? __builtin_bit_cast(unsigned int, d2) : 0xFFFFFFFFu;
-        key[r] = (static_cast<unsigned long long>(hi) << 32) | static_cast<unsigned int>(j);
-        rank[r] = M - 1 - r;  // pairs in which this slot is the first element; each lost comparison adds one below
+        ok[l] = lane_ok & (r + 1 < N);
+        if constexpr (SPAN) ok[l] &= r < M;
+        const unsigned int hi = ok[l] ? __builtin_bit_cast(unsigned int, d2) : 0xFFFFFFFFu;
+        key[l] = (static_cast<unsigned long long>(hi) << 32) | static_cast<unsigned int>(j);
+        if constexpr (SPAN) {  // both words by a move: recomputing j from ag and the other half's r costs three instructions
+            const unsigned int ohi = static_cast<unsigned int>(xor_lane_i<8>(static_cast<int>(hi)));
+            okey[l] = (static_cast<unsigned long long>(ohi) << 32) | static_cast<unsigned int>(xor_lane_i<8>(j));
+        }
+        rank[l] = S - 1 - l;  // own pairs in which this slot is the first element; each lost comparison adds one below
     });
     const bool all_others = Knb >= N - 1;
-    // rank of a partner = number of partners ahead of it: one comparison per unordered pair (q < k)
-    static_for<1, M>([&](auto KK) {
+    // rank of a partner = number of partners ahead of it: one comparison per unordered pair (q < k) of this lane's slots
+    static_for<1, S>([&](auto KK) {
         constexpr int k = decltype(KK)::value;
         static_for<0, k>([&](auto QQ) {
             constexpr int q = decltype(QQ)::value;
@@ -337,9 +350,15 @@ __device__ __forceinline__ void write_neighbour_obs(Lds<GW> &lds, int N, int Knb
             rank[q] -= q_first;
         });
     });
+    if constexpr (SPAN) {  // ... and the other half's slots ahead of each of mine
+        static_for<0, S>([&](auto LL) {
+            constexpr int l = decltype(LL)::value;
+            static_for<0, S>([&](auto QQ) { rank[l] += okey[decltype(QQ)::value] < key[l] ? 1 : 0; });
+        });
+    }
     // the rows first (independent LDS reads in flight together), then the predicated stores
-    float row[M > 0 ? M : 1][OD];
-    static_for<0, M>([&](auto RR) {
+    float row[S > 0 ? S : 1][OD];
+    static_for<0, S>([&](auto RR) {
         constexpr int r = decltype(RR)::value;
         const float *src = &lds.own[gbase + who[r]][0];
         if constexpr (OD == 4) {
@@ -353,7 +372,7 @@ __device__ __forceinline__ void write_neighbour_obs(Lds<GW> &lds, int N, int Knb
             for (int c = 0; c < OD; ++c) row[r][c] = src[c];
         }
     });
-    static_for<0, M>([&](auto RR) {
+    static_for<0, S>([&](auto RR) {
         constexpr int r = decltype(RR)::value;
         const int j = who[r];
         const int slot = all_others ? (j < ag ? j : j - 1) : rank[r];
@@ -384,7 +403,9 @@ __device__ __forceinline__ void write_neighbour_obs(Lds<GW> &lds, int N, int Knb
 // the env's next index.  Its own instantiations (team_step_kernel).
 // SPAN: an env owns a whole 16-lane DPP row (GW = 8): lanes 8..15 of the row (the "helper" half) run a bit-identical replica of
 // lanes 0..7 -- same loads, same code, same votes -- and take over part of the env's order-free work (the sparse and dense
-// collision pre-tests, whose result is a minimum over pairs and sub-steps); they make no global store.  Every DPP exchange and
+// collision pre-tests, whose result is a minimum over pairs and sub-steps; in the epilogue prey 4..7 of PredatorCapturePrey's prey
+// pass and the upper half of the neighbour slots).  The replica makes ONE kind of global store: the neighbour rows of the slots it
+// owns, into its agent's own obs_row (write_neighbour_obs); every other store is the group half's.  Every DPP exchange and
 // reduction at GW = 8 stays inside its 8-lane half (quad permutes, row_half_mirror), so no value mixes the two halves except
 // where a result is brought across on purpose (row_ror:8, xor_lane_i<8>).
 template <int SCN, int GW, bool OBS_ONLY, int NT, bool AHEAD, bool GYM, int QPM = 0, typename QpLds = void, typename Sync = WgSync,
@@ -445,6 +466,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     const bool env_ok = (g < epw) & (e < q_E);
     const bool lane_ok = env_ok && ag < N;
     const bool env_st = env_ok & !helper, lane_st = lane_ok & !helper;   // the lanes that store
+    const bool lane_nb = SPAN ? lane_ok : lane_st;                       // ... the neighbour rows (write_neighbour_obs)
     const size_t eN = static_cast<size_t>(e) * N;
 
     // ---- loads, ALL issued before anything waits for one of them (coalesced: a wave covers EPW consecutive
@@ -560,8 +582,14 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         if (P <= 8) {
             if (env_ok) {
                 const float2 *src = reinterpret_cast<const float2 *>(q_prey) + static_cast<size_t>(e) * P;
+                if constexpr (SPAN) {  // each half of the row holds the four prey it scans: 0..3 the group, 4..7 the replica
+                    const int t0 = helper ? 4 : 0;
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) prey_r[t] = src[t0 + t < P ? t0 + t : P - 1];
+                } else {
 #pragma unroll
                 for (int t = 0; t < 8; ++t) prey_r[t] = src[t < P ? t : P - 1];
+                }
                 if (ag < P) {
                     flag_raw[0] = q_sen[static_cast<size_t>(e) * P + ag];
                     flag_raw[1] = q_cap[static_cast<size_t>(e) * P + ag];
@@ -946,7 +974,59 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             }
         };
         float closest = -1.0f, qx = -5.0f, qy = -5.0f;
-        if (P <= 8) {
+        if (SPAN && P <= 8) {
+            // 16-lane rows: the prey pass split between the halves of the row.  prey_r[0 .. 3] holds prey t0 .. t0 + 3 of this
+            // half (t0 = 0 in the group half, 4 in the replica), slots past the end a copy of prey P - 1.
+            const float2 (&pl)[8] = prey_r;
+            const int t0 = helper ? 4 : 0;
+            // the membership tests with the lane's conditions folded into the radii: a squared distance is >= 0 (or NaN), so
+            // against -1 no test passes -- an idle lane senses nothing, a lane that does not play 'no_action' captures nothing.
+            // A copy of prey P - 1 sets its bit at its own slot's index >= P; `in_p` drops those after the reduction.
+            const bool acts = lane_ok & (act == 4);
+            const float sr2e = lane_ok ? sr2 : -1.0f, cr2e = acts ? cr2 : -1.0f;
+            float d2[4];
+            uint32_t m = 0;  // bits 0..3: prey t0 + t within this agent's sensing radius; bits 8..11: within its capture radius
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float dx = x - pl[t].x, dy = y - pl[t].y;
+                d2[t] = dx * dx + dy * dy;
+                m |= (d2[t] <= sr2e ? 1u : 0u) << t;
+                m |= (d2[t] <= cr2e ? 1u : 0u) << (8 + t);
+            }
+            m <<= t0;
+            m = group_or<GW>(m);                            // over the agents of this half: its four prey
+            m |= static_cast<uint32_t>(xor_lane_i<8>(static_cast<int>(m)));  // and the other half's: all 16 lanes hold all 8
+            const uint32_t in_p = (1u << P) - 1u;
+            if constexpr (!OBS_ONLY) {  // a11 _update_tracking_and_locations (PredatorCapturePrey.py:72-95)
+                const uint32_t s_b = m & in_p, c_b = (m >> 8) & in_p;
+                nsen_lo = sen_lo | (s_b & ~cap_lo);            // sensed: any agent in range, prey not yet captured
+                ncap_lo = cap_lo | (nsen_lo & c_b & ~cap_lo);  // captured: sensed and a 'no_action' agent in range
+                if (env_st && ag < P) {
+                    a.st.prey_sensed[static_cast<size_t>(e) * P + ag] = (nsen_lo >> ag) & 1u;
+                    a.st.prey_captured[static_cast<size_t>(e) * P + ag] = (ncap_lo >> ag) & 1u;
+                }
+            }
+            // a13 nearest uncaptured prey within the agent's own sensing radius.  The sequential scan over t = 0 .. P - 1 takes
+            // a prey iff it is eligible and strictly nearer than the best so far, so it ends with the LOWEST index among the
+            // eligible prey at the minimal distance.  Each half runs that scan over its own four prey from "none"; the group
+            // half then takes the replica's candidate iff the replica has one and the group has none or the replica's is
+            // STRICTLY nearer: at equal distance the group's stays, whose index is the lower one (0..3 against 4..7).  That is
+            // the candidate the one scan over all eight ends with.  (The copies of prey P - 1 count as captured here: never
+            // eligible.)  Only the group half's qx, qy are read afterwards.
+            const uint32_t cap_l = (ncap_lo | ~in_p) >> t0;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const bool cap = ((cap_l >> t) & 1u) != 0;
+                const bool take = !cap & (d2[t] <= sr2) & ((d2[t] < closest) | (closest == -1.0f));
+                qx = take ? pl[t].x : qx;
+                qy = take ? pl[t].y : qy;
+                closest = take ? d2[t] : closest;
+            }
+            const float o_closest = xor_lane<8>(closest), o_qx = xor_lane<8>(qx), o_qy = xor_lane<8>(qy);
+            const bool other = (o_closest != -1.0f) & ((closest == -1.0f) | (o_closest < closest));
+            qx = other ? o_qx : qx;
+            qy = other ? o_qy : qy;
+        } else if (P <= 8) {
             // common case (P = 6): the whole prey block in registers, one pass for tracking and
             // the nearest-prey search, no second trip to LDS
             const float2 (&pl)[8] = prey_r;
@@ -1044,10 +1124,10 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
 #pragma unroll
                 for (int cc = 0; cc < 6; ++cc) obs_row[cc] = lds.own[lane][cc];
             }
-            write_neighbour_obs<GW, 6, NT>(lds, N, p.num_neighbors, ag, gbase, lane_st, x, y, obs_row);
+            write_neighbour_obs<GW, 6, NT, SPAN>(lds, N, p.num_neighbors, ag, gbase, lane_nb, x, y, obs_row);
         } else {
             if (lane_st) out_store4(obs_row, x, y, qx, qy);
-            write_neighbour_obs<GW, 4, NT>(lds, N, p.num_neighbors, ag, gbase, lane_st, x, y, obs_row);
+            write_neighbour_obs<GW, 4, NT, SPAN>(lds, N, p.num_neighbors, ag, gbase, lane_nb, x, y, obs_row);
         }
         RG_STAMP_E(1);  // observations written
         if constexpr (!OBS_ONLY) {  // a14 reward / termination (PredatorCapturePrey.py:155-176, 209-216)
@@ -1079,7 +1159,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             obs_row[1] = y;
             obs_row[2] = loaded ? 1.0f : 0.0f;
         }
-        write_neighbour_obs<GW, 3, NT>(lds, N, p.num_neighbors, ag, gbase, lane_st, x, y, obs_row);
+        write_neighbour_obs<GW, 3, NT, SPAN>(lds, N, p.num_neighbors, ag, gbase, lane_nb, x, y, obs_row);
         if constexpr (!OBS_ONLY) {
             if (viol) {
                 reward = p.violation_reward;
@@ -1111,7 +1191,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             obs_row[2 * N] = goal_x;
             obs_row[2 * N + 1] = goal_y;
         }
-        write_neighbour_obs<GW, 2, NT>(lds, N, N - 1, ag, gbase, lane_st, x, y, obs_row);  // all others, index order
+        write_neighbour_obs<GW, 2, NT, SPAN>(lds, N, N - 1, ag, gbase, lane_nb, x, y, obs_row);  // all others, index order
         if constexpr (!OBS_ONLY) {
             if (viol) {
                 reward = p.violation_reward;

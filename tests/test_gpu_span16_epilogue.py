@@ -1,0 +1,271 @@
+"""The scenario epilogue of the 16-lane-row step kernels (step_group.h, step_once SPAN), whose prey pass and neighbour slots are
+split between the two halves of an env's row, against the 8-lane-group kernels (RG_STEP_SPAN=0 at rg_create), which are
+unchanged: every output and every state word of every step, word for word, and the float32 oracle where it has a helper.
+
+Batches: 7 envs = one env per wave, 1025 = two per wave (ragged), 2049 = four per wave (last wave ragged); the row kernel runs
+whenever the lane-group dispatch picks at most four env slots per wave (`expected_slots`), which every case asserts.
+"""
+import numpy as np
+import pytest
+
+from test_gpu_baseline_shapes import expected_slots, shape_rollout_vs_oracle
+
+pytestmark = pytest.mark.gpu
+
+STATE = ("poses", "carry_dist", "episode_steps", "reset_count", "prey_loc", "prey_sensed", "prey_captured", "loaded", "load",
+         "zone_load", "messages", "ep_return", "done_return_sum", "done_count", "done_steps_sum")
+OUTS = ("obs", "reward", "done", "dist_travelled", "violation", "remaining", "qp_sweeps")
+SLOTS = {7: 1, 1025: 2, 2049: 4}
+
+
+@pytest.fixture(autouse=True)
+def _lane_group_kernel(monkeypatch):
+    monkeypatch.setenv("RG_STEP_KERNEL", "group")
+
+
+def _pair(scenario, ov, E, monkeypatch, auto_reset=True):
+    """(16-lane rows, 8-lane groups): the same env twice."""
+    from marbler_amd import VecRobotariumEnv
+    envs = []
+    for span in (True, False):
+        if span:
+            monkeypatch.delenv("RG_STEP_SPAN", raising=False)
+        else:
+            monkeypatch.setenv("RG_STEP_SPAN", "0")
+        env = VecRobotariumEnv(scenario, E, overrides=ov, seed=7, auto_reset=auto_reset, collect_qp_stats=True)
+        monkeypatch.delenv("RG_STEP_SPAN", raising=False)
+        env.reset()
+        assert env.step_kernel == "group"
+        envs.append(env)
+    N = envs[0].N
+    assert 5 <= N <= 8 and expected_slots(N, E) == SLOTS[E] <= 4, "the case no longer dispatches the row kernel at this fill"
+    return envs
+
+
+def _outputs(env, step_result):
+    import torch
+    obs, rew, done, info = step_result
+    torch.cuda.synchronize()
+    return [obs.cpu().numpy().view(np.uint32), rew.cpu().numpy().view(np.uint32), done.cpu().numpy(),
+            info["dist_travelled"].cpu().numpy().view(np.uint32), info["violation"].cpu().numpy(), info["remaining"].cpu().numpy(),
+            env.qp_sweeps.cpu().numpy()]
+
+
+def _same_step(what, t, new, old, res_new, res_old):
+    a, b = _outputs(new, res_new), _outputs(old, res_old)
+    for name, x, y in zip(OUTS, a, b):
+        assert np.array_equal(x, y), f"{what} step {t}: {name} differs in {int(np.sum(x != y))} words"
+    for name in STATE:
+        x, y = getattr(new, name), getattr(old, name)
+        assert np.array_equal(x.cpu().numpy().view(np.uint8), y.cpu().numpy().view(np.uint8)), f"{what} step {t}: state {name} differs"
+    return a
+
+
+def _free_run(what, new, old, n_act, steps, seed=11):
+    import torch
+    rng = np.random.RandomState(seed)
+    for t in range(steps):
+        a = torch.as_tensor(rng.randint(0, n_act, size=(new.E, new.N)).astype(np.int32), device=new.device)
+        _same_step(what, t, new, old, new.step(a), old.step(a))
+
+
+NO_ACTION = 4
+
+
+# ---------------------------------------------------------------- 1. the prey split
+def _pcp(N, P=6, **kw):
+    return dict({"predator": (N + 1) // 2, "capture": N // 2, "n_agents": N, "num_prey": P, "max_episode_steps": 12}, **kw)
+
+
+# prey counts: all in the group half / exactly full / one in the replica / the headline / both full / the untouched P > 8 path
+PREY_CASES = [(P, N, E) for i, (P, N) in enumerate((P, N) for P in (1, 4, 5, 6, 8, 9) for N in (5, 8)) for E in ((7, 1025, 2049)[i % 3],)]
+PREY_CASES += [(6, 5, 7), (6, 5, 2049)]   # the headline shape at every fill (1025 is in the list above)
+
+
+@pytest.mark.parametrize("P,N,E", PREY_CASES, ids=[f"P{p}-N{n}-E{e}" for p, n, e in PREY_CASES])
+def test_prey_pass_split_matches_eight_lane_groups(P, N, E, monkeypatch):
+    """24 free-running steps with auto-reset.  The first episode starts from an injected prey block (the sampler puts the prey
+    on the far side of the arena, where a small batch would not reach them in a short run): prey t of env e sits within 0.1 of
+    an agent's x and y -- with e + t even next to a capture agent and already sensed, else next to a predator and not yet
+    sensed -- and in step 0 every agent plays 'no_action', which moves it by less than 0.04.  So step 0 senses the one kind
+    (radius 0.45) and captures the other (radius 0.25) in every env, whatever P and E are; the later steps are random."""
+    import torch
+    new, old = _pair("PredatorCapturePrey", _pcp(N, P), E, monkeypatch)
+    npred = (N + 1) // 2
+    rng = np.random.RandomState(5)
+    xy = new.poses.cpu().numpy()[:, :2, :]                         # [E, 2, N]
+    pre_sensed = ((np.arange(E)[:, None] + np.arange(P)[None, :]) % 2 == 0)
+    agent = np.where(pre_sensed, npred + np.arange(P)[None, :] % (N - npred), np.arange(P)[None, :] % npred)   # [E, P]
+    near = np.take_along_axis(xy, np.repeat(agent[:, None, :], 2, axis=1), axis=2).transpose(0, 2, 1)          # [E, P, 2]
+    prey = (near + rng.uniform(-0.1, 0.1, size=near.shape)).astype(np.float32)
+    for env in (new, old):
+        sd = env.state_dict()
+        sd["prey_loc"] = torch.as_tensor(prey)
+        sd["prey_sensed"] = torch.as_tensor(pre_sensed.astype(np.uint8))
+        env.load_state_dict(sd)
+    sensed = captured = 0
+    rng = np.random.RandomState(11)
+    for t in range(24):
+        acts = rng.randint(0, 5, size=(E, N)).astype(np.int32)
+        if t == 0:
+            acts[:] = NO_ACTION
+        a = torch.as_tensor(acts, device=new.device)
+        out = _same_step(f"P={P} N={N} E={E}", t, new, old, new.step(a), old.step(a))
+        if t == 0:
+            # an env whose every prey is now captured has ended and was reset (flags cleared): it reports `remaining` 0
+            ended = out[2].astype(bool)
+            sensed += int((new.prey_sensed.cpu().numpy().astype(bool) & ~pre_sensed)[~ended].sum())
+            captured += int(new.prey_captured.cpu().numpy()[~ended].sum()) + int((ended & (out[5] == 0) & (out[4] == 0)).sum())
+    assert sensed > 0, "no prey was newly sensed in step 0"
+    assert captured > 0, "no prey was captured in step 0"
+    assert int(new.reset_count.max()) > 1, "no env went through the fused reset"
+
+
+def test_headline_shape_four_per_wave_is_bit_exact_vs_oracle(oracle_lib):
+    shape_rollout_vs_oracle("span16-epilogue-pcp-2049x5", "PredatorCapturePrey",
+                            {"predator": 3, "capture": 2, "n_agents": 5, "max_episode_steps": 8}, 5, 2049, 20, 4, oracle_lib)
+
+
+# ---------------------------------------------------------------- 2. the nearest-prey tie across the halves
+X0, D = np.float32(-0.9), np.float32(0.3)
+# per env: ({prey index: (dy, captured)} of the prey placed on agent 0's vertical, the prey its observation must name or None)
+TIE_ENVS = [({1: (+D, 0), 5: (-D, 0)}, 1),            # tie across the halves: the group half's index wins
+            ({6: (+D, 0), 2: (-D, 0)}, 2),            # the other way round in space
+            ({0: (+D, 0), 3: (-D, 0)}, 0),            # both in the group half
+            ({4: (-D, 0), 7: (+D, 0)}, 4),            # both in the replica's half
+            ({5: (+D, 0)}, 5),                        # the only eligible prey is the replica's
+            ({}, None),                               # none eligible: qx = qy = -5
+            ({1: (np.float32(0.15), 1), 6: (-D, 0)}, 6)]   # the nearer prey is already captured
+
+
+def _tie_state(N, P):
+    E = len(TIE_ENVS)
+    poses = np.zeros((E, 3, N), np.float32)
+    poses[:, 0, 0], poses[:, 1, 0] = X0, 0.0                                  # agent 0 (a predator: it senses), heading 0
+    poses[:, 0, 1:] = np.linspace(0.1, 1.3, N - 1, dtype=np.float32)          # the others far from it and from each other
+    poses[:, 1, 1:] = np.where(np.arange(N - 1) % 2 == 0, 0.7, -0.7).astype(np.float32)
+    prey = np.zeros((E, P, 2), np.float32)
+    prey[:, :, 0] = 1.45                                                      # the rest out of agent 0's reach
+    prey[:, :, 1] = np.linspace(-0.25, 0.25, P, dtype=np.float32)
+    cap = np.zeros((E, P), np.uint8)
+    for e, (placed, _) in enumerate(TIE_ENVS):
+        for i, (dy, c) in placed.items():
+            prey[e, i] = (X0, dy)
+            cap[e, i] = c
+    return poses, prey, cap
+
+
+def test_nearest_prey_tie_goes_to_the_lower_index(oracle_lib, monkeypatch):
+    import torch
+    N, P, E = 5, 8, len(TIE_ENVS)
+    ov = _pcp(N, P)
+    new, old = _pair("PredatorCapturePrey", ov, E, monkeypatch, auto_reset=False)
+    poses, prey, cap = _tie_state(N, P)
+    for env in (new, old):
+        sd = env.state_dict()
+        sd.update(poses=torch.as_tensor(poses), prey_loc=torch.as_tensor(prey), prey_captured=torch.as_tensor(cap),
+                  prey_sensed=torch.as_tensor(cap.copy()))
+        env.load_state_dict(sd)
+    orc = oracle_lib.OracleVecEnv("PredatorCapturePrey", dict(new.cfg), E, dtype=np.float32)
+    orc.poses[...], orc.prey_loc[...], orc.prey_captured[...], orc.prey_sensed[...] = poses, prey, cap, cap
+    acts = np.full((E, N), NO_ACTION, np.int32)
+    o_obs = orc.step(acts)[0].copy()
+    # the states really produce the ties: with the oracle's own post-step pose the two squared distances are equal bit for bit
+    ax, ay = orc.poses[:, 0, 0], orc.poses[:, 1, 0]
+    for e, (placed, want) in enumerate(TIE_ENVS):
+        free = [i for i, (_, c) in placed.items() if not c]
+        d2 = [np.float32(np.float32(ax[e] - prey[e, i, 0]) ** 2) + np.float32(np.float32(ay[e] - prey[e, i, 1]) ** 2) for i in free]
+        if len(free) == 2:
+            assert d2[0].view(np.uint32) == d2[1].view(np.uint32), (e, d2)
+        assert not orc.prey_captured[e][free].any(), "a tied prey was captured in the step: it would leave the search"
+        expect = prey[e, want] if want is not None else np.float32([-5.0, -5.0])
+        assert np.array_equal(o_obs[e, 0, 2:4], expect), (e, o_obs[e, 0, :4], expect)
+    a = torch.as_tensor(acts, device=new.device)
+    got = _same_step("tie", 0, new, old, new.step(a), old.step(a))
+    assert np.array_equal(got[0], o_obs.view(np.uint32)), "obs differs from the oracle"
+
+
+# ---------------------------------------------------------------- 3. the neighbour slots
+NB_CASES = [("PredatorCapturePrey", _pcp(N, num_neighbors=K, capability_aware=cap), 5, E)
+            for N, E in ((5, 2049), (6, 1025), (7, 7), (8, 2049)) for K in (1, 2, 3, N - 1) for cap in (False, True)]
+NB_CASES += [("Warehouse", {"n_agents": 8, "num_neighbors": K, "max_episode_steps": 12}, 5, E) for K, E in ((1, 7), (3, 1025), (7, 2049))]
+NB_CASES += [("Simple", {"n_agents": 7, "max_episode_steps": 12}, 5, E) for E in (7, 2049)]
+
+
+def _nb_id(c):
+    return f"{c[0]}-N{c[1]['n_agents']}-K{c[1].get('num_neighbors', 'all')}-{'cap' if c[1].get('capability_aware') else 'plain'}-E{c[3]}"
+
+
+@pytest.mark.parametrize("scenario,ov,n_act,E", NB_CASES, ids=[_nb_id(c) for c in NB_CASES])
+def test_neighbour_slot_split_matches_eight_lane_groups(scenario, ov, n_act, E, monkeypatch):
+    """M = N - 1 = 4..7 partner slots (odd M: an uneven split), 1, 2, 3 and all neighbours, both row widths."""
+    new, old = _pair(scenario, ov, E, monkeypatch)
+    _free_run(_nb_id((scenario, ov, n_act, E)), new, old, n_act, 20)
+    assert int(new.reset_count.max()) > 1
+
+
+def test_warehouse_two_per_wave_is_bit_exact_vs_oracle(oracle_lib):
+    shape_rollout_vs_oracle("span16-epilogue-wh-1025x8", "Warehouse", {"n_agents": 8, "max_episode_steps": 8}, 5, 1025, 16, 2, oracle_lib)
+
+
+def test_equidistant_neighbours_one_per_half_keep_index_order(oracle_lib, monkeypatch):
+    """Every agent at heading 0 playing 'no_action' (the step moves each along x only, y stays as placed), agents 1 and 4 at
+    (x0, +d) and (x0, -d) of agent 0: with N = 5 agent 0's partner slots are
+    agents 1, 2 (group half) and 3, 4 (replica), so the tied pair has one member in each half.  num_neighbors = 1: only the first
+    of the two is observed, and it must be agent 1."""
+    import torch
+    N, E = 5, 7
+    ov = _pcp(N, 6, num_neighbors=1)
+    new, old = _pair("PredatorCapturePrey", ov, E, monkeypatch, auto_reset=False)
+    poses = np.zeros((E, 3, N), np.float32)
+    poses[:, 0, :] = np.float32([-0.9, -0.9, 0.3, 0.9, -0.9])
+    poses[:, 1, :] = np.float32([0.0, 0.45, 0.6, -0.6, -0.45])
+    for env in (new, old):
+        sd = env.state_dict()
+        sd["poses"] = torch.as_tensor(poses)
+        env.load_state_dict(sd)
+    orc = oracle_lib.OracleVecEnv("PredatorCapturePrey", dict(new.cfg), E, dtype=np.float32)
+    orc.poses[...] = poses
+    orc.prey_loc[...] = new.prey_loc.cpu().numpy()
+    acts = np.full((E, N), NO_ACTION, np.int32)
+    o_obs = orc.step(acts)[0].copy()
+    px, py = orc.poses[:, 0, :], orc.poses[:, 1, :]
+    d2 = [np.float32(np.float32(px[:, j] - px[:, 0]) ** 2) + np.float32(np.float32(py[:, j] - py[:, 0]) ** 2) for j in (1, 4)]
+    assert np.array_equal(d2[0].view(np.uint32), d2[1].view(np.uint32)), d2
+    assert np.array_equal(o_obs[:, 0, 4:6], np.stack([px[:, 1], py[:, 1]], axis=1)), "the oracle does not name agent 1"
+    a = torch.as_tensor(acts, device=new.device)
+    got = _same_step("equidistant", 0, new, old, new.step(a), old.step(a))
+    assert np.array_equal(got[0], o_obs.view(np.uint32)), "obs differs from the oracle"
+
+
+# ---------------------------------------------------------------- 4. the replica's stores stay inside the agent's own row
+GUARD_CASES = [("pcp-od4", "PredatorCapturePrey", _pcp(5), 5), ("pcp-od6", "PredatorCapturePrey", _pcp(6, capability_aware=True), 5),
+               ("warehouse", "Warehouse", {"n_agents": 8, "max_episode_steps": 12}, 5), ("simple", "Simple", {"n_agents": 7, "max_episode_steps": 12}, 5)]
+
+
+@pytest.mark.parametrize("name,scenario,ov,n_act", GUARD_CASES, ids=[c[0] for c in GUARD_CASES])
+def test_replica_stores_leave_the_red_zones_intact(name, scenario, ov, n_act, monkeypatch):
+    """E = 2049: four env slots per wave, and the last wave holds one env and three absent ones, whose rows would begin right
+    where `obs` ends.  Every array of the row-kernel env is carved out of one slab with 1 KB red zones of a sentinel byte around it
+    (tests/test_gpu_redzone.py): after every step all red-zone bytes must be intact -- a neighbour row stored by the replica half
+    of an absent env's row would land in the zone behind `obs` -- and every output and state word must equal the 8-lane-group
+    env's, which has ordinary allocations."""
+    import torch
+    from marbler_amd import VecRobotariumEnv
+    from test_gpu_redzone import _guarded_class
+    E = 2049
+    monkeypatch.setenv("RG_STEP_SPAN", "0")
+    old = VecRobotariumEnv(scenario, E, overrides=ov, seed=7, collect_qp_stats=True)
+    monkeypatch.delenv("RG_STEP_SPAN", raising=False)
+    new = _guarded_class()(scenario, E, overrides=ov, seed=7, collect_qp_stats=True, slab_bytes=E * 8192 + (8 << 20))
+    assert new.step_kernel == old.step_kernel == "group" and expected_slots(new.N, E) == 4
+    new.reset()
+    old.reset()
+    assert new.red_zones_intact().size == 0
+    rng = np.random.RandomState(3)
+    for t in range(16):
+        a = torch.as_tensor(rng.randint(0, n_act, size=(E, new.N)).astype(np.int32), device=new.device)
+        _same_step(name, t, new, old, new.step(a), old.step(a))
+        bad = new.red_zones_intact()
+        assert bad.size == 0, f"{name} step {t}: {bad.size} red-zone bytes damaged, first after `{new.owner_of(int(bad[0]))}`"
+    assert int(new.reset_count.max()) > 1
