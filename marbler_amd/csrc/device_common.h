@@ -91,6 +91,52 @@ __device__ __forceinline__ float mirror_upper_half(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(b, b, 0x141, 0xF, 0xC, false));
 }
 
+// both halves at once: every lane gets the value of the lane eight away (row_ror:8 under a full mask).  For a value whose old
+// contents neither half needs again: unlike to_lower_half it is not tied to them, so it costs no copy where they are still live.
+__device__ __forceinline__ float swap_halves(float v) {
+    return xor_lane<8>(v);
+}
+
+// ------------------------------------------------------------------ the argument block in vector registers (SPAN kernels)
+// A kernel at the scalar-register limit does not keep its argument values: the compiler fetches each one again where it is used,
+// one scalar-memory round trip in front of the instruction that needs it.  The 16-lane-row kernels therefore fetch the whole
+// block ONCE more with vector loads at their very start -- dword i of the block in lane i % 64 of register i / 64 -- and read a
+// value where it is needed with v_readlane_b32: one instruction, no wait (the loads return long before the epilogue).
+constexpr int ARG_REGS = 4;
+static_assert(sizeof(KernelArgs) <= ARG_REGS * 64 * 4 && sizeof(KernelArgs) % 4 == 0, "the argument block fits four registers of dwords");
+__device__ __forceinline__ void load_arg_regs(const KernelArgs &a, int lane, int (&av)[ARG_REGS]) {
+    constexpr int DW = static_cast<int>(sizeof(KernelArgs) / 4);
+#pragma unroll
+    for (int c = 0; c < ARG_REGS; ++c) {
+        const int i = c * 64 + lane;
+        av[c] = reinterpret_cast<const int *>(&a)[i < DW ? i : DW - 1];   // (clamped: no lane reads past the block)
+    }
+}
+// the argument at byte offset `off` of the block (a constant where this is inlined).  A pointer is rebuilt as a GLOBAL one first:
+// read back from registers, the compiler can no longer tell by itself, and would store through it with flat instructions.
+template <typename T>
+__device__ __forceinline__ T arg_reg(const int (&av)[ARG_REGS], unsigned off) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "dwords and pointers");
+    const int lo = __builtin_amdgcn_readlane(av[off >> 8], (off >> 2) & 63);
+    if constexpr (sizeof(T) == 4) {
+        return __builtin_bit_cast(T, lo);
+    } else {
+        const unsigned o2 = off + 4;
+        const int hi = __builtin_amdgcn_readlane(av[o2 >> 8], (o2 >> 2) & 63);
+        const unsigned long long b = (static_cast<unsigned long long>(static_cast<unsigned int>(hi)) << 32) | static_cast<unsigned int>(lo);
+        if constexpr (std::is_pointer<T>::value) {
+#ifdef __HIP_DEVICE_COMPILE__
+            typedef __attribute__((address_space(1))) std::remove_pointer_t<T> *GlobalPtr;
+            return (T) reinterpret_cast<GlobalPtr>(b);
+#else
+            return reinterpret_cast<T>(b);   // (the host pass of a translation unit only parses the kernels)
+#endif
+        } else {
+            return __builtin_bit_cast(T, b);
+        }
+    }
+}
+
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 // d[i] <- bits of d[i].x * d[i].x + d[i].y * d[i].y in binary32, i < K: VOP3P v_dot2_f32_f16 with a literal-zero addend
 // (the compiler's own selection for __builtin_amdgcn_fdot2 is v_dot2c, which costs an extra v_mov to clear the

@@ -10,7 +10,8 @@
 //   RG_TPE_DIAG              thread-per-env kernel: replayed-chunk mask and per-controller sweep counts in io.qp_sweeps
 //   RG_TPE_GUARD             thread-per-env kernel: stores through the LDS staging block are bounds-checked
 //   RG_HOST_SIM              the kernels compiled for the host (tests/sanitize/): 64 threads = 64 lanes
-// and the tuning constants RG_CHUNK, RG_MAX_WAVES, RG_TPE_W4 / W5 / W78, RG_TPE_NO_W3 (A/B builds).
+// and the tuning constants RG_CHUNK, RG_MAX_WAVES, RG_ROW_ARG_REGS / SWAP_HALVES, RG_TPE_W4 / W5 / W78, RG_TPE_NO_W3
+// (A/B builds).
 // One-off probes of rounds 2-4 (shadow copies, RG_PROBE_*, RG_FIXED_U, RG_DENSE_PRETEST, RG_NT_STORES, RG_NO_XCD_REMAP,
 // RG_TPE_NO_DMAX_GUARD) were removed in round 5; what they measured is in NOTEBOOK.md and profiles/, the code in git history.
 #pragma once
@@ -21,6 +22,13 @@
 #endif
 #ifndef RG_MAX_WAVES
 #define RG_MAX_WAVES 1024   // lane-group kernel: partly filled waves up to one wave per SIMD
+#endif
+// the 16-lane-row kernels' argument handling, one switch per part (A/B builds; NOTEBOOK.md "argument reloads"): 1 = shipped
+#ifndef RG_ROW_ARG_REGS
+#define RG_ROW_ARG_REGS 1      // arguments behind the sub-step loop from the block's copy in vector registers
+#endif
+#ifndef RG_ROW_SWAP_HALVES
+#define RG_ROW_SWAP_HALVES 1   // controller set-up: the replica's pair constants cross by an untied move
 #endif
 #ifndef RG_TPE_W4
 #define RG_TPE_W4 3   // waves per SIMD the N <= 4 instantiations are compiled for

@@ -159,12 +159,15 @@ __device__ __forceinline__ int controller(const rg_scenario_params &p, const Con
         });
         static_for<3, 7>([&](auto JJ) {
             constexpr int J = decltype(JJ)::value;
-            ex[J] = to_lower_half(ex[J]);
-            ey[J] = to_lower_half(ey[J]);
-            fx[J] = to_lower_half(fx[J]);
-            fy[J] = to_lower_half(fy[J]);
-            bp[J] = to_lower_half(bp[J]);
-            emax[J] = to_lower_half(emax[J]);
+            // (both halves swap: the replica's own slots J are dead from here on -- it runs no sweep -- and a move that kept
+            // them would be tied to the values just copied to slots 0..2: one register copy per move)
+            auto cross = [](float v) { return RG_ROW_SWAP_HALVES ? swap_halves(v) : to_lower_half(v); };
+            ex[J] = cross(ex[J]);
+            ey[J] = cross(ey[J]);
+            fx[J] = cross(fx[J]);
+            fy[J] = cross(fy[J]);
+            bp[J] = cross(bp[J]);
+            emax[J] = cross(emax[J]);
         });
     } else {
         static_for<1, GW>([&](auto KK) {
@@ -418,6 +421,24 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     RG_STAMPS_BEGIN()
     const rg_scenario_params &p = a.p;
     const Consts &k = a.k;
+    // SPAN: the argument block a second time, in four vector registers (device_common.h load_arg_regs), requested before anything
+    // else.  Everything behind the sub-step loop reads its arguments from them: RG_ARG(a.x) / RG_OUT(x) below are one or two
+    // v_readlane_b32 there, and the plain a.x / sv.io.x in every other kernel (a single-step launch: sv.io is a.io).
+    // RG_ARG_OR(a.x, q): the same for an argument the prologue holds as q.  (Macros, and a conditional on a constant, of which
+    // the compiler emits the live side only: every other kernel is compiled from the plain member access, as before.)
+    constexpr bool ARGV = SPAN && RG_ROW_ARG_REGS != 0;
+    int av[ARG_REGS] = {0, 0, 0, 0};
+    if constexpr (ARGV) load_arg_regs(a, threadIdx.x, av);
+#define RG_ARG_OFF(f) static_cast<unsigned>(reinterpret_cast<const char *>(&(f)) - reinterpret_cast<const char *>(&a))
+#define RG_ARG(f) (ARGV ? arg_reg<std::decay_t<decltype(f)>>(av, RG_ARG_OFF(f)) : (f))
+#define RG_ARG_OR(f, q) (ARGV ? arg_reg<std::decay_t<decltype(q)>>(av, RG_ARG_OFF(f)) : (q))
+#define RG_OUT(m) (ARGV ? arg_reg<std::decay_t<decltype(sv.io.m)>>(av, RG_ARG_OFF(a.io.m)) : (sv.io.m))
+    auto arg_elem = [&](const auto &array, int i) {   // element i of an int array of the block that lies in one register (ARGV only)
+        const unsigned off = static_cast<unsigned>(reinterpret_cast<const char *>(&array) - reinterpret_cast<const char *>(&a));
+        return __builtin_amdgcn_readlane(av[off >> 8], static_cast<int>((off >> 2) & 63) + i);
+    };
+    static_assert(offsetof(KernelArgs, p.torque) / 256 == (offsetof(KernelArgs, p.torque) + sizeof(rg_scenario_params::torque) - 1) / 256,
+                  "arg_elem(p.torque, j): the table lies in one of the argument registers");
     // ---- kernel arguments first: every pointer and scalar the loads below need, fetched TOGETHER.  Left to itself
     // the compiler fetches each kernarg field where it is first used: five dependent scalar-memory round trips, the
     // state loads issued in between and waited for one group at a time -- 3.3 k of a wave's 24 k cycles went by
@@ -527,14 +548,14 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     uint32_t nx_grid[7] = {0, 0, 0, 0, 0, 0, 0};   // ArcticTransport: this lane's 6 terrain dwords + the goal column
     auto load_next = [&](bool want) {              // this lane's share of the env's drawn-ahead block
         if (want) {
-            const float *nb = q_nin + static_cast<size_t>(e) * q_nst;
+            const auto nb = RG_ARG_OR(a.st.next_init, q_nin) + static_cast<size_t>(e) * RG_ARG_OR(a.next_stride, q_nst);
             if (ag < N) {
                 nx_pose[0] = nb[ag];
                 nx_pose[1] = nb[N + ag];
                 nx_pose[2] = nb[2 * N + ag];
             }
             if constexpr (SCN == RG_SCN_PREDATOR_CAPTURE_PREY || SCN == RG_SCN_SIMPLE) {
-                if (ag < q_P) {
+                if (ag < RG_ARG_OR(p.num_prey, q_P)) {
                     nx_a = nb[3 * N + 2 * ag];
                     nx_b = nb[3 * N + 2 * ag + 1];
                 }
@@ -919,8 +940,11 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     }
 
     // ---- scenario epilogue
-    const int D = p.obs_dim;
-    float *obs_row = sv.io.obs + (eN + ag) * D;
+    const int D = RG_ARG(p.obs_dim);
+    const auto obs_row = RG_OUT(obs) + (eN + ag) * D;
+    // (SPAN: the prologue's flags formed again from the registers, rather than fetched again)
+    const bool ahead_e = ARGV ? AHEAD && (!OBS_ONLY) && RG_ARG(a.next_stride) > 0 && RG_ARG(a.auto_reset) : ahead;
+    const bool stats_e = ARGV ? (!OBS_ONLY) && RG_ARG(a.st.ep_return) != nullptr : stats;
     bool done = false;
     int remaining = -1;
     float reward = 0.0f;
@@ -930,12 +954,12 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     // drawn-ahead block is fetched now, behind the epilogue
     RG_LATE(rc_raw);
     RG_LATE(nx_tag);
-    const bool have_next = ahead & (nx_tag == rc_raw);  // the block holds exactly the episode that would start now
-    const bool next_early = env_ok & have_next & ((viol != 0) | (steps > p.max_episode_steps));
+    const bool have_next = ahead_e & (nx_tag == rc_raw);  // the block holds exactly the episode that would start now
+    const bool next_early = env_ok & have_next & ((viol != 0) | (steps > RG_ARG(p.max_episode_steps)));
     if constexpr (AHEAD) load_next(next_early & !helper);
 
     if constexpr (SCN == RG_SCN_PREDATOR_CAPTURE_PREY) {
-        const int P = q_P;
+        const int P = RG_ARG_OR(p.num_prey, q_P);
         if constexpr (TEAM) {
             RG_LATE(sr);
             RG_LATE(cr);
@@ -1002,8 +1026,8 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                 nsen_lo = sen_lo | (s_b & ~cap_lo);            // sensed: any agent in range, prey not yet captured
                 ncap_lo = cap_lo | (nsen_lo & c_b & ~cap_lo);  // captured: sensed and a 'no_action' agent in range
                 if (env_st && ag < P) {
-                    a.st.prey_sensed[static_cast<size_t>(e) * P + ag] = (nsen_lo >> ag) & 1u;
-                    a.st.prey_captured[static_cast<size_t>(e) * P + ag] = (ncap_lo >> ag) & 1u;
+                    RG_ARG(a.st.prey_sensed)[static_cast<size_t>(e) * P + ag] = (nsen_lo >> ag) & 1u;
+                    RG_ARG(a.st.prey_captured)[static_cast<size_t>(e) * P + ag] = (ncap_lo >> ag) & 1u;
                 }
             }
             // a13 nearest uncaptured prey within the agent's own sensing radius.  The sequential scan over t = 0 .. P - 1 takes
@@ -1091,8 +1115,8 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                 for (int i = ag; i < P; i += GW) {
                     const uint32_t sw_ = i < 32 ? nsen_lo >> i : nsen_hi >> (i - 32);
                     const uint32_t cw_ = i < 32 ? ncap_lo >> i : ncap_hi >> (i - 32);
-                    a.st.prey_sensed[static_cast<size_t>(e) * P + i] = sw_ & 1u;
-                    a.st.prey_captured[static_cast<size_t>(e) * P + i] = cw_ & 1u;
+                    RG_ARG(a.st.prey_sensed)[static_cast<size_t>(e) * P + i] = sw_ & 1u;
+                    RG_ARG(a.st.prey_captured)[static_cast<size_t>(e) * P + i] = cw_ & 1u;
                 }
             }
         }
@@ -1111,7 +1135,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         }
         }
         RG_STAMP_E(0);  // prey tracked, nearest prey found
-        const int od = p.capability_aware ? 6 : 4;
+        const int od = RG_ARG(p.capability_aware) ? 6 : 4;
         lds.own[lane][0] = x;
         lds.own[lane][1] = y;
         lds.own[lane][2] = qx;
@@ -1124,10 +1148,10 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
 #pragma unroll
                 for (int cc = 0; cc < 6; ++cc) obs_row[cc] = lds.own[lane][cc];
             }
-            write_neighbour_obs<GW, 6, NT, SPAN>(lds, N, p.num_neighbors, ag, gbase, lane_nb, x, y, obs_row);
+            write_neighbour_obs<GW, 6, NT, SPAN>(lds, N, RG_ARG(p.num_neighbors), ag, gbase, lane_nb, x, y, obs_row);
         } else {
             if (lane_st) out_store4(obs_row, x, y, qx, qy);
-            write_neighbour_obs<GW, 4, NT, SPAN>(lds, N, p.num_neighbors, ag, gbase, lane_nb, x, y, obs_row);
+            write_neighbour_obs<GW, 4, NT, SPAN>(lds, N, RG_ARG(p.num_neighbors), ag, gbase, lane_nb, x, y, obs_row);
         }
         RG_STAMP_E(1);  // observations written
         if constexpr (!OBS_ONLY) {  // a14 reward / termination (PredatorCapturePrey.py:155-176, 209-216)
@@ -1136,14 +1160,14 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             const int unseen1 = P - __builtin_popcount(nsen_lo) - __builtin_popcount(nsen_hi);
             const int left1 = P - __builtin_popcount(ncap_lo) - __builtin_popcount(ncap_hi);
             if (viol) {
-                reward = p.violation_reward;
+                reward = RG_ARG(p.violation_reward);
                 done = true;
             } else {
                 reward = 0.0f;
-                reward = reward + static_cast<float>(unseen0 - unseen1) * p.sense_reward;
-                reward = reward + static_cast<float>(left0 - left1) * p.capture_reward;
-                reward = reward + p.time_penalty;
-                if (steps > p.max_episode_steps || left1 == 0) {
+                reward = reward + static_cast<float>(unseen0 - unseen1) * RG_ARG(p.sense_reward);
+                reward = reward + static_cast<float>(left0 - left1) * RG_ARG(p.capture_reward);
+                reward = reward + RG_ARG(p.time_penalty);
+                if (steps > RG_ARG(p.max_episode_steps) || left1 == 0) {
                     done = true;
                     remaining = left1;
                 }
@@ -1159,26 +1183,26 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             obs_row[1] = y;
             obs_row[2] = loaded ? 1.0f : 0.0f;
         }
-        write_neighbour_obs<GW, 3, NT, SPAN>(lds, N, p.num_neighbors, ag, gbase, lane_nb, x, y, obs_row);
+        write_neighbour_obs<GW, 3, NT, SPAN>(lds, N, RG_ARG(p.num_neighbors), ag, gbase, lane_nb, x, y, obs_row);
         if constexpr (!OBS_ONLY) {
             if (viol) {
-                reward = p.violation_reward;
+                reward = RG_ARG(p.violation_reward);
                 done = true;
             } else {
                 const bool green = (ag % 2) == 0;  // warehouse.py:63-65
                 if (loaded) {
-                    if (x < -1.5f + p.goal_width && ((green && y > 0.0f) || (!green && y <= 0.0f))) {
-                        reward = p.unload_reward;
+                    if (x < -1.5f + RG_ARG(p.goal_width) && ((green && y > 0.0f) || (!green && y <= 0.0f))) {
+                        reward = RG_ARG(p.unload_reward);
                         loaded = 0;
                     }
                 } else {
-                    if (x > 1.5f - p.goal_width && ((!green && y > 0.0f) || (green && y <= 0.0f))) {
-                        reward = p.load_reward;
+                    if (x > 1.5f - RG_ARG(p.goal_width) && ((!green && y > 0.0f) || (green && y <= 0.0f))) {
+                        reward = RG_ARG(p.load_reward);
                         loaded = 1;
                     }
                 }
-                done = steps > p.max_episode_steps;
-                if (lane_st) a.st.loaded[eN + ag] = static_cast<uint8_t>(loaded);
+                done = steps > RG_ARG(p.max_episode_steps);
+                if (lane_st) RG_ARG(a.st.loaded)[eN + ag] = static_cast<uint8_t>(loaded);
             }
         }
     } else if constexpr (SCN == RG_SCN_SIMPLE) {  // scenarios/Simple/simple.py:155-225
@@ -1194,13 +1218,13 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         write_neighbour_obs<GW, 2, NT, SPAN>(lds, N, N - 1, ag, gbase, lane_nb, x, y, obs_row);  // all others, index order
         if constexpr (!OBS_ONLY) {
             if (viol) {
-                reward = p.violation_reward;
+                reward = RG_ARG(p.violation_reward);
                 done = true;
             } else {
                 const float dx = x - goal_x, dy = y - goal_y;
                 const float r = -(dx * dx + dy * dy);
-                reward = r * p.reward_scaler;
-                done = steps > p.max_episode_steps;
+                reward = r * RG_ARG(p.reward_scaler);
+                done = steps > RG_ARG(p.max_episode_steps);
             }
         }
     } else if constexpr (SCN == RG_SCN_ARCTIC_TRANSPORT) {  // ArcticTransport.py:84-143, agent.py:14-87
@@ -1305,7 +1329,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             obs_row[4] = static_cast<float>(zone1);
 #pragma unroll
             for (int i = 0; i < 4; ++i) obs_row[5 + i] = static_cast<float>(msg[i]);
-            if (p.capability_aware) {
+            if (RG_ARG(p.capability_aware)) {
                 if constexpr (TEAM) obs_row[9] = static_cast<float>(tq_raw);
                 else obs_row[9] = static_cast<float>(p.torque[ag]);
                 obs_row[10] = agent_step;
@@ -1318,24 +1342,25 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             if constexpr (TEAM) team_lds<SCN, GW>().torque[lane] = tq_raw;   // the replay reads every partner's
             Sync::sync();
             if (viol) {
-                reward = p.violation_reward;
+                reward = RG_ARG(p.violation_reward);
                 done = true;
             } else {
                 // zone depletion is order-dependent across agents (MaterialTransport.py:161-189):
                 // every lane replays the env's sequential loop from the LDS copy
-                reward = p.time_penalty;
-                const float egw = p.end_goal_width;
-                const float zr2 = p.zone1_radius * p.zone1_radius;
+                reward = RG_ARG(p.time_penalty);
+                const float egw = RG_ARG(p.end_goal_width);
+                const float zr2 = RG_ARG(p.zone1_radius) * RG_ARG(p.zone1_radius);
                 bool any_load = false;
                 for (int j = 0; j < N; ++j) {
                     const float jx = lds.ax[gbase + j], jy = lds.ay[gbase + j];
                     int jl = lds.aload[gbase + j];
                     int tq;
                     if constexpr (TEAM) tq = team_lds<SCN, GW>().torque[gbase + j];
+                    else if constexpr (ARGV) tq = arg_elem(p.torque, j);
                     else tq = p.torque[j];
                     if (jl > 0) {
                         if (jx < -1.5f + egw) {
-                            reward = reward + static_cast<float>(jl) * p.unload_multiplier;
+                            reward = reward + static_cast<float>(jl) * RG_ARG(p.unload_multiplier);
                             jl = 0;
                         }
                     } else {
@@ -1347,7 +1372,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                                 jl = zone1;
                                 zone1 = 0;
                             }
-                            reward = reward + static_cast<float>(jl) * p.load_multiplier;
+                            reward = reward + static_cast<float>(jl) * RG_ARG(p.load_multiplier);
                         } else if (jx * jx + jy * jy <= zr2) {
                             if (zone0 > tq) {
                                 jl = tq;
@@ -1356,13 +1381,13 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                                 jl = zone0;
                                 zone0 = 0;
                             }
-                            reward = reward + static_cast<float>(jl) * p.load_multiplier;
+                            reward = reward + static_cast<float>(jl) * RG_ARG(p.load_multiplier);
                         }
                     }
                     if (j == ag) load = jl;
                     any_load = any_load || (jl != 0);
                 }
-                done = steps > p.max_episode_steps;
+                done = steps > RG_ARG(p.max_episode_steps);
                 if (!done) done = (zone0 == 0 && zone1 == 0 && !any_load);
             }
             int total = 0;
@@ -1372,12 +1397,12 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                 for (int j = 0; j < N; ++j) total += lds.aload[gbase + j];
             }
             if (done) remaining = zone0 + zone1 + total;
-            if (lane_st) a.st.load[eN + ag] = load;
+            if (lane_st) RG_ARG(a.st.load)[eN + ag] = load;
             if (lane_st && ag == 0) {
-                a.st.zone_load[2 * e] = zone0;
-                a.st.zone_load[2 * e + 1] = zone1;
+                RG_ARG(a.st.zone_load)[2 * e] = zone0;
+                RG_ARG(a.st.zone_load)[2 * e + 1] = zone1;
             }
-            if (lane_st && ag < 4) a.st.messages[4 * e + ag] = msg[ag == 0 ? 0 : ag == 1 ? 1 : ag == 2 ? 2 : 3];
+            if (lane_st && ag < 4) RG_ARG(a.st.messages)[4 * e + ag] = msg[ag == 0 ? 0 : ag == 1 ? 1 : ag == 2 ? 2 : 3];
         }
     }
 
@@ -1395,7 +1420,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         const bool ended = done | trunc;
         // sum of the agents' rewards in agent order (read when shared_reward == 0, and by the gymma block)
         float rsum = 0.0f;
-        if ((stats && !p.shared_reward) || gym) {
+        if ((stats_e && !RG_ARG(p.shared_reward)) || gym) {
             Sync::sync();
             lds.ax[lane] = lane_ok ? reward : 0.0f;
             Sync::sync();
@@ -1403,39 +1428,39 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         }
         // ---- stores
         if (lane_st) {
-            float *X = a.st.poses + eN * 3;
+            const auto X = RG_ARG(a.st.poses) + eN * 3;
             X[ag] = x;
             X[N + ag] = y;
             X[2 * N + ag] = th;
-            a.st.carry_dist[eN + ag] = carry;
-            out_store1(sv.io.reward + eN + ag, reward);
-            out_store1(sv.io.dist_travelled + eN + ag, dist);
+            RG_ARG(a.st.carry_dist)[eN + ag] = carry;
+            out_store1(RG_OUT(reward) + eN + ag, reward);
+            out_store1(RG_OUT(dist_travelled) + eN + ag, dist);
             if (ag == 0) {
-                a.st.episode_steps[e] = steps;
-                if (stats) {  // misc.py:178-185: episodeReward += reward[0] | sum(reward)
+                RG_ARG(a.st.episode_steps)[e] = steps;
+                if (stats_e) {  // misc.py:178-185: episodeReward += reward[0] | sum(reward)
                     RG_LATE(st_ret);
                     RG_LATE(st_sum);
                     RG_LATE(st_cnt);
                     RG_LATE(st_steps);
-                    float ret = st_ret + (p.shared_reward ? reward : rsum);
+                    float ret = st_ret + (RG_ARG(p.shared_reward) ? reward : rsum);
                     if (ended) {  // a truncated episode counts like a finished one (run_env counts them, misc.py:186-206)
-                        a.st.done_return_sum[e] = st_sum + ret;
-                        a.st.done_count[e] = st_cnt + 1;
-                        a.st.done_steps_sum[e] = st_steps + steps;
+                        RG_ARG(a.st.done_return_sum)[e] = st_sum + ret;
+                        RG_ARG(a.st.done_count)[e] = st_cnt + 1;
+                        RG_ARG(a.st.done_steps_sum)[e] = st_steps + steps;
                         ret = 0.0f;
                     }
-                    a.st.ep_return[e] = ret;
+                    RG_ARG(a.st.ep_return)[e] = ret;
                 }
-                sv.io.done[e] = done ? 1 : 0;
+                RG_OUT(done)[e] = done ? 1 : 0;
                 if (gym) {
                     q_el[e] = ended ? 0 : el_raw + 1;
                     sv.io.truncated[e] = trunc ? 1 : 0;
                     sv.io.ended[e] = ended ? 1 : 0;
                     sv.io.reward_sum[e] = rsum;
                 }
-                sv.io.violation[e] = static_cast<uint8_t>(viol);
-                sv.io.remaining[e] = remaining;
-                if (sv.io.qp_sweeps) sv.io.qp_sweeps[e] = max_sweeps;
+                RG_OUT(violation)[e] = static_cast<uint8_t>(viol);
+                RG_OUT(remaining)[e] = remaining;
+                if (RG_OUT(qp_sweeps)) RG_OUT(qp_sweeps)[e] = max_sweeps;
             }
             if constexpr (GYM) {
                 // rg_step_io.zero_obs_on_end: an env that ends hands the trainer the reset observation (zeros).  This lane wrote
@@ -1448,21 +1473,21 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         RG_STAMP(5);  // outputs stored
         // ---- fused auto-reset of finished envs (scenario.reset(); ~1 env in 70 per step)
         // an env whose block holds exactly the episode that starts now copies it; any other runs the sampler
-        if (a.auto_reset && __any(env_ok & ended)) {
+        if (RG_ARG(a.auto_reset) && __any(env_ok & ended)) {
             Sync::sync();  // the wave's state stores are issued before the resetting lanes rewrite them
             if constexpr (AHEAD) load_next(env_st & ended & have_next & !next_early);  // ended some other way: fetched late
             if (__any(env_ok & ended & !have_next)) reset_group<SCN, GW, Sync>(a, lds, e, g, ag, env_st & ended & !have_next, rc_raw);
             if (env_st & ended & have_next) {  // the same stores reset_group makes with commit = true
                 if (ag < N) {
-                    float *X = a.st.poses + eN * 3;
+                    const auto X = RG_ARG(a.st.poses) + eN * 3;
                     X[ag] = nx_pose[0];
                     X[N + ag] = nx_pose[1];
                     X[2 * N + ag] = nx_pose[2];
-                    a.st.carry_dist[eN + ag] = 0.0f;
-                    if constexpr (SCN == RG_SCN_WAREHOUSE) a.st.loaded[eN + ag] = 0;
+                    RG_ARG(a.st.carry_dist)[eN + ag] = 0.0f;
+                    if constexpr (SCN == RG_SCN_WAREHOUSE) RG_ARG(a.st.loaded)[eN + ag] = 0;
                     if constexpr (SCN == RG_SCN_MATERIAL_TRANSPORT) {
-                        a.st.load[eN + ag] = 0;
-                        if (ag < 4) a.st.messages[4 * e + ag] = 0;
+                        RG_ARG(a.st.load)[eN + ag] = 0;
+                        if (ag < 4) RG_ARG(a.st.messages)[4 * e + ag] = 0;
                     }
                     if constexpr (SCN == RG_SCN_ARCTIC_TRANSPORT) {
                         a.st.pixel_type[eN + ag] = 0;
@@ -1470,19 +1495,19 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                     }
                 }
                 if constexpr (SCN == RG_SCN_PREDATOR_CAPTURE_PREY || SCN == RG_SCN_SIMPLE) {
-                    const int P = q_P;
-                    const float *nb = q_nin + static_cast<size_t>(e) * q_nst + 3 * N;
+                    const int P = RG_ARG_OR(p.num_prey, q_P);
+                    const auto nb = RG_ARG_OR(a.st.next_init, q_nin) + static_cast<size_t>(e) * RG_ARG_OR(a.next_stride, q_nst) + 3 * N;
                     for (int i = ag; i < P; i += GW) {  // prey `ag` was prefetched; more than GW prey: the rest from the block
-                        float *pl = a.st.prey_loc + (static_cast<size_t>(e) * P + i) * 2;
+                        const auto pl = RG_ARG(a.st.prey_loc) + (static_cast<size_t>(e) * P + i) * 2;
                         pl[0] = i == ag ? nx_a : nb[2 * i];
                         pl[1] = i == ag ? nx_b : nb[2 * i + 1];
                         if constexpr (SCN == RG_SCN_PREDATOR_CAPTURE_PREY) {
-                            a.st.prey_sensed[static_cast<size_t>(e) * P + i] = 0;
-                            a.st.prey_captured[static_cast<size_t>(e) * P + i] = 0;
+                            RG_ARG(a.st.prey_sensed)[static_cast<size_t>(e) * P + i] = 0;
+                            RG_ARG(a.st.prey_captured)[static_cast<size_t>(e) * P + i] = 0;
                         }
                     }
                 } else if constexpr (SCN == RG_SCN_MATERIAL_TRANSPORT) {
-                    if (ag < 2) a.st.zone_load[2 * e + ag] = __builtin_bit_cast(int32_t, nx_a);
+                    if (ag < 2) RG_ARG(a.st.zone_load)[2 * e + ag] = __builtin_bit_cast(int32_t, nx_a);
                 } else if constexpr (SCN == RG_SCN_ARCTIC_TRANSPORT) {
                     uint32_t *gd = reinterpret_cast<uint32_t *>(a.st.grid + static_cast<size_t>(e) * 96);
 #pragma unroll
@@ -1490,8 +1515,8 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                     if (ag == 0) a.st.goal_col[e] = static_cast<int32_t>(nx_grid[6]);
                 }
                 if (ag == 0) {
-                    a.st.reset_count[e] = rc_raw + 1;
-                    a.st.episode_steps[e] = 0;
+                    RG_ARG(a.st.reset_count)[e] = rc_raw + 1;
+                    RG_ARG(a.st.episode_steps)[e] = 0;
                 }
             }
             // the new episode's team: the episode just started is episode rc_raw on either path above (the drawn-ahead block is
@@ -1506,16 +1531,21 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         // A wavefront that is already long -- a QP of one of its envs needed more than two sweeps, or a chunk was
         // replayed -- leaves the draw to a later launch (an env that finishes before it happened runs the sampler as
         // before): the draw must not lengthen the waves the launch is waiting for.
-        if (AHEAD && ahead && !(replayed | __any(max_sweeps > 2)) && __any(env_ok & !ended & !have_next)) {
+        if (AHEAD && ahead_e && !(replayed | __any(max_sweeps > 2)) && __any(env_ok & !ended & !have_next)) {
             const bool need = env_st & !ended & !have_next;
             Sync::sync();  // (LDS scratch of a reset above is free again)
             reset_group<SCN, GW, Sync>(a, lds, e, g, ag, need, rc_raw, reset_dst_next(a, e));
-            if (need && ag == 0) a.st.next_episode[e] = rc_raw;
+            if (need && ag == 0) RG_ARG(a.st.next_episode)[e] = rc_raw;
         }
         RG_STAMP(6);  // reset done
         RG_STAMPS_WRITE(lane, sv.io.qp_sweeps, chunk * EPW, a.E, max_sweeps)
     }
 }
+
+#undef RG_ARG
+#undef RG_ARG_OFF
+#undef RG_ARG_OR
+#undef RG_OUT
 
 // ------------------------------------------------------------------ the step kernels: three families, one body
 // The step comes in three families of kernels: plain; with the lidar on (rg_set_lidar: the range block of lidar.h written at the
