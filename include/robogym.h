@@ -30,7 +30,8 @@ extern "C" {
 /* 7: + rg_policy_rollout() and rg_policy_io (T actor steps and env steps in one launch), rg_sizeof_policy_io(); later, purely
  * additive (no existing layout or entry point changed): + rg_set_lidar(), rg_lidar_params, rg_sizeof_lidar_params(); + rg_set_teams(),
  * rg_team_params, rg_sizeof_team_params(); + rg_actor_forward_sample(), rg_policy_rollout_sample(), rg_policy_sample,
- * rg_sizeof_policy_sample() (soft-policies action sampling).
+ * rg_sizeof_policy_sample() (soft-policies action sampling); + rg_set_disturbance(), rg_disturbance_params,
+ * rg_sizeof_disturbance_params() (per-step pose disturbance).
  * 6 (round 5): rg_scenario_params ends in the barrier-QP solver selection (qp_mode + cvxopt's options): RG_QP_CVXOPT computes the
  * interior-point iterate the reference's stack computes (utilities/controller.py:13-16,23) instead of the exact projection;
  * rg_step_io.zero_obs_on_end; + rg_actor_forward_explore(), rg_actor_pack_gru_f16x2() and rg_actor_weights.gru_packed == 3.
@@ -309,6 +310,29 @@ int rg_sizeof_team_params(void);
  * team_index is NULL, -30 the launch failed, -100 a build without the team kernels.  rg_set_lidar refuses a handle with a
  * pool (-54). */
 int rg_set_teams(rg_handle *h, const rg_team_params *tp);
+
+/* ---- pose disturbance: a random pose error every step (opt-in; out of parity scope: the reference has no such thing) ----
+ * With it on, the first thing an env step (rg_step, rg_rollout) does is displace every agent's stored pose by a bounded,
+ * zero-mean, near-Gaussian amount of standard deviation sigma_xy metres per axis and sigma_theta radians; the rest of the step
+ * reads the displaced pose, so the error accumulates as a random walk through the integrated pose.  The draw is a function of
+ * (seed, global env, episode, step of the episode, agent) alone -- no state is added -- and rg_get_obs applies nothing.  The
+ * spec (Philox block, variates, scale, update) is csrc/disturb.h and DESIGN.md "Pose disturbance".
+ * Layout: 16 bytes, no padding; checked against the binding with rg_sizeof_disturbance_params(). */
+#define RG_DISTURB_MAX_SIGMA_XY 0.1f
+#define RG_DISTURB_MAX_SIGMA_THETA 0.5f
+typedef struct rg_disturbance_params {
+    float sigma_xy;      /* metres, 0 <= sigma_xy <= 0.1 */
+    float sigma_theta;   /* radians, 0 <= sigma_theta <= 0.5 */
+    float reserved[2];   /* ignored */
+} rg_disturbance_params;
+int rg_sizeof_disturbance_params(void);
+/* Turns the disturbance on for every later rg_step / rg_rollout of the handle (either sigma > 0), or off (dp NULL or both
+ * zero: the default kernel choice comes back).  With it on the handle steps with the lane-group kernel at every batch size
+ * (rg_step_kernel() reports 0), and rg_policy_rollout / rg_policy_rollout_sample refuse it (-38).  Errors: -1 NULL handle,
+ * -70 sigma_xy not a finite number in [0, 0.1], -71 sigma_theta not a finite number in [0, 0.5], -72 a handle with the lidar
+ * on, -73 a handle with a team pool, -100 a build without the disturbance kernels.  rg_set_lidar (-57) and rg_set_teams (-65)
+ * refuse a disturbed handle. */
+int rg_set_disturbance(rg_handle *h, const rg_disturbance_params *dp);
 
 /* ---- policy inference for evaluation rollouts ------------------------
  * The EPyMARL recurrent actor the reference evaluates with (utilities/rnn_agent.py:5-29 `RNNAgent`:

@@ -107,12 +107,20 @@ class RgTeamParams(C.Structure):
                 ("capture_radius", C.c_void_p), ("torque", C.c_void_p), ("team_index", C.c_void_p)]
 
 
+DISTURB_MAX_SIGMA_XY, DISTURB_MAX_SIGMA_THETA = 0.1, 0.5
+
+
+class RgDisturbanceParams(C.Structure):
+    _fields_ = [("sigma_xy", C.c_float), ("sigma_theta", C.c_float), ("reserved", C.c_float * 2)]
+
+
 EXPORTS = ("rg_abi_version", "rg_last_error", "rg_sizeof_params", "rg_sizeof_state", "rg_sizeof_step_io", "rg_next_init_stride",
            "rg_create", "rg_destroy", "rg_bind_state", "rg_set_stream", "rg_reset", "rg_step", "rg_rollout", "rg_get_obs", "rg_step_kernel",
            "rg_actor_forward", "rg_actor_forward_explore", "rg_actor_pack_gru", "rg_actor_pack_gru_bf16x3", "rg_actor_pack_gru_f16x2", "rg_actor_last_error",
            "rg_sizeof_policy_io", "rg_policy_rollout", "rg_sizeof_lidar_params", "rg_set_lidar",
            "rg_sizeof_team_params", "rg_set_teams",
-           "rg_actor_forward_sample", "rg_sizeof_policy_sample", "rg_policy_rollout_sample")
+           "rg_actor_forward_sample", "rg_sizeof_policy_sample", "rg_policy_rollout_sample",
+           "rg_sizeof_disturbance_params", "rg_set_disturbance")
 
 _lib = None
 
@@ -179,6 +187,9 @@ def load():
     lib.rg_set_teams.argtypes = [C.c_void_p, C.POINTER(RgTeamParams)]
     lib.rg_set_teams.restype = C.c_int
     lib.rg_sizeof_team_params.restype = C.c_int
+    lib.rg_set_disturbance.argtypes = [C.c_void_p, C.POINTER(RgDisturbanceParams)]
+    lib.rg_set_disturbance.restype = C.c_int
+    lib.rg_sizeof_disturbance_params.restype = C.c_int
     for f in (lib.rg_destroy, lib.rg_bind_state, lib.rg_set_stream, lib.rg_reset, lib.rg_step, lib.rg_rollout, lib.rg_get_obs,
               lib.rg_sizeof_params, lib.rg_sizeof_state, lib.rg_sizeof_step_io):
         f.restype = C.c_int
@@ -187,7 +198,8 @@ def load():
     if (lib.rg_sizeof_params() != C.sizeof(RgScenarioParams) or lib.rg_sizeof_state() != C.sizeof(RgState)
             or lib.rg_sizeof_step_io() != C.sizeof(RgStepIO) or lib.rg_sizeof_policy_io() != C.sizeof(RgPolicyIO)
             or lib.rg_sizeof_policy_sample() != C.sizeof(RgPolicySample)
-            or lib.rg_sizeof_lidar_params() != C.sizeof(RgLidarParams) or lib.rg_sizeof_team_params() != C.sizeof(RgTeamParams)):
+            or lib.rg_sizeof_lidar_params() != C.sizeof(RgLidarParams) or lib.rg_sizeof_team_params() != C.sizeof(RgTeamParams)
+            or lib.rg_sizeof_disturbance_params() != C.sizeof(RgDisturbanceParams)):
         raise RobogymError("struct layout of the binding differs from the compiled library; rebuild")
     _lib = lib
     return lib

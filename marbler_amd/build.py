@@ -19,7 +19,8 @@ SOURCES = ["robogym_kernels.hip", "robogym_rollout_group.hip", "robogym_kernels_
            "robogym_tpe.hip", "robogym_rollout_tpe.hip", "robogym_capi.hip", "actor_mfma.hip", "robogym_policy_h64.hip",
            "robogym_policy_h128.hip", "robogym_policy_sample_h64.hip", "robogym_policy_sample_h128.hip", "robogym_lidar.hip", "robogym_lidar_rollout.hip", "robogym_lidar_ipm.hip",
            "robogym_lidar_rollout_ipm.hip", "robogym_team.hip", "robogym_team_rollout.hip", "robogym_team_ipm.hip",
-           "robogym_team_rollout_ipm.hip"]
+           "robogym_team_rollout_ipm.hip", "robogym_disturb.hip", "robogym_disturb_rollout.hip", "robogym_disturb_ipm.hip",
+           "robogym_disturb_rollout_ipm.hip"]
 # every header of csrc/ (a forgotten one would mean a stale library), and the C ABI's
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(CSRC, "probes", "*.h"))) + \
           [os.path.join(HERE, "..", "include", "robogym.h")]
@@ -63,7 +64,10 @@ FILE_FLAGS = {"robogym_tpe.hip": ["-fno-slp-vectorize"], "robogym_rollout_tpe.hi
               "robogym_lidar_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_lidar_rollout_ipm.hip": GROUP_SLP + IPM_SCHED,
               # the team kernels (step_group.h team_step_kernel): lane-group kernels, with the flags of their mode
               "robogym_team.hip": GROUP_SLP, "robogym_team_rollout.hip": GROUP_SLP,
-              "robogym_team_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_team_rollout_ipm.hip": GROUP_SLP + IPM_SCHED}
+              "robogym_team_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_team_rollout_ipm.hip": GROUP_SLP + IPM_SCHED,
+              # the pose-disturbance kernels (step_group.h disturb_step_kernel): lane-group kernels, with the flags of their mode
+              "robogym_disturb.hip": GROUP_SLP, "robogym_disturb_rollout.hip": GROUP_SLP,
+              "robogym_disturb_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_disturb_rollout_ipm.hip": GROUP_SLP + IPM_SCHED}
 BASE_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 STAMP = LIB + ".flags"
 

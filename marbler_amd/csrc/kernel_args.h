@@ -112,11 +112,12 @@ inline hipError_t for_scenario(int scn, F &&f) {
 
 hipError_t launch_reset(const KernelArgs &a, hipStream_t stream);
 
-// The lane-group step kernels (step_group.h) come in three families -- plain, with the lidar block (rg_set_lidar), with a team
-// pool (rg_set_teams) -- and every (family, solver mode, launch kind) has a translation unit of its own with ONE entry, so that
+// The lane-group step kernels (step_group.h) come in four families -- plain, with the lidar block (rg_set_lidar), with a team
+// pool (rg_set_teams), with the pose disturbance (rg_set_disturbance) -- and every (family, solver mode, launch kind) has a translation unit of its own with ONE entry, so that
 // they compile side by side and each gets its mode's flags (build.py FILE_FLAGS).  The list: X(entry, family, qp_mode, kind).
-// An observation-only launch (rg_get_obs) runs no controller: it exists in the exact mode only and serves both.
-enum GroupFamily { GROUP_PLAIN, GROUP_LIDAR, GROUP_TEAM };
+// An observation-only launch (rg_get_obs) runs no controller: it exists in the exact mode only and serves both.  The disturbance
+// family has none: rg_get_obs displaces nothing, and a disturbed handle's goes to the plain entry.
+enum GroupFamily { GROUP_PLAIN, GROUP_LIDAR, GROUP_TEAM, GROUP_DISTURB };
 enum GroupKind { GROUP_STEP, GROUP_ROLLOUT, GROUP_OBS };
 #define RG_GROUP_ENTRIES(X)                                              \
     X(launch_step, GROUP_PLAIN, RG_QP_EXACT, GROUP_STEP)                 \
@@ -133,11 +134,23 @@ enum GroupKind { GROUP_STEP, GROUP_ROLLOUT, GROUP_OBS };
     X(launch_team_obs, GROUP_TEAM, RG_QP_EXACT, GROUP_OBS)               \
     X(launch_team_rollout, GROUP_TEAM, RG_QP_EXACT, GROUP_ROLLOUT)       \
     X(launch_team_step_ipm, GROUP_TEAM, RG_QP_CVXOPT, GROUP_STEP)        \
-    X(launch_team_rollout_ipm, GROUP_TEAM, RG_QP_CVXOPT, GROUP_ROLLOUT)
-// what a family's kernels take next to the KernelArgs: the handle's lidar and pool blocks (the plain family reads neither)
+    X(launch_team_rollout_ipm, GROUP_TEAM, RG_QP_CVXOPT, GROUP_ROLLOUT)  \
+    X(launch_disturb_step, GROUP_DISTURB, RG_QP_EXACT, GROUP_STEP)       \
+    X(launch_disturb_rollout, GROUP_DISTURB, RG_QP_EXACT, GROUP_ROLLOUT) \
+    X(launch_disturb_step_ipm, GROUP_DISTURB, RG_QP_CVXOPT, GROUP_STEP)  \
+    X(launch_disturb_rollout_ipm, GROUP_DISTURB, RG_QP_CVXOPT, GROUP_ROLLOUT)
+// what a family's kernels take next to the KernelArgs: the handle's lidar and pool blocks and its disturbance scales (the plain
+// family reads none of them)
+// the disturbance's two scales (disturb.h: k of sigma_xy and of sigma_theta), computed once by rg_set_disturbance in binary64:
+// k = binary32(double(sigma) * sqrt(3.0 / 1048575.0)) -- the variates' own standard deviation is sqrt((2^20 - 1) / 3)
+struct DisturbScale {
+    float k_xy, k_theta;
+};
+inline float disturb_scale(float sigma) { return static_cast<float>(static_cast<double>(sigma) * sqrt(3.0 / 1048575.0)); }
 struct GroupSide {
     const rg_lidar_params *lidar;
     const rg_team_params *teams;
+    const DisturbScale *disturb;
 };
 typedef hipError_t GroupLaunch(const KernelArgs &a, const GroupSide &side, hipStream_t stream);
 #define RG_X(entry, family, mode, kind) GroupLaunch entry;

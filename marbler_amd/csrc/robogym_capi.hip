@@ -25,9 +25,11 @@ struct rg_handle {
     bool use_tpe;  // step with the thread-per-env kernel (robogym_tpe.hip) instead of the lane-group kernel
     bool seed_seen;      // the precomputed-reset blocks (rg_state.next_init) were drawn with last_seed
     uint64_t last_seed;
-    bool default_tpe;    // use_tpe as rg_create chose it (restored when the lidar and the team pool are both off)
+    bool default_tpe;    // use_tpe as rg_create chose it (restored when the lidar, the team pool and the disturbance are all off)
     rg_lidar_params lidar;   // rays == 0: off (rg_set_lidar)
     rg_team_params teams;    // n_sets == 0: no pool (rg_set_teams)
+    bool disturbed;          // the pose disturbance is on (rg_set_disturbance), with the scales below
+    rg::DisturbScale disturb;
     bool span;           // rg_step's lane-group launch may put an env on a 16-lane row (step_group.h); RG_STEP_SPAN=0 forces 8-lane groups
 };
 
@@ -194,6 +196,7 @@ int rg_sizeof_policy_io(void) { return static_cast<int>(sizeof(rg_policy_io)); }
 int rg_sizeof_policy_sample(void) { return static_cast<int>(sizeof(rg_policy_sample)); }
 int rg_sizeof_lidar_params(void) { return static_cast<int>(sizeof(rg_lidar_params)); }
 int rg_sizeof_team_params(void) { return static_cast<int>(sizeof(rg_team_params)); }
+int rg_sizeof_disturbance_params(void) { return static_cast<int>(sizeof(rg_disturbance_params)); }
 int rg_next_init_stride(const rg_scenario_params *params) {
     if (check_params(params) != 0) return -1;
     return rg::next_init_stride(*params);
@@ -246,6 +249,8 @@ rg_handle *rg_create(const rg_scenario_params *params, int32_t num_envs, int64_t
     }
     memset(&h->lidar, 0, sizeof(h->lidar));
     memset(&h->teams, 0, sizeof(h->teams));
+    h->disturbed = false;
+    h->disturb = rg::DisturbScale{0.0f, 0.0f};
     return h;
 }
 
@@ -253,9 +258,10 @@ int rg_set_lidar(rg_handle *h, const rg_lidar_params *lp) {
     if (!h) return fail(-1, "handle is NULL");
     if (!lp || lp->rays == 0) {
         memset(&h->lidar, 0, sizeof(h->lidar));
-        h->use_tpe = h->teams.n_sets ? false : h->default_tpe;
+        h->use_tpe = (h->teams.n_sets || h->disturbed) ? false : h->default_tpe;
         return 0;
     }
+    if (h->disturbed) return fail(-57, "rg_set_lidar: the handle has the pose disturbance on (rg_set_disturbance); the disturbance and the lidar do not combine");
     if (h->teams.n_sets) return fail(-54, "rg_set_lidar: the handle has a team pool (rg_set_teams); a pool and the lidar do not combine");
     if (lp->rays < 4 || lp->rays > RG_LIDAR_MAX_RAYS || (lp->rays & 3))
         return fail(-50, "rg_set_lidar: rays must be 0 or a multiple of 4 in 4..32");
@@ -267,6 +273,28 @@ int rg_set_lidar(rg_handle *h, const rg_lidar_params *lp) {
     if (!group_family_built(rg::GROUP_LIDAR)) return fail(-100, "rg_set_lidar: this build has no lidar kernels");
     h->lidar = *lp;
     h->use_tpe = false;   // the lidar is built into the lane-group kernel only
+    return 0;
+}
+
+int rg_set_disturbance(rg_handle *h, const rg_disturbance_params *dp) {
+    if (!h) return fail(-1, "handle is NULL");
+    if (!dp || (dp->sigma_xy == 0.0f && dp->sigma_theta == 0.0f)) {
+        h->disturbed = false;
+        h->disturb = rg::DisturbScale{0.0f, 0.0f};
+        h->use_tpe = (h->lidar.rays || h->teams.n_sets) ? false : h->default_tpe;
+        return 0;
+    }
+    // (a NaN fails both comparisons)
+    if (!(dp->sigma_xy >= 0.0f && dp->sigma_xy <= RG_DISTURB_MAX_SIGMA_XY))
+        return fail(-70, "rg_set_disturbance: sigma_xy must be a finite number of metres in [0, 0.1]");
+    if (!(dp->sigma_theta >= 0.0f && dp->sigma_theta <= RG_DISTURB_MAX_SIGMA_THETA))
+        return fail(-71, "rg_set_disturbance: sigma_theta must be a finite number of radians in [0, 0.5]");
+    if (h->lidar.rays) return fail(-72, "rg_set_disturbance: the handle has the lidar on (rg_set_lidar); the disturbance and the lidar do not combine");
+    if (h->teams.n_sets) return fail(-73, "rg_set_disturbance: the handle has a team pool (rg_set_teams); the disturbance and a pool do not combine");
+    if (!group_family_built(rg::GROUP_DISTURB)) return fail(-100, "rg_set_disturbance: this build has no disturbance kernels");
+    h->disturb = rg::DisturbScale{rg::disturb_scale(dp->sigma_xy), rg::disturb_scale(dp->sigma_theta)};
+    h->disturbed = true;
+    h->use_tpe = false;   // the disturbance is built into the lane-group kernel only
     return 0;
 }
 
@@ -364,12 +392,14 @@ static int launched(hipError_t err) {
     return 0;
 }
 
-// The lane-group launch of a handle: the family its side blocks select (a pool and the lidar exclude each other), the handle's
-// solver mode -- an observation-only launch runs no controller and uses the exact mode's kernel in either -- and the launch kind.
+// The lane-group launch of a handle: the family its side blocks select (a pool, the lidar and the disturbance exclude one
+// another), the handle's solver mode -- an observation-only launch runs no controller and uses the exact mode's kernel in either,
+// and displaces nothing: a disturbed handle's is the plain family's -- and the launch kind.
 static int launch_group_entry(const rg_handle *h, const rg::KernelArgs &a, int kind) {
-    const int family = h->teams.n_sets ? rg::GROUP_TEAM : h->lidar.rays ? rg::GROUP_LIDAR : rg::GROUP_PLAIN;
+    const int family = h->teams.n_sets ? rg::GROUP_TEAM : h->lidar.rays ? rg::GROUP_LIDAR
+                       : (h->disturbed && kind != rg::GROUP_OBS) ? rg::GROUP_DISTURB : rg::GROUP_PLAIN;
     const int mode = kind == rg::GROUP_OBS ? RG_QP_EXACT : h->params.qp_mode;
-    const rg::GroupSide side = {&h->lidar, &h->teams};
+    const rg::GroupSide side = {&h->lidar, &h->teams, &h->disturb};
     for (const GroupEntry &g : g_group)
         if (g.family == family && g.mode == mode && g.kind == kind && g.launch) return launched(g.launch(a, side, h->stream));
     return fail(-100, "this build has no lane-group step kernels");
@@ -405,7 +435,7 @@ int rg_step(rg_handle *h, const int32_t *actions, const rg_step_io *io, int32_t 
     RG_ON_DEVICE(h);
     if (int rc = sync_seed(h, seed)) return rc;
     // (asks the plain family's dispatcher for 8-lane groups throughout: it sets the real value itself)
-    if (!h->span && !h->teams.n_sets && !h->lidar.rays) a.envs_per_wave = -1;
+    if (!h->span && !h->teams.n_sets && !h->lidar.rays && !h->disturbed) a.envs_per_wave = -1;
     if (h->use_tpe) return launched(rg::launch_step_tpe(a, h->stream));
     return launch_group_entry(h, a, rg::GROUP_STEP);
 }
@@ -455,6 +485,7 @@ static int policy_rollout(rg_handle *h, const rg_actor_weights *w, int32_t num_s
     if (h->params.qp_mode == RG_QP_CVXOPT) return fail(-40, "rg_policy_rollout: the interior-point mode (barrier_solver: cvxopt) is not supported");
     if (h->lidar.rays) return fail(-49, "rg_policy_rollout: a handle with the lidar observation on (rg_set_lidar) is not supported");
     if (h->teams.n_sets) return fail(-39, "rg_policy_rollout: a handle with a team pool (rg_set_teams) is not supported");
+    if (h->disturbed) return fail(-38, "rg_policy_rollout: a handle with the pose disturbance on (rg_set_disturbance) is not supported");
     if (!w->use_rnn || w->gru_packed != 3)
         return fail(-41, "rg_policy_rollout: the actor must be a GRU with gru_packed == 3 (two binary16 planes, pack_gru='f16x2')");
     if (w->hidden_dim != 64 && w->hidden_dim != 128) return fail(-42, "rg_policy_rollout: hidden_dim must be 64 or 128");
@@ -502,9 +533,10 @@ int rg_set_teams(rg_handle *h, const rg_team_params *tp) {
     if (!h) return fail(-1, "handle is NULL");
     if (!tp || tp->n_sets == 0) {
         memset(&h->teams, 0, sizeof(h->teams));
-        h->use_tpe = h->lidar.rays ? false : h->default_tpe;
+        h->use_tpe = (h->lidar.rays || h->disturbed) ? false : h->default_tpe;
         return 0;
     }
+    if (h->disturbed) return fail(-65, "rg_set_teams: the handle has the pose disturbance on (rg_set_disturbance); the disturbance and a pool do not combine");
     if (tp->n_sets < 1 || tp->n_sets > RG_TEAM_MAX_SETS) return fail(-60, "rg_set_teams: n_sets must be 0 or in 1..64");
     if (tp->mode != RG_TEAM_EPISODE && tp->mode != RG_TEAM_FIXED)
         return fail(-61, "rg_set_teams: unknown mode (RG_TEAM_EPISODE or RG_TEAM_FIXED)");

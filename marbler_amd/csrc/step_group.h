@@ -1,7 +1,7 @@
 // step_group.h -- the fused env-step kernel for gfx950 (MI355X, CDNA4), lane-group mapping.
-// (Templates only: the step, its kernels in three families -- plain, lidar, team pool -- and their one launch dispatcher.
-// Instantiated by robogym_kernels*.hip / robogym_rollout_group*.hip, robogym_lidar*.hip and robogym_team*.hip, one translation
-// unit per (family, solver mode, launch kind): kernel_args.h RG_GROUP_ENTRIES.)
+// (Templates only: the step, its kernels in four families -- plain, lidar, team pool, pose disturbance -- and their one launch
+// dispatcher.  Instantiated by robogym_kernels*.hip / robogym_rollout_group*.hip, robogym_lidar*.hip, robogym_team*.hip and
+// robogym_disturb*.hip, one translation unit per (family, solver mode, launch kind): kernel_args.h RG_GROUP_ENTRIES.)
 //
 // One launch = one env step for E envs: goal generation, U sim sub-iterations (controller with
 // the barrier-certificate QP every 15th, collision/boundary validation, Euler integration),
@@ -33,6 +33,7 @@
 #include "ipm_qp.h"
 #include "lidar.h"
 #include "team.h"
+#include "disturb.h"
 #include "probes/diag.h"   // diagnostic hooks: every RG_* macro below expands to nothing in the shipped build
 
 namespace rg {
@@ -411,11 +412,15 @@ __device__ __forceinline__ void write_neighbour_obs(Lds<GW> &lds, int N, int Knb
 // owns, into its agent's own obs_row (write_neighbour_obs); every other store is the group half's.  Every DPP exchange and
 // reduction at GW = 8 stays inside its 8-lane half (quad permutes, row_half_mirror), so no value mixes the two halves except
 // where a result is brought across on purpose (row_ror:8, xor_lane_i<8>).
+// NOISE: the pose disturbance of `nz` (disturb.h): the step begins by displacing the poses it has just loaded.  Its own
+// instantiations (disturb_step_kernel).
 template <int SCN, int GW, bool OBS_ONLY, int NT, bool AHEAD, bool GYM, int QPM = 0, typename QpLds = void, typename Sync = WgSync,
-          bool LIDAR = false, bool TEAM = false, bool SPAN = false>
+          bool LIDAR = false, bool TEAM = false, bool SPAN = false, bool NOISE = false>
 __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, const StepView &sv, QpLds *qp_lds = nullptr,
-                                          const rg_lidar_params *lid = nullptr, const rg_team_params *tm = nullptr) {
-    static_assert(!SPAN || (GW == 8 && QPM == 0 && !GYM && !LIDAR && !TEAM), "the 16-lane rows: exact mode, GW = 8, no side blocks");
+                                          const rg_lidar_params *lid = nullptr, const rg_team_params *tm = nullptr,
+                                          const DisturbScale *nz = nullptr) {
+    static_assert(!SPAN || (GW == 8 && QPM == 0 && !GYM && !LIDAR && !TEAM && !NOISE), "the 16-lane rows: exact mode, GW = 8, no side blocks");
+    static_assert(!NOISE || !OBS_ONLY, "an observation-only launch displaces nothing");
     constexpr int RW = SPAN ? 2 * GW : GW;  // lanes per env
     constexpr int EPW = WAVE / RW;  // envs per wave
     RG_STAMPS_BEGIN()
@@ -475,6 +480,12 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         else if constexpr (SCN == RG_SCN_MATERIAL_TRANSPORT) asm volatile("" ::"s"(q_ttq));
     }
 
+    // NOISE: the draw's key and the scales, with the rest (read where the poses arrive: no scalar-memory trip there)
+    const uint64_t q_seed = NOISE ? a.seed : 0;
+    const int64_t q_off = NOISE ? a.env_offset : 0;
+    const float q_kxy = NOISE ? nz->k_xy : 0.0f, q_kth = NOISE ? nz->k_theta : 0.0f;
+    if constexpr (NOISE) asm volatile("" ::"s"(q_seed), "s"(q_off), "s"(q_kxy), "s"(q_kth));
+
     const int N = NT > 0 ? NT : q_N;
     const int lane = threadIdx.x;
     const int ag = lane & (GW - 1);
@@ -506,6 +517,14 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     int team_raw = 0, tq_raw = 0;  // TEAM: the env's set index (fetched first: the pool loads below depend on it); own torque
     if constexpr (TEAM) {
         if (env_ok) team_raw = q_tidx[e];
+    }
+    // NOISE: what the draw is keyed by (the env's episode and step), requested before the poses, with everything else
+    int nz_rc = 0, nz_steps = 0;
+    if constexpr (NOISE) {
+        if (env_ok) {
+            nz_rc = q_rc[e];
+            nz_steps = q_steps[e];
+        }
     }
     if (lane_ok) {
         const float *X = q_poses + eN * 3;
@@ -670,6 +689,23 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             zone1 = q_zone[2 * e + 1];
         }
         if (lane_ok) load = q_load[eN + ag];
+    }
+
+    if constexpr (NOISE) {
+        // The pose the rest of the step reads: displaced before its first use (disturb.h).  The draw is integer work on the two
+        // early loads, pinned HERE, behind every request of the prologue: left free, its first multiply moves up to the two
+        // loads and waits for them before the poses are requested -- a second memory round trip on the step's chain.  Pinned,
+        // the chain grows by the Philox rounds alone.  (They do not overlap the loads' latency: the requests sit in divergent
+        // blocks, behind which a wait for the oldest load is a wait for all of them.)
+        RG_LATE(nz_rc);
+        RG_LATE(nz_steps);
+        int nz_c[3];
+        disturb_draw(static_cast<uint64_t>(q_off + e), nz_rc - 1, nz_steps, ag, q_seed, nz_c);
+        float dx = x, dy = y, dth = th;
+        disturb_pose(q_kxy, q_kth, nz_c, dx, dy, dth);
+        x = lane_ok ? dx : x;
+        y = lane_ok ? dy : y;
+        th = lane_ok ? dth : th;
     }
 
     int viol = 0, max_sweeps = 0;
@@ -1547,35 +1583,48 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
 #undef RG_ARG_OR
 #undef RG_OUT
 
-// ------------------------------------------------------------------ the step kernels: three families, one body
-// The step comes in three families of kernels: plain; with the lidar on (rg_set_lidar: the range block of lidar.h written at the
+// ------------------------------------------------------------------ the step kernels: four families, one body
+// The step comes in four families of kernels: plain; with the lidar on (rg_set_lidar: the range block of lidar.h written at the
 // end of the observation phase); with a team pool (rg_set_teams: the agents' capabilities from set team_index[e] of team.h, and
-// the index of every episode the step starts).  Neither of the last two has a thread-per-env form: such a handle always runs
+// the index of every episode the step starts); with the pose disturbance (rg_set_disturbance: the poses displaced by the draw of
+// disturb.h before the step reads them).  None of the last three has a thread-per-env form: such a handle always runs
 // these.  A family is described by its argument block (the step's own KernelArgs, and the side block next to it that the other
 // kernels never see), by what it hands step_once, and by whether a rollout re-addresses the block every step.
 struct PlainFamily {
     using Args = KernelArgs;
-    static constexpr bool LIDAR = false, TEAM = false, READDRESS = false;
+    static constexpr bool LIDAR = false, TEAM = false, NOISE = false, READDRESS = false;
     static Args args(const KernelArgs &a, const GroupSide &) { return a; }
     __device__ __forceinline__ static const KernelArgs &kernel_args(const Args &x) { return x; }
     __device__ __forceinline__ static const rg_lidar_params *lidar(const Args &) { return nullptr; }
     __device__ __forceinline__ static const rg_team_params *teams(const Args &) { return nullptr; }
+    __device__ __forceinline__ static const DisturbScale *disturb(const Args &) { return nullptr; }
 };
 struct LidarFamily {
     using Args = LidarArgs;
-    static constexpr bool LIDAR = true, TEAM = false, READDRESS = true;
+    static constexpr bool LIDAR = true, TEAM = false, NOISE = false, READDRESS = true;
     static Args args(const KernelArgs &a, const GroupSide &side) { return Args{a, *side.lidar}; }
     __device__ __forceinline__ static const KernelArgs &kernel_args(const Args &x) { return x.k; }
     __device__ __forceinline__ static const rg_lidar_params *lidar(const Args &x) { return &x.lid; }
     __device__ __forceinline__ static const rg_team_params *teams(const Args &) { return nullptr; }
+    __device__ __forceinline__ static const DisturbScale *disturb(const Args &) { return nullptr; }
 };
 struct TeamFamily {
     using Args = TeamArgs;
-    static constexpr bool LIDAR = false, TEAM = true, READDRESS = true;
+    static constexpr bool LIDAR = false, TEAM = true, NOISE = false, READDRESS = true;
     static Args args(const KernelArgs &a, const GroupSide &side) { return Args{a, *side.teams}; }
     __device__ __forceinline__ static const KernelArgs &kernel_args(const Args &x) { return x.k; }
     __device__ __forceinline__ static const rg_lidar_params *lidar(const Args &) { return nullptr; }
     __device__ __forceinline__ static const rg_team_params *teams(const Args &x) { return &x.tp; }
+    __device__ __forceinline__ static const DisturbScale *disturb(const Args &) { return nullptr; }
+};
+struct DisturbFamily {
+    using Args = DisturbArgs;
+    static constexpr bool LIDAR = false, TEAM = false, NOISE = true, READDRESS = true;
+    static Args args(const KernelArgs &a, const GroupSide &side) { return Args{a, *side.disturb}; }
+    __device__ __forceinline__ static const KernelArgs &kernel_args(const Args &x) { return x.k; }
+    __device__ __forceinline__ static const rg_lidar_params *lidar(const Args &) { return nullptr; }
+    __device__ __forceinline__ static const rg_team_params *teams(const Args &) { return nullptr; }
+    __device__ __forceinline__ static const DisturbScale *disturb(const Args &x) { return &x.ds; }
 };
 
 // The argument block of a rollout's next step.  READDRESS: through an opaque copy of the kernel-argument segment's address
@@ -1612,15 +1661,15 @@ __device__ __forceinline__ void step_kernel_body(const typename F::Args &args) {
     const KernelArgs &a = F::kernel_args(args);
     const int N = NT > 0 ? NT : a.p.n_agents;
     if constexpr (!ROLLOUT) {
-        step_once<SCN, GW, OBS_ONLY, NT, true, GYM, QPM, Q, WgSync, F::LIDAR, F::TEAM, SPAN>(a, lds, step_view(a, 0, N, a.p.obs_dim), qp_lds,
-                                                                                           F::lidar(args), F::teams(args));
+        step_once<SCN, GW, OBS_ONLY, NT, true, GYM, QPM, Q, WgSync, F::LIDAR, F::TEAM, SPAN, F::NOISE>(a, lds, step_view(a, 0, N, a.p.obs_dim), qp_lds,
+                                                                                                     F::lidar(args), F::teams(args), F::disturb(args));
     } else {
         for (int t = 0; t < a.num_steps; ++t) {
             if (t) __syncthreads();
             const typename F::Args &now = rollout_step_args<F>(args);
             const KernelArgs &at = F::kernel_args(now);
-            step_once<SCN, GW, OBS_ONLY, NT, false, false, QPM, Q, WgSync, F::LIDAR, F::TEAM>(at, lds, step_view(at, t, N, at.p.obs_dim), qp_lds,
-                                                                                             F::lidar(now), F::teams(now));
+            step_once<SCN, GW, OBS_ONLY, NT, false, false, QPM, Q, WgSync, F::LIDAR, F::TEAM, false, F::NOISE>(at, lds, step_view(at, t, N, at.p.obs_dim), qp_lds,
+                                                                                                            F::lidar(now), F::teams(now), F::disturb(now));
         }
     }
 }
@@ -1645,6 +1694,12 @@ __global__ __launch_bounds__(WAVE) void lidar_step_kernel(const LidarArgs la) {
 template <int SCN, int GW, bool OBS_ONLY, int NT, bool ROLLOUT, bool GYM, int QPM>
 __global__ __launch_bounds__(WAVE) void team_step_kernel(const TeamArgs ta) {
     step_kernel_body<TeamFamily, SCN, GW, OBS_ONLY, NT, ROLLOUT, GYM, QPM>(ta);
+}
+
+// generic agent count (NT = 0) throughout; no observation-only form (rg_get_obs displaces nothing: the plain kernel)
+template <int SCN, int GW, bool ROLLOUT, bool GYM, int QPM>
+__global__ __launch_bounds__(WAVE) void disturb_step_kernel(const DisturbArgs da) {
+    step_kernel_body<DisturbFamily, SCN, GW, false, 0, ROLLOUT, GYM, QPM>(da);
 }
 
 template <int SCN, int GW>
@@ -1702,16 +1757,18 @@ static void launch_kernel(const typename F::Args &args, int grid, hipStream_t st
     if constexpr (ROWS) hipLaunchKernelGGL((step_kernel<SCN, GW, OBS_ONLY, NT, ROLLOUT, 16>), dim3(grid), dim3(WAVE), 0, stream, args);
     else if constexpr (F::LIDAR) hipLaunchKernelGGL((lidar_step_kernel<SCN, GW, OBS_ONLY, ROLLOUT, GYM, QPM>), dim3(grid), dim3(WAVE), 0, stream, args);
     else if constexpr (F::TEAM) hipLaunchKernelGGL((team_step_kernel<SCN, GW, OBS_ONLY, NT, ROLLOUT, GYM, QPM>), dim3(grid), dim3(WAVE), 0, stream, args);
+    else if constexpr (F::NOISE) hipLaunchKernelGGL((disturb_step_kernel<SCN, GW, ROLLOUT, GYM, QPM>), dim3(grid), dim3(WAVE), 0, stream, args);
     else hipLaunchKernelGGL((step_kernel<SCN, GW, OBS_ONLY, NT, ROLLOUT, GYM, QPM>), dim3(grid), dim3(WAVE), 0, stream, args);
 }
 
 // The kernel of (family, scenario, launch kind, mode) at group width gw.  Generic agent count (NT = 0), except GW 8 of the exact
 // mode's step and rollout in the plain and team families: bodies specialised for the agent count (NT = N, 5..8).  The gymma
-// block's, the observation-only, the interior-point and every lidar kernel are generic.  rows: the 16-lane-row kernel instead.
+// block's, the observation-only, the interior-point and every lidar and disturbance kernel are generic.  rows: the 16-lane-row
+// kernel instead.
 template <class F, int SCN, bool OBS_ONLY, bool ROLLOUT, bool GYM, int QPM>
 static hipError_t launch_gw(const typename F::Args &args, int gw, int n, bool rows, int grid, hipStream_t stream) {
     constexpr bool EXACT = QPM == RG_QP_EXACT;
-    constexpr bool BY_N = EXACT && !OBS_ONLY && !GYM && !F::LIDAR;
+    constexpr bool BY_N = EXACT && !OBS_ONLY && !GYM && !F::LIDAR && !F::NOISE;
     constexpr bool ROWS = BY_N && !ROLLOUT && !F::TEAM && !kStampsBuild;
     if (gw == 4) {
         launch_kernel<F, SCN, 4, OBS_ONLY, 0, ROLLOUT, GYM, QPM>(args, grid, stream);
@@ -1743,6 +1800,7 @@ static hipError_t launch_gw(const typename F::Args &args, int gw, int n, bool ro
 template <class F, bool OBS_ONLY, bool ROLLOUT, int QPM>
 static hipError_t launch_group(const KernelArgs &a_in, const GroupSide &side, hipStream_t stream) {
     static_assert(!OBS_ONLY || (!ROLLOUT && QPM == RG_QP_EXACT), "rg_get_obs is a single launch of the exact mode's kernel");
+    static_assert(!OBS_ONLY || !F::NOISE, "rg_get_obs of a disturbed handle is the plain family's launch");
     return for_scenario(a_in.p.scenario, [&](auto scn) -> hipError_t {
         constexpr int SCN = decltype(scn)::value;
         constexpr bool ARCTIC = SCN == RG_SCN_ARCTIC_TRANSPORT;

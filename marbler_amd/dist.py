@@ -1,8 +1,8 @@
 """Multi-GPU: one process per GPU, envs sharded in contiguous blocks, no per-step exchange.
 
 The path shards trivially (envs are independent); the only collectives
-are a broadcast of the scenario parameter block (and of the lidar block and team pool next to it) from rank 0 at init and a gather of
-per-env episode statistics per reporting interval -- both through torch.distributed
+are a broadcast of the scenario parameter block (and of the lidar block, team pool and disturbance block next to it) from rank 0
+at init and a gather of per-env episode statistics per reporting interval -- both through torch.distributed
 (backend "nccl" = RCCL over xGMI on ROCm; "gloo" on CPU for the world_size-2 tests).
 """
 import os
@@ -91,6 +91,28 @@ def broadcast_lidar(lidar, src=0, device=None):
     out = RgLidarParams()
     ctypes.memmove(ctypes.addressof(out), buf.cpu().numpy().tobytes(), n)
     return out if out.rays > 0 else None
+
+
+def broadcast_disturbance(disturbance, src=0, device=None):
+    """The disturbance block next to the parameter block: rank `src` sends its RgDisturbanceParams (None = none, sent as zeros);
+    every rank returns a copy of it, or None.  Every rank calls it (a collective), whatever its own argument."""
+    import ctypes
+    from ._lib import RgDisturbanceParams
+    if not dist.is_initialized():
+        return disturbance
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = collective_device(device)
+    n = ctypes.sizeof(RgDisturbanceParams)
+    if dist.get_rank() == src:
+        blk = disturbance if disturbance is not None else RgDisturbanceParams()
+        buf = torch.frombuffer(bytearray(ctypes.string_at(ctypes.addressof(blk), n)), dtype=torch.uint8).to(device)
+    else:
+        buf = torch.zeros(n, dtype=torch.uint8, device=device)
+    dist.broadcast(buf, src=src)
+    out = RgDisturbanceParams()
+    ctypes.memmove(ctypes.addressof(out), buf.cpu().numpy().tobytes(), n)
+    return out if (out.sigma_xy != 0.0 or out.sigma_theta != 0.0) else None
 
 
 def broadcast_teams(teams, src=0, device=None):

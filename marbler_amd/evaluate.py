@@ -187,6 +187,9 @@ def policy_rollout(env, actor, T, io, hidden, actions, restart=None, append_agen
         raise ValueError("one launch: an env with a team pool (teams) is not supported; use the two-launch path")
     if getattr(env, "lidar", None) is not None:
         raise ValueError("one launch: an env with the lidar observation (lidar_rays > 0) is not supported; use the two-launch path")
+    if getattr(env, "disturbance", None) is not None:
+        raise ValueError("one launch: an env with the pose disturbance (pose_noise_xy / pose_noise_theta) is not supported; "
+                         "use the two-launch path")
     if not (actor.use_rnn and actor.pack_gru == "f16x2"):
         raise ValueError("one launch: the actor must be a GRU packed as two binary16 planes (pack_gru=True / 'f16x2')")
     if actor.hidden_dim not in (64, 128):
@@ -320,6 +323,9 @@ def run_eval(env, actor, steps, obs_agent_id=True, use_graph=False, fused=None, 
     one_launch: the fused loop with the actor and the env step inside ONE launch per (up to) 64 steps (rg_policy_rollout):
     the same statistics as fused=True bit for bit, and the env left in the same state.  Needs an actor packed as two binary16
     planes and the exact barrier QP; anything else raises ValueError."""
+    if one_launch and getattr(env, "disturbance", None) is not None:
+        raise ValueError("one_launch: an env with the pose disturbance (pose_noise_xy / pose_noise_theta) is not supported; the "
+                         "fused loop evaluates it with two launches per step")
     E, N = env.E, env.N
     dev = env.device
     eye = torch.eye(N, device=dev).unsqueeze(0).expand(E, N, N)

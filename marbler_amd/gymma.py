@@ -279,6 +279,9 @@ class BatchedRunner(object):
         E, N, D, A = v.E, v.n_agents, v.obs_size, v.n_actions
         if int(T) < 1:
             raise ValueError("run(T) collects T >= 1 time steps")
+        if one_launch and getattr(env, "disturbance", None) is not None:
+            raise ValueError("one_launch: an env with the pose disturbance (pose_noise_xy / pose_noise_theta) is not supported; "
+                             "run(T) collects it on the two-launch path")
         out = {"obs": torch.empty(T + 1, E, N, D, device=dev),
                "avail_actions": torch.ones(T + 1, E, N, A, dtype=torch.int32, device=dev),
                "actions": torch.empty(T, E, N, dtype=torch.int32, device=dev),

@@ -12,7 +12,7 @@ import os
 import numpy as np
 import yaml
 
-from ._lib import LIDAR_MAX_RAYS, MAX_AGENTS, MAX_PREY, TEAM_EPISODE, TEAM_FIXED, TEAM_MAX_SETS, RgGrid, RgLidarParams, RgScenarioParams
+from ._lib import DISTURB_MAX_SIGMA_THETA, DISTURB_MAX_SIGMA_XY, LIDAR_MAX_RAYS, MAX_AGENTS, MAX_PREY, TEAM_EPISODE, TEAM_FIXED, TEAM_MAX_SETS, RgDisturbanceParams, RgGrid, RgLidarParams, RgScenarioParams
 
 SCENARIO_IDS = {"PredatorCapturePrey": 0, "Warehouse": 1, "MaterialTransport": 2, "Simple": 3, "ArcticTransport": 4}
 COLLISION_VARIANTS = {"center": 0, "offset": 1}
@@ -281,6 +281,38 @@ def lidar_params(scenario, cfg, params):
     for k in range(rays):
         lp.dir[k][0], lp.dir[k][1] = float(d[k, 0]), float(d[k, 1])
     return lp
+
+
+# ------------------------------------------------------------------ pose disturbance (DESIGN.md "Pose disturbance")
+def disturbance_config(cfg):
+    """(sigma_xy, sigma_theta) of the config keys `pose_noise_xy` (metres, 0..0.1) and `pose_noise_theta` (radians, 0..0.5); both
+    default to 0 = off.  Not part of the reference (its simulated robots are exact): without the keys nothing changes."""
+    out = []
+    for key, hi, unit in (("pose_noise_xy", DISTURB_MAX_SIGMA_XY, "metres"), ("pose_noise_theta", DISTURB_MAX_SIGMA_THETA, "radians")):
+        v = cfg.get(key, 0.0)
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)) \
+                or not 0.0 <= float(v) <= hi:
+            raise ValueError(f"{key} must be a finite number of {unit} in [0, {hi}] (got {v!r})")
+        out.append(float(v))
+    return tuple(out)
+
+
+def disturbance_params(scenario, cfg, params):
+    """The rg_disturbance_params block of a config (None when both `pose_noise_xy` and `pose_noise_theta` are 0 or absent).
+    The disturbance combines with neither the lidar nor a team pool."""
+    if scenario not in SCENARIO_IDS:
+        raise KeyError(f"scenario {scenario!r} is not built (have {sorted(SCENARIO_IDS)})")
+    sxy, sth = disturbance_config(cfg)
+    if sxy == 0.0 and sth == 0.0:
+        return None
+    if lidar_config(cfg)[0] > 0:
+        raise ValueError("pose_noise_xy / pose_noise_theta: the pose disturbance does not combine with the lidar (lidar_rays > 0)")
+    if cfg.get("teams") is not None:
+        raise ValueError("pose_noise_xy / pose_noise_theta: the pose disturbance does not combine with a team pool (teams)")
+    dp = RgDisturbanceParams()
+    # (a bound rounded to binary32 may lie above it -- 0.1 does: the library compares in binary32 too)
+    dp.sigma_xy, dp.sigma_theta = float(np.float32(sxy)), float(np.float32(sth))
+    return dp
 
 
 # ------------------------------------------------------------------ team pool (DESIGN.md "Team pool")

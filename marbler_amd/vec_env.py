@@ -15,7 +15,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .params import TeamPool, lidar_params, load_config, make_params, team_pool
+from .params import TeamPool, disturbance_params, lidar_params, load_config, make_params, team_pool
 
 VIOLATION_MESSAGES = ("", "collision", "boundary", "collision_boundary")  # roboEnv.py:82-94
 
@@ -23,7 +23,7 @@ VIOLATION_MESSAGES = ("", "collision", "boundary", "collision_boundary")  # robo
 class VecRobotariumEnv(object):
     def __init__(self, scenario, num_envs, config_path=None, overrides=None, device="cuda:0", seed=0,
                  env_offset=0, auto_reset=True, reference_reset_obs=True, params=None, collect_qp_stats=False, lidar=None,
-                 teams=None):
+                 teams=None, disturbance=None):
         """scenario: 'PredatorCapturePrey' | 'Warehouse' | 'MaterialTransport' | 'Simple' | 'ArcticTransport'
         (wrapper.py:12-16).
         config_path / overrides: the reference's scenario YAML (same keys) and a dict of overrides.
@@ -38,7 +38,10 @@ class VecRobotariumEnv(object):
             the keys `lidar_rays` / `lidar_range` decide (DESIGN.md "Lidar").
         teams: a params.TeamPool (params.team_pool; dist.broadcast_teams) or the config's `teams` list (sampled per episode), or
             None: from a config the keys `teams` / `team_sampling` decide (DESIGN.md "Team pool").  With a pool every env draws
-            one of its capability sets per episode; `team_index` [E] int32 says which (part of the state)."""
+            one of its capability sets per episode; `team_index` [E] int32 says which (part of the state).
+        disturbance: with `params`, its RgDisturbanceParams (params.disturbance_params; dist.broadcast_disturbance), or None for
+            none.  From a config the keys `pose_noise_xy` / `pose_noise_theta` decide (DESIGN.md "Pose disturbance"): every
+            step then begins by displacing the stored poses by a random amount; it adds no state."""
         self.lib = _lib.load()
         self.scenario = scenario
         self.cfg = None
@@ -49,6 +52,8 @@ class VecRobotariumEnv(object):
                 lidar = lidar_params(scenario, self.cfg, params)
             if teams is None:
                 teams = team_pool(scenario, self.cfg, params)
+            if disturbance is None:
+                disturbance = disturbance_params(scenario, self.cfg, params)
         if lidar is not None and int(lidar.rays) == 0:
             lidar = None
         if teams is not None and not isinstance(teams, TeamPool):
@@ -58,7 +63,14 @@ class VecRobotariumEnv(object):
                 raise ValueError(f"teams: the pool is built for {teams.n_agents} agents, the scenario has {int(params.n_agents)}")
             if lidar is not None:
                 raise ValueError("teams: a team pool does not combine with the lidar (lidar_rays > 0)")
+        if disturbance is not None and float(disturbance.sigma_xy) == 0.0 and float(disturbance.sigma_theta) == 0.0:
+            disturbance = None
+        if disturbance is not None and lidar is not None:
+            raise ValueError("disturbance: the pose disturbance does not combine with the lidar (lidar_rays > 0)")
+        if disturbance is not None and teams is not None:
+            raise ValueError("disturbance: the pose disturbance does not combine with a team pool (teams)")
         self.params = params
+        self.disturbance = disturbance   # RgDisturbanceParams or None: every step displaces the stored poses first
         self.teams = teams   # params.TeamPool or None
         self.lidar = lidar   # RgLidarParams or None: the last lidar.rays columns of every observation row
         self.device = torch.device(device)
@@ -157,6 +169,13 @@ class VecRobotariumEnv(object):
                 self.lib.rg_destroy(self._h)
                 self._h = None
                 raise (ValueError if -70 < rc <= -60 else _lib.RobogymError)(msg)
+        if self.disturbance is not None:
+            rc = self.lib.rg_set_disturbance(self._h, C.byref(self.disturbance))
+            if rc != 0:
+                msg = "rg_set_disturbance failed (%d): %s" % (rc, self.lib.rg_last_error().decode())
+                self.lib.rg_destroy(self._h)
+                self._h = None
+                raise (ValueError if -80 < rc <= -70 else _lib.RobogymError)(msg)
         self._io = _lib.RgStepIO(self.obs.data_ptr(), self.reward.data_ptr(), self.done_u8.data_ptr(),
                                  self.dist_travelled.data_ptr(), self.violation.data_ptr(),
                                  self.remaining.data_ptr(),
