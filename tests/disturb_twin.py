@@ -43,8 +43,10 @@ def displace(poses, seed, env_offset, reset_count, episode_steps, sigma_xy, sigm
     s = np.asarray(episode_steps, np.int64)[:, None]
     c = variates(seed, ge, ep, s, np.arange(N, dtype=np.int64)[None, :])
     kxy, kth = scale(sigma_xy), scale(sigma_theta)
-    out = np.empty_like(poses)
-    out[:, 0] = poses[:, 0] + (kxy * c[0].astype(np.float32)).astype(np.float32)
-    out[:, 1] = poses[:, 1] + (kxy * c[1].astype(np.float32)).astype(np.float32)
-    out[:, 2] = wrap_spec(poses[:, 2] + (kth * c[2].astype(np.float32)).astype(np.float32))
+    out = poses.copy()                       # k = 0 leaves that part of the pose alone: x + 0 * c would turn a -0.0 into +0.0
+    if kxy != 0:
+        out[:, 0] = poses[:, 0] + (kxy * c[0].astype(np.float32)).astype(np.float32)
+        out[:, 1] = poses[:, 1] + (kxy * c[1].astype(np.float32)).astype(np.float32)
+    if kth != 0:
+        out[:, 2] = wrap_spec(poses[:, 2] + (kth * c[2].astype(np.float32)).astype(np.float32))
     return out

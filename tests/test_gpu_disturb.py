@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from disturb_cases import Regime
 from disturb_twin import displace
 from helpers import GPU_NAME, STATE_KEYS
 from test_gpu_actor import _random_actor
@@ -29,9 +30,13 @@ OUT_KEYS = ("obs", "reward", "done_u8", "dist_travelled", "violation", "remainin
 THREADS = max(1, min(16, os.cpu_count() or 1))
 
 
-def _env(scenario, E, ov=None, noise=True, **kw):
+def _noise(sigma):
+    return {"pose_noise_xy": sigma[0], "pose_noise_theta": sigma[1]}
+
+
+def _env(scenario, E, ov=None, noise=True, sigma=(SXY, STH), **kw):
     from marbler_amd.vec_env import VecRobotariumEnv
-    return VecRobotariumEnv(scenario, E, overrides=dict(ov or {}, **(NOISE if noise else {})), device="cuda:0", **kw)
+    return VecRobotariumEnv(scenario, E, overrides=dict(ov or {}, **(_noise(sigma) if noise else {})), device="cuda:0", **kw)
 
 
 def _actions(env, T, seed):
@@ -57,21 +62,26 @@ def _words(a):
     return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint8)
 
 
-def _oracle_step(orc, env, pre, reset_count, acts, displaced=True):
-    """The oracle loaded with the GPU's state `pre`, its poses displaced by the twin, stepped with `acts`."""
+def _oracle_step(orc, env, pre, reset_count, acts, displaced=True, sigma=(SXY, STH), regime=None):
+    """The oracle loaded with the GPU's state `pre`, its poses displaced by the twin, stepped with `acts`.  `regime`
+    (disturb_cases.Regime) is shown the stored and the displaced poses."""
     for k in STATE_KEYS:
         arr = getattr(orc, k)
         arr[...] = pre[k].astype(arr.dtype).reshape(arr.shape)
     if displaced:
-        orc.poses[...] = displace(pre["poses"], env.seed, env.env_offset, reset_count, pre["steps"], SXY, STH)
+        orc.poses[...] = displace(pre["poses"], env.seed, env.env_offset, reset_count, pre["steps"], sigma[0], sigma[1])
+        if regime is not None:
+            regime.see_poses(pre["poses"], orc.poses)
     return orc.step(acts, threads=THREADS)
 
 
-def disturbed_vs_oracle(scenario, ov, solver, E, T, oracle_lib, episode_steps=5, seed=13, env_offset=0):
+def disturbed_vs_oracle(scenario, ov, solver, E, T, oracle_lib, episode_steps=5, seed=13, env_offset=0, sigma=(SXY, STH)):
     """Every step: the GPU's state before the step into the oracle, the oracle's poses displaced by the twin, one step of each;
-    every word of the outputs and -- for envs that did not end (the others were reset) -- of the stored state."""
+    every word of the outputs (the QP's sweep or iteration count among them) and -- for envs that did not end (the others were
+    reset) -- of the stored state.  Returns what it collected: the actions [T, E, N], every output stacked over the steps
+    (`steps`), the stepped handle's final `state_dict` and the oracle's counts (`regime`, a disturb_cases.Regime)."""
     ov = dict(ov, barrier_solver=solver, max_episode_steps=episode_steps)
-    env = _env(scenario, E, ov, seed=seed, env_offset=env_offset)
+    env = _env(scenario, E, ov, sigma=sigma, seed=seed, env_offset=env_offset, collect_qp_stats=True)
     plain = _env(scenario, E, ov, noise=False, seed=seed, env_offset=env_offset)
     assert env.disturbance is not None and plain.disturbance is None and env.step_kernel == "group"
     cfg = {k: v for k, v in env.cfg.items() if k not in NOISE}
@@ -81,15 +91,19 @@ def disturbed_vs_oracle(scenario, ov, solver, E, T, oracle_lib, episode_steps=5,
     assert _same(env.poses, plain.poses)
     acts = _actions(env, T, seed=3)
     acts_np = acts.cpu().numpy()
-    n_done = 0
+    regime = Regime()
+    kept = {k: [] for k in OUT_KEYS + ("qp_sweeps",)}
     for t in range(T):
         pre, rc = _gpu_state(env), env.reset_count.cpu().numpy()
         env.step(acts[t])
         plain.step(acts[t])
-        o_obs, o_rew, o_done, o_info = _oracle_step(orc, env, pre, rc, acts_np[t])
-        got = {k: getattr(env, k).cpu().numpy() for k in OUT_KEYS}
+        o_obs, o_rew, o_done, o_info = _oracle_step(orc, env, pre, rc, acts_np[t], sigma=sigma, regime=regime)
+        regime.see_step(o_done, o_info["violation"], orc.qp_sweeps)
+        for k in kept:
+            kept[k].append(getattr(env, k).clone())
+        got = {k: kept[k][-1].cpu().numpy() for k in kept}
         for k, want in (("done_u8", o_done), ("violation", o_info["violation"]), ("remaining", o_info["remaining"]), ("obs", o_obs),
-                        ("reward", o_rew), ("dist_travelled", o_info["dist_travelled"])):
+                        ("reward", o_rew), ("dist_travelled", o_info["dist_travelled"]), ("qp_sweeps", orc.qp_sweeps)):
             a, b = _words(got[k]), _words(np.asarray(want).astype(got[k].dtype))
             if not np.array_equal(a, b):
                 bad = np.nonzero((a != b).reshape(E, -1).any(axis=1))[0]
@@ -99,11 +113,12 @@ def disturbed_vs_oracle(scenario, ov, solver, E, T, oracle_lib, episode_steps=5,
         for k in STATE_KEYS:
             a, b = post[k][alive], getattr(orc, k)[alive].astype(post[k].dtype).reshape(post[k][alive].shape)
             assert np.array_equal(_words(a), _words(b)), (scenario, solver, t, k)
-        n_done += int(o_done.sum())
-    assert n_done >= E, "every env ends at least one episode inside the run (the draw's episode and step both move)"
+    assert regime.episode_ends >= E, "every env ends at least one episode inside the run (the draw's episode and step both move)"
     assert not _same(env.poses, plain.poses) and not _same(env.obs, plain.obs), "the disturbance changed nothing"
+    result = {"actions": acts, "steps": {k: torch.stack(v) for k, v in kept.items()}, "state": env.state_dict(), "regime": regime}
     env.close()
     plain.close()
+    return result
 
 
 # ---------------------------------------------------------------- 1. / 2. bit parity with the float32 oracle
