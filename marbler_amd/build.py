@@ -15,7 +15,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librobogym_hip.so")
-SOURCES = ["robogym_kernels.hip", "robogym_rollout_group.hip", "robogym_kernels_ipm.hip", "robogym_rollout_group_ipm.hip",
+SOURCES = ["robogym_kernels.hip", "robogym_resident.hip", "robogym_rollout_group.hip", "robogym_kernels_ipm.hip", "robogym_rollout_group_ipm.hip",
            "robogym_tpe.hip", "robogym_rollout_tpe.hip", "robogym_capi.hip", "actor_mfma.hip", "robogym_policy_h64.hip",
            "robogym_policy_h128.hip", "robogym_policy_sample_h64.hip", "robogym_policy_sample_h128.hip", "robogym_lidar.hip", "robogym_lidar_rollout.hip", "robogym_lidar_ipm.hip",
            "robogym_lidar_rollout_ipm.hip", "robogym_team.hip", "robogym_team_rollout.hip", "robogym_team_ipm.hip",
@@ -54,8 +54,16 @@ GROUP_SLP = ["-mllvm", "-slp-threshold=-60"]
 # 12.70 -> 12.74, 32 768 envs 27.1 -> 29.0: NOT for the other files).  The one-lane-per-env interior-point kernels stay with the
 # default strategy: under max-ILP the N = 5 one shows the exec-prologue shape isa_scan looks for.
 IPM_SCHED = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
+# The resident form of the row kernels (robogym_resident.hip; kernel_args.h ResidentCall): its leading kernel arguments -- the
+# image's address, the actions, the seed, auto_reset, the grid: 8 dwords; the hidden grid size lies behind the by-value rg_step_io
+# and would not be among them -- are handed to a wave in scalar registers by the command processor instead of being fetched from the argument
+# segment, which a host launch has just written.  The flag asks for up to 16 dwords and the compiler takes what precedes the
+# first by-value struct; it changes every kernel of a translation unit it is given to, hence a file of its own.
+# tools/ubench/resident_args.py priced it (profiles/resident_args_ubench.txt).
+RESIDENT_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 FILE_FLAGS = {"robogym_tpe.hip": ["-fno-slp-vectorize"], "robogym_rollout_tpe.hip": ["-fno-slp-vectorize"],
               "robogym_kernels.hip": GROUP_SLP, "robogym_rollout_group.hip": GROUP_SLP,
+              "robogym_resident.hip": GROUP_SLP + RESIDENT_PRELOAD,
               "robogym_kernels_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_rollout_group_ipm.hip": GROUP_SLP + IPM_SCHED,
               "robogym_policy_h64.hip": GROUP_SLP, "robogym_policy_h128.hip": GROUP_SLP,
               "robogym_policy_sample_h64.hip": GROUP_SLP, "robogym_policy_sample_h128.hip": GROUP_SLP,

@@ -102,15 +102,58 @@ __device__ __forceinline__ float swap_halves(float v) {
 // one scalar-memory round trip in front of the instruction that needs it.  The 16-lane-row kernels therefore fetch the whole
 // block ONCE more with vector loads at their very start -- dword i of the block in lane i % 64 of register i / 64 -- and read a
 // value where it is needed with v_readlane_b32: one instruction, no wait (the loads return long before the epilogue).
-constexpr int ARG_REGS = 4;
-static_assert(sizeof(KernelArgs) <= ARG_REGS * 64 * 4 && sizeof(KernelArgs) % 4 == 0, "the argument block fits four registers of dwords");
+constexpr int BLOCK_REGS = 4;
+constexpr int ARG_REGS = BLOCK_REGS + 1;   // the fifth: the per-call arguments of the resident form (below), unused otherwise
+static_assert(sizeof(KernelArgs) <= BLOCK_REGS * 64 * 4 && sizeof(KernelArgs) % 4 == 0, "the argument block fits four registers of dwords");
 __device__ __forceinline__ void load_arg_regs(const KernelArgs &a, int lane, int (&av)[ARG_REGS]) {
     constexpr int DW = static_cast<int>(sizeof(KernelArgs) / 4);
 #pragma unroll
-    for (int c = 0; c < ARG_REGS; ++c) {
+    for (int c = 0; c < BLOCK_REGS; ++c) {
         const int i = c * 64 + lane;
         av[c] = reinterpret_cast<const int *>(&a)[i < DW ? i : DW - 1];   // (clamped: no lane reads past the block)
     }
+}
+#ifndef RG_HOST_SIM
+// The resident form (kernel_args.h ResidentCall): `a` is the handle's image, and the per-call arguments lie in the kernel-argument
+// segment, whose dwords go into the fifth register.  resident_arg_off maps a per-call member's offset in the block to its place
+// there (byte 1024 on), so that RG_ARG / RG_OUT read either with the same v_readlane_b32.
+__device__ __forceinline__ void load_arg_regs_resident(const KernelArgs &a, int lane, int (&av)[ARG_REGS]) {
+    load_arg_regs(a, lane, av);
+    constexpr int DW = static_cast<int>(sizeof(ResidentCall) / 4);
+    typedef const __attribute__((address_space(4))) int *Seg;
+    av[BLOCK_REGS] = ((Seg)__builtin_amdgcn_kernarg_segment_ptr())[lane < DW ? lane : DW - 1];   // (clamped: no lane reads past the arguments)
+}
+#else
+inline void load_arg_regs_resident(const KernelArgs &a, int lane, int (&av)[ARG_REGS]) { load_arg_regs(a, lane, av); }   // (never instantiated there)
+#endif
+#ifndef RG_HOST_SIM
+// the image once more, through an opaque copy of its address (in the constant address space, like the first)
+__device__ __forceinline__ const KernelArgs &reopened_image(const KernelArgs &a) {
+    typedef const __attribute__((address_space(4))) KernelArgs *ConstImage;
+    ConstImage ci = (ConstImage)&a;
+    asm volatile("" : "+s"(ci));
+    return *(const KernelArgs *)ci;
+}
+#else
+inline const KernelArgs &reopened_image(const KernelArgs &a) { return a; }
+#endif
+constexpr unsigned resident_arg_off(unsigned off) {
+    constexpr unsigned SEG = BLOCK_REGS * 256;
+    return off >= offsetof(KernelArgs, io) && off < offsetof(KernelArgs, io) + sizeof(rg_step_io) ? SEG + offsetof(ResidentCall, io) + (off - offsetof(KernelArgs, io))
+           : off >= offsetof(KernelArgs, actions) && off < offsetof(KernelArgs, actions) + 8 ? SEG + offsetof(ResidentCall, actions) + (off - offsetof(KernelArgs, actions))
+           : off >= offsetof(KernelArgs, seed) && off < offsetof(KernelArgs, seed) + 8       ? SEG + offsetof(ResidentCall, seed) + (off - offsetof(KernelArgs, seed))
+           : off == offsetof(KernelArgs, auto_reset)                                         ? SEG + offsetof(ResidentCall, auto_reset)
+                                                                                             : off;
+}
+// a pointer as a GLOBAL one (for the compiler: the same address)
+template <typename T>
+__device__ __forceinline__ T *as_global(T *p) {
+#ifdef __HIP_DEVICE_COMPILE__
+    typedef __attribute__((address_space(1))) T *GlobalPtr;
+    return (T *)(GlobalPtr)p;
+#else
+    return p;
+#endif
 }
 // the argument at byte offset `off` of the block (a constant where this is inlined).  A pointer is rebuilt as a GLOBAL one first:
 // read back from registers, the compiler can no longer tell by itself, and would store through it with flat instructions.
@@ -424,9 +467,11 @@ __device__ __forceinline__ ResetDst reset_dst_next(const KernelArgs &a, int e) {
 
 // episode_pre >= 0: the env's reset_count, already fetched by the caller (the step kernels prefetch it with the rest of
 // the state, so a finished env's reset does not start with a memory round trip of its own)
-template <int SCN, int GW, typename Sync = WgSync>
+// seed: where the launch's seed lies (the step kernels: StepView::seed); OWN_SEED: the block's own member, read where it is used
+template <int SCN, int GW, typename Sync = WgSync, bool OWN_SEED = false>
 __device__ __forceinline__ void reset_group(const KernelArgs &a, Lds<GW> &lds, int e, int g, int ag, bool do_reset,
-                                            int episode_pre, const ResetDst &dst) {
+                                            int episode_pre, const ResetDst &dst, const uint64_t *seed) {
+#define RG_SEED (OWN_SEED ? a.seed : *seed)
     const rg_scenario_params &p = a.p;
     const int N = p.n_agents;
     if constexpr (SCN == RG_SCN_ARCTIC_TRANSPORT) {
@@ -442,7 +487,7 @@ __device__ __forceinline__ void reset_group(const KernelArgs &a, Lds<GW> &lds, i
                 uint32_t blk[4];
                 philox4x32_10(static_cast<uint32_t>(ge), static_cast<uint32_t>(ge >> 32),
                               static_cast<uint32_t>(episode), static_cast<uint32_t>(b),
-                              static_cast<uint32_t>(a.seed), static_cast<uint32_t>(a.seed >> 32), blk);
+                              static_cast<uint32_t>(RG_SEED), static_cast<uint32_t>(RG_SEED >> 32), blk);
 #pragma unroll
                 for (int t = 0; t < 4; ++t) lds.draws[g][4 * b + t] = blk[t];
             }
@@ -489,7 +534,7 @@ __device__ __forceinline__ void reset_group(const KernelArgs &a, Lds<GW> &lds, i
         for (int b = ag; 4 * b < ndraws; b += GW) {
             uint32_t blk[4];
             philox4x32_10(static_cast<uint32_t>(ge), static_cast<uint32_t>(ge >> 32), static_cast<uint32_t>(episode),
-                          static_cast<uint32_t>(b), static_cast<uint32_t>(a.seed), static_cast<uint32_t>(a.seed >> 32),
+                          static_cast<uint32_t>(b), static_cast<uint32_t>(RG_SEED), static_cast<uint32_t>(RG_SEED >> 32),
                           blk);
             lds.draws[g][4 * b + 0] = blk[0];
             lds.draws[g][4 * b + 1] = blk[1];
@@ -542,13 +587,20 @@ __device__ __forceinline__ void reset_group(const KernelArgs &a, Lds<GW> &lds, i
         a.st.reset_count[e] = episode + 1;
         a.st.episode_steps[e] = 0;
     }
+#undef RG_SEED
 }
 
 // the draw straight into the env's state: scenario.reset()
 template <int SCN, int GW, typename Sync = WgSync>
 __device__ __forceinline__ void reset_group(const KernelArgs &a, Lds<GW> &lds, int e, int g, int ag, bool do_reset,
                                             int episode_pre = -1) {
-    reset_group<SCN, GW, Sync>(a, lds, e, g, ag, do_reset, episode_pre, reset_dst_state(a, e));
+    reset_group<SCN, GW, Sync, true>(a, lds, e, g, ag, do_reset, episode_pre, reset_dst_state(a, e), nullptr);
+}
+// ... under the seed at `seed` (the step kernels: StepView::seed)
+template <int SCN, int GW, typename Sync = WgSync>
+__device__ __forceinline__ void reset_group(const KernelArgs &a, Lds<GW> &lds, int e, int g, int ag, bool do_reset,
+                                            int episode_pre, const uint64_t *seed) {
+    reset_group<SCN, GW, Sync>(a, lds, e, g, ag, do_reset, episode_pre, reset_dst_state(a, e), seed);
 }
 
 }  // namespace rg

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <type_traits>
@@ -118,9 +119,10 @@ hipError_t launch_reset(const KernelArgs &a, hipStream_t stream);
 // An observation-only launch (rg_get_obs) runs no controller: it exists in the exact mode only and serves both.  The disturbance
 // family has none: rg_get_obs displaces nothing, and a disturbed handle's goes to the plain entry.
 enum GroupFamily { GROUP_PLAIN, GROUP_LIDAR, GROUP_TEAM, GROUP_DISTURB };
-enum GroupKind { GROUP_STEP, GROUP_ROLLOUT, GROUP_OBS };
+enum GroupKind { GROUP_STEP, GROUP_ROLLOUT, GROUP_OBS, GROUP_STEP_RESIDENT };
 #define RG_GROUP_ENTRIES(X)                                              \
     X(launch_step, GROUP_PLAIN, RG_QP_EXACT, GROUP_STEP)                 \
+    X(launch_step_resident, GROUP_PLAIN, RG_QP_EXACT, GROUP_STEP_RESIDENT) \
     X(launch_obs, GROUP_PLAIN, RG_QP_EXACT, GROUP_OBS)                   \
     X(launch_rollout, GROUP_PLAIN, RG_QP_EXACT, GROUP_ROLLOUT)           \
     X(launch_step_ipm, GROUP_PLAIN, RG_QP_CVXOPT, GROUP_STEP)            \
@@ -151,7 +153,26 @@ struct GroupSide {
     const rg_lidar_params *lidar;
     const rg_team_params *teams;
     const DisturbScale *disturb;
+    const struct KernelArgs *image;   // the handle's resident image on the device (below), or null: the launch goes by value
 };
+
+// The resident form of the 16-lane-row step kernels (robogym_resident.hip).  What rg_create / rg_bind_state fix -- p, k, st, E,
+// envs_per_wave as the dispatcher computes it, next_stride, env_offset -- lies in an IMAGE of the block in device memory that the
+// handle owns, written where one of them changes and never again once a launch may read it (a change takes a fresh slot), and
+// the kernel takes the image's address and the per-call arguments alone: 136 bytes of kernel arguments instead of 0.8 KB, the
+// leading ones handed over in scalar registers (build.py RESIDENT_PRELOAD).  GROUP_STEP_RESIDENT is the dispatcher's own kind
+// (step_group.h launch_gw calls it where it chooses rows and has an image); rg_step never asks for it.
+struct ResidentCall {   // the kernel-argument segment of a resident kernel (its parameters in this order)
+    const KernelArgs *image;
+    const int32_t *actions;
+    uint64_t seed;
+    int32_t auto_reset;
+    int32_t grid;   // the launch's grid (behind a by-value struct the hidden grid size is not among the preloaded arguments)
+    rg_step_io io;
+};
+static_assert(sizeof(ResidentCall) <= 256, "the per-call arguments fit one register of dwords (device_common.h load_arg_regs_resident)");
+// the image of a handle's block: the per-call members cleared, envs_per_wave as launch_group sets it
+hipError_t resident_image(KernelArgs &a);
 typedef hipError_t GroupLaunch(const KernelArgs &a, const GroupSide &side, hipStream_t stream);
 #define RG_X(entry, family, mode, kind) GroupLaunch entry;
 RG_GROUP_ENTRIES(RG_X)
@@ -161,6 +182,10 @@ RG_GROUP_ENTRIES(RG_X)
 struct StepView {
     const int32_t *actions;
     rg_step_io io;
+    // the launch's other per-call arguments, where they lie (the block's own members, except in the resident form below)
+    const int32_t *auto_reset;
+    const uint64_t *seed;
+    int32_t grid;   // resident form: the launch's grid (0: gridDim.x)
 };
 __host__ __device__ inline StepView step_view(const KernelArgs &a, int k, int n_agents, int obs_dim) {
     StepView v;
@@ -179,6 +204,9 @@ __host__ __device__ inline StepView step_view(const KernelArgs &a, int k, int n_
     v.io.reward_sum = a.io.reward_sum ? a.io.reward_sum + e : nullptr;
     v.io.time_limit = a.io.time_limit;
     v.io.zero_obs_on_end = a.io.zero_obs_on_end;
+    v.auto_reset = &a.auto_reset;
+    v.seed = &a.seed;
+    v.grid = 0;
     return v;
 }
 // thread-per-env step kernel (robogym_tpe.hip): same results, chosen by the host for large batches

@@ -31,7 +31,25 @@ struct rg_handle {
     bool disturbed;          // the pose disturbance is on (rg_set_disturbance), with the scales below
     rg::DisturbScale disturb;
     bool span;           // rg_step's lane-group launch may put an env on a 16-lane row (step_group.h); RG_STEP_SPAN=0 forces 8-lane groups
+    // The resident image of the argument block (kernel_args.h ResidentCall): what rg_create / rg_bind_state fix, in device memory
+    // of the handle's device, for the resident form of the row kernels.  An image is IMMUTABLE once written: a launch -- or a
+    // captured graph that replays one -- may read it at any later time.  Whatever alters it (a re-bind; rg_set_*) makes the
+    // current one stale, and the next one is written into a fresh slot; the slots live until rg_destroy.  No valid image (the
+    // slots used up, no memory, a write due while the stream is being captured, RG_STEP_RESIDENT=0): the launch goes by value.
+    bool resident;               // RG_STEP_RESIDENT=0 at rg_create: by-value launches only
+    rg::KernelArgs *image_slots; // device: RG_IMAGE_SLOTS slots of RG_IMAGE_STRIDE bytes (allocated with the first image)
+    int32_t images_used;
+    const rg::KernelArgs *image; // the image of the handle as it is now, or null
+    bool image_stale;            // the handle has changed since `image` was written (or none was written yet)
 };
+constexpr int RG_IMAGE_SLOTS = 8;
+constexpr size_t RG_IMAGE_STRIDE = 1024;
+static_assert(sizeof(rg::KernelArgs) <= RG_IMAGE_STRIDE, "an image slot holds the block");
+static void write_image(rg_handle *h);
+static void drop_image(rg_handle *h) {   // the handle changes: its image no longer describes it
+    h->image = nullptr;
+    h->image_stale = true;
+}
 
 // Which step kernel: both give identical results.  The lane-group kernel has the shorter chain for
 // small batches and is linear in the batch; the thread-per-env kernel's time is a step function of how many
@@ -152,6 +170,7 @@ hipError_t launch_policy_rollout_sample_h128(const KernelArgs &, const rg_actor_
 RG_GROUP_ENTRIES(RG_X)
 #undef RG_X
 hipError_t launch_team_index(const KernelArgs &, const rg_team_params &, hipStream_t) __attribute__((weak));
+hipError_t resident_image(KernelArgs &) __attribute__((weak));
 }  // namespace rg
 
 // The scenario's own observation width: the columns its builder writes (the lidar block may start at or after it).
@@ -247,6 +266,14 @@ rg_handle *rg_create(const rg_scenario_params *params, int32_t num_envs, int64_t
         const char *span = getenv("RG_STEP_SPAN");
         h->span = !(span && !strcmp(span, "0"));
     }
+    {
+        const char *res = getenv("RG_STEP_RESIDENT");
+        h->resident = !(res && !strcmp(res, "0")) && rg::resident_image && rg::launch_step_resident;
+    }
+    h->image_slots = nullptr;
+    h->images_used = 0;
+    h->image = nullptr;
+    h->image_stale = true;
     memset(&h->lidar, 0, sizeof(h->lidar));
     memset(&h->teams, 0, sizeof(h->teams));
     h->disturbed = false;
@@ -259,6 +286,7 @@ int rg_set_lidar(rg_handle *h, const rg_lidar_params *lp) {
     if (!lp || lp->rays == 0) {
         memset(&h->lidar, 0, sizeof(h->lidar));
         h->use_tpe = (h->teams.n_sets || h->disturbed) ? false : h->default_tpe;
+        drop_image(h);
         return 0;
     }
     if (h->disturbed) return fail(-57, "rg_set_lidar: the handle has the pose disturbance on (rg_set_disturbance); the disturbance and the lidar do not combine");
@@ -273,6 +301,7 @@ int rg_set_lidar(rg_handle *h, const rg_lidar_params *lp) {
     if (!group_family_built(rg::GROUP_LIDAR)) return fail(-100, "rg_set_lidar: this build has no lidar kernels");
     h->lidar = *lp;
     h->use_tpe = false;   // the lidar is built into the lane-group kernel only
+    drop_image(h);
     return 0;
 }
 
@@ -282,6 +311,7 @@ int rg_set_disturbance(rg_handle *h, const rg_disturbance_params *dp) {
         h->disturbed = false;
         h->disturb = rg::DisturbScale{0.0f, 0.0f};
         h->use_tpe = (h->lidar.rays || h->teams.n_sets) ? false : h->default_tpe;
+        drop_image(h);
         return 0;
     }
     // (a NaN fails both comparisons)
@@ -295,11 +325,16 @@ int rg_set_disturbance(rg_handle *h, const rg_disturbance_params *dp) {
     h->disturb = rg::DisturbScale{rg::disturb_scale(dp->sigma_xy), rg::disturb_scale(dp->sigma_theta)};
     h->disturbed = true;
     h->use_tpe = false;   // the disturbance is built into the lane-group kernel only
+    drop_image(h);
     return 0;
 }
 
 int rg_destroy(rg_handle *h) {
     if (!h) return fail(-1, "handle is NULL");
+    if (h->image_slots) {
+        DeviceGuard guard(h->device);
+        if (guard.err == hipSuccess) (void)hipFree(h->image_slots);
+    }
     delete h;
     return 0;
 }
@@ -342,10 +377,64 @@ int rg_bind_state(rg_handle *h, const rg_state *st) {
     if (reinterpret_cast<uintptr_t>(st->next_init) & 15u) return fail(-26, "next_init must be 16-byte aligned");
     h->state = *st;
     h->bound = true;
+    drop_image(h);
+    write_image(h);   // (no image is no error: the steps go by value until one can be written)
     // whatever the rebound next_init / next_episode arrays hold was not drawn by this handle under a seed it knows:
     // the first rg_step / rg_rollout after a bind marks every block stale (sync_seed), whatever the caller put there
     h->seed_seen = false;
     return 0;
+}
+
+static int fill_args(rg_handle *h, rg::KernelArgs &a);
+#define RG_ON_DEVICE(h)                                                                           \
+    DeviceGuard guard_((h)->device);                                                              \
+    if (guard_.err != hipSuccess) return fail(-31, "cannot select the handle's device: %s", hipGetErrorString(guard_.err))
+
+// Writes the handle's image into a fresh slot, if it may use the resident form at all.  Called where the handle changes
+// (rg_bind_state) and, while the image is stale, by rg_step: a write that could not be made then is made by the first step
+// that can.  Synchronous (hipMemcpy from host memory: the image is on the device when this returns), so never while the handle's
+// stream is being captured.  Leaves h->image null where there is none: never an error.
+static void write_image(rg_handle *h) {
+    h->image = nullptr;
+    if (!h->resident || !h->bound || h->use_tpe || !h->span || h->teams.n_sets || h->lidar.rays || h->disturbed ||
+        h->params.qp_mode != RG_QP_EXACT) {
+        h->image_stale = false;   // no row kernel serves this handle as it is; a change marks it stale again
+        return;
+    }
+    if (h->images_used >= RG_IMAGE_SLOTS) {
+        h->image_stale = false;   // the slots are used up: by value from here on
+        return;
+    }
+    rg::KernelArgs a;
+    if (fill_args(h, a) != 0 || rg::resident_image(a) != hipSuccess) {
+        h->image_stale = false;   // (not a shape of the row kernels)
+        return;
+    }
+    DeviceGuard guard(h->device);
+    if (guard.err != hipSuccess) return;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(h->stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return;   // stays stale: written by the first step outside the capture
+    }
+    if (!h->image_slots) {
+        void *mem = nullptr;
+        if (hipMalloc(&mem, RG_IMAGE_SLOTS * RG_IMAGE_STRIDE) != hipSuccess) {
+            (void)hipGetLastError();
+            h->images_used = RG_IMAGE_SLOTS;   // no memory: by value
+            h->image_stale = false;
+            return;
+        }
+        h->image_slots = static_cast<rg::KernelArgs *>(mem);
+    }
+    rg::KernelArgs *slot = reinterpret_cast<rg::KernelArgs *>(reinterpret_cast<char *>(h->image_slots) + RG_IMAGE_STRIDE * h->images_used);
+    h->images_used += 1;   // (a slot whose write failed is not used again either)
+    h->image_stale = false;
+    if (hipMemcpy(slot, &a, sizeof(a), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+    }
+    h->image = slot;
 }
 
 static int fill_args(rg_handle *h, rg::KernelArgs &a) {
@@ -395,19 +484,15 @@ static int launched(hipError_t err) {
 // The lane-group launch of a handle: the family its side blocks select (a pool, the lidar and the disturbance exclude one
 // another), the handle's solver mode -- an observation-only launch runs no controller and uses the exact mode's kernel in either,
 // and displaces nothing: a disturbed handle's is the plain family's -- and the launch kind.
-static int launch_group_entry(const rg_handle *h, const rg::KernelArgs &a, int kind) {
+static int launch_group_entry(const rg_handle *h, const rg::KernelArgs &a, int kind, const rg::KernelArgs *image = nullptr) {
     const int family = h->teams.n_sets ? rg::GROUP_TEAM : h->lidar.rays ? rg::GROUP_LIDAR
                        : (h->disturbed && kind != rg::GROUP_OBS) ? rg::GROUP_DISTURB : rg::GROUP_PLAIN;
     const int mode = kind == rg::GROUP_OBS ? RG_QP_EXACT : h->params.qp_mode;
-    const rg::GroupSide side = {&h->lidar, &h->teams, &h->disturb};
+    const rg::GroupSide side = {&h->lidar, &h->teams, &h->disturb, family == rg::GROUP_PLAIN ? image : nullptr};
     for (const GroupEntry &g : g_group)
         if (g.family == family && g.mode == mode && g.kind == kind && g.launch) return launched(g.launch(a, side, h->stream));
     return fail(-100, "this build has no lane-group step kernels");
 }
-
-#define RG_ON_DEVICE(h)                                                                           \
-    DeviceGuard guard_((h)->device);                                                              \
-    if (guard_.err != hipSuccess) return fail(-31, "cannot select the handle's device: %s", hipGetErrorString(guard_.err))
 
 int rg_reset(rg_handle *h, const uint8_t *mask, uint64_t seed, int32_t flags) {
     rg::KernelArgs a;
@@ -437,7 +522,9 @@ int rg_step(rg_handle *h, const int32_t *actions, const rg_step_io *io, int32_t 
     // (asks the plain family's dispatcher for 8-lane groups throughout: it sets the real value itself)
     if (!h->span && !h->teams.n_sets && !h->lidar.rays && !h->disturbed) a.envs_per_wave = -1;
     if (h->use_tpe) return launched(rg::launch_step_tpe(a, h->stream));
-    return launch_group_entry(h, a, rg::GROUP_STEP);
+    if (h->image_stale) write_image(h);
+    // (the dispatcher takes the resident form where it chooses rows; the gymma block has kernels of its own)
+    return launch_group_entry(h, a, rg::GROUP_STEP, io->elapsed ? nullptr : h->image);
 }
 
 int rg_rollout(rg_handle *h, const int32_t *actions, int32_t num_steps, const rg_step_io *io, int32_t auto_reset,
@@ -534,6 +621,7 @@ int rg_set_teams(rg_handle *h, const rg_team_params *tp) {
     if (!tp || tp->n_sets == 0) {
         memset(&h->teams, 0, sizeof(h->teams));
         h->use_tpe = (h->lidar.rays || h->disturbed) ? false : h->default_tpe;
+        drop_image(h);
         return 0;
     }
     if (h->disturbed) return fail(-65, "rg_set_teams: the handle has the pose disturbance on (rg_set_disturbance); the disturbance and a pool do not combine");
@@ -557,6 +645,7 @@ int rg_set_teams(rg_handle *h, const rg_team_params *tp) {
     }
     h->teams = *tp;
     h->use_tpe = false;   // the pool is built into the lane-group kernel only
+    drop_image(h);
     return 0;
 }
 

@@ -415,12 +415,13 @@ __device__ __forceinline__ void write_neighbour_obs(Lds<GW> &lds, int N, int Knb
 // NOISE: the pose disturbance of `nz` (disturb.h): the step begins by displacing the poses it has just loaded.  Its own
 // instantiations (disturb_step_kernel).
 template <int SCN, int GW, bool OBS_ONLY, int NT, bool AHEAD, bool GYM, int QPM = 0, typename QpLds = void, typename Sync = WgSync,
-          bool LIDAR = false, bool TEAM = false, bool SPAN = false, bool NOISE = false>
+          bool LIDAR = false, bool TEAM = false, bool SPAN = false, bool NOISE = false, bool RES = false>
 __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, const StepView &sv, QpLds *qp_lds = nullptr,
                                           const rg_lidar_params *lid = nullptr, const rg_team_params *tm = nullptr,
                                           const DisturbScale *nz = nullptr) {
     static_assert(!SPAN || (GW == 8 && QPM == 0 && !GYM && !LIDAR && !TEAM && !NOISE), "the 16-lane rows: exact mode, GW = 8, no side blocks");
     static_assert(!NOISE || !OBS_ONLY, "an observation-only launch displaces nothing");
+    static_assert(!RES || (SPAN && RG_ROW_ARG_REGS != 0), "the resident form: the 16-lane rows, arguments in vector registers");
     constexpr int RW = SPAN ? 2 * GW : GW;  // lanes per env
     constexpr int EPW = WAVE / RW;  // envs per wave
     RG_STAMPS_BEGIN()
@@ -432,9 +433,13 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     // RG_ARG_OR(a.x, q): the same for an argument the prologue holds as q.  (Macros, and a conditional on a constant, of which
     // the compiler emits the live side only: every other kernel is compiled from the plain member access, as before.)
     constexpr bool ARGV = SPAN && RG_ROW_ARG_REGS != 0;
-    int av[ARG_REGS] = {0, 0, 0, 0};
-    if constexpr (ARGV) load_arg_regs(a, threadIdx.x, av);
-#define RG_ARG_OFF(f) static_cast<unsigned>(reinterpret_cast<const char *>(&(f)) - reinterpret_cast<const char *>(&a))
+    // RES (the resident form, kernel_args.h): `a` is the handle's image, read like the kernel arguments, and the per-call arguments
+    // come through `sv`; in the registers they are the fifth (device_common.h resident_arg_off).
+    int av[ARG_REGS] = {0, 0, 0, 0, 0};
+    if constexpr (RES) load_arg_regs_resident(a, threadIdx.x, av);
+    else if constexpr (ARGV) load_arg_regs(a, threadIdx.x, av);
+#define RG_ARG_BLOCK_OFF(f) static_cast<unsigned>(reinterpret_cast<const char *>(&(f)) - reinterpret_cast<const char *>(&a))
+#define RG_ARG_OFF(f) (RES ? resident_arg_off(RG_ARG_BLOCK_OFF(f)) : RG_ARG_BLOCK_OFF(f))
 #define RG_ARG(f) (ARGV ? arg_reg<std::decay_t<decltype(f)>>(av, RG_ARG_OFF(f)) : (f))
 #define RG_ARG_OR(f, q) (ARGV ? arg_reg<std::decay_t<decltype(q)>>(av, RG_ARG_OFF(f)) : (q))
 #define RG_OUT(m) (ARGV ? arg_reg<std::decay_t<decltype(sv.io.m)>>(av, RG_ARG_OFF(a.io.m)) : (sv.io.m))
@@ -444,26 +449,34 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     };
     static_assert(offsetof(KernelArgs, p.torque) / 256 == (offsetof(KernelArgs, p.torque) + sizeof(rg_scenario_params::torque) - 1) / 256,
                   "arg_elem(p.torque, j): the table lies in one of the argument registers");
+    // RG_IMG(ptr): a pointer read from the block with scalar loads.  Of one that was a kernel argument the compiler knows that it
+    // is a global one; of one read from the resident image it has to be told, or every access through it is a flat one.
+#define RG_IMG(ptr) (RES ? as_global(ptr) : (ptr))
+    // RG_SAMPLER_ARGS: the block as the sampler's calls get it.  The image through an address the compiler cannot see through: it
+    // would otherwise merge the sampler's loads of the state pointers with the prologue's, keep those values across the whole
+    // kernel, and -- at the scalar-register limit -- fetch them again inside the sub-step loop.  (Kernel arguments become loads too
+    // late for that merge.)
+#define RG_SAMPLER_ARGS (RES ? reopened_image(a) : (a))
     // ---- kernel arguments first: every pointer and scalar the loads below need, fetched TOGETHER.  Left to itself
     // the compiler fetches each kernarg field where it is first used: five dependent scalar-memory round trips, the
     // state loads issued in between and waited for one group at a time -- 3.3 k of a wave's 24 k cycles went by
     // before the first controller (tools/stamp_probe.py).  The empty asm makes all of them live here: one trip.
-    const float *q_poses = a.st.poses, *q_carry = a.st.carry_dist, *q_ret = a.st.ep_return, *q_sum = a.st.done_return_sum;
-    const int32_t *q_steps = a.st.episode_steps, *q_act = sv.actions, *q_cnt = a.st.done_count, *q_stp = a.st.done_steps_sum;
+    const float *q_poses = RG_IMG(a.st.poses), *q_carry = RG_IMG(a.st.carry_dist), *q_ret = RG_IMG(a.st.ep_return), *q_sum = RG_IMG(a.st.done_return_sum);
+    const int32_t *q_steps = RG_IMG(a.st.episode_steps), *q_act = sv.actions, *q_cnt = RG_IMG(a.st.done_count), *q_stp = RG_IMG(a.st.done_steps_sum);
     int32_t *q_el = GYM ? sv.io.elapsed : nullptr;  // gymma block (gym TimeLimit's counter)
     const int q_tl = GYM ? sv.io.time_limit : 0;
-    const int32_t *q_rc = a.st.reset_count, *q_nep = AHEAD ? a.st.next_episode : nullptr;
-    const float *q_nin = AHEAD ? a.st.next_init : nullptr;
+    const int32_t *q_rc = RG_IMG(a.st.reset_count), *q_nep = AHEAD ? RG_IMG(a.st.next_episode) : nullptr;
+    const float *q_nin = AHEAD ? RG_IMG(a.st.next_init) : nullptr;
     const int q_nst = AHEAD ? a.next_stride : 0;
-    const int q_E = a.E, q_epw = a.envs_per_wave, q_P = p.num_prey, q_N = p.n_agents, q_G = gridDim.x;
+    const int q_E = a.E, q_epw = a.envs_per_wave, q_P = p.num_prey, q_N = p.n_agents, q_G = RES ? sv.grid : gridDim.x;
     asm volatile("" ::"s"(q_poses), "s"(q_carry), "s"(q_ret), "s"(q_sum), "s"(q_steps), "s"(q_act), "s"(q_cnt), "s"(q_stp),
                  "s"(q_E), "s"(q_epw), "s"(q_P), "s"(q_N), "s"(q_G), "s"(q_rc));
     if constexpr (GYM) asm volatile("" ::"s"(q_el), "s"(q_tl));
     if constexpr (AHEAD) asm volatile("" ::"s"(q_nep), "s"(q_nin), "s"(q_nst));
-    const float *q_prey = a.st.prey_loc;
-    const uint8_t *q_sen = a.st.prey_sensed, *q_cap = a.st.prey_captured, *q_loaded = a.st.loaded, *q_grid = a.st.grid;
-    const uint8_t *q_pix = a.st.pixel_type, *q_reached = a.st.reached_goal;
-    const int32_t *q_gcol = a.st.goal_col, *q_msg = a.st.messages, *q_zone = a.st.zone_load, *q_load = a.st.load;
+    const float *q_prey = RG_IMG(a.st.prey_loc);
+    const uint8_t *q_sen = RG_IMG(a.st.prey_sensed), *q_cap = RG_IMG(a.st.prey_captured), *q_loaded = RG_IMG(a.st.loaded), *q_grid = RG_IMG(a.st.grid);
+    const uint8_t *q_pix = RG_IMG(a.st.pixel_type), *q_reached = RG_IMG(a.st.reached_goal);
+    const int32_t *q_gcol = RG_IMG(a.st.goal_col), *q_msg = RG_IMG(a.st.messages), *q_zone = RG_IMG(a.st.zone_load), *q_load = RG_IMG(a.st.load);
     if constexpr (SCN == RG_SCN_PREDATOR_CAPTURE_PREY) asm volatile("" ::"s"(q_prey), "s"(q_sen), "s"(q_cap));
     else if constexpr (SCN == RG_SCN_WAREHOUSE) asm volatile("" ::"s"(q_loaded));
     else if constexpr (SCN == RG_SCN_SIMPLE) asm volatile("" ::"s"(q_prey));
@@ -560,7 +573,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     // the sampler (Philox, Fisher-Yates through LDS: ~2 k cycles at the very end of the launch's critical path).
     // Only the block's tag is fetched here (4 bytes per env); the block itself is fetched for the few envs that end
     // (load_next below), early enough to hide its latency behind the epilogue.
-    const bool ahead = AHEAD && (!OBS_ONLY) && q_nst > 0 && a.auto_reset;
+    const bool ahead = AHEAD && (!OBS_ONLY) && q_nst > 0 && *sv.auto_reset;
     int nx_tag = -2;                               // episode the block was drawn for
     float nx_pose[3] = {0.0f, 0.0f, 0.0f};         // this lane's agent
     float nx_a = 0.0f, nx_b = 0.0f;                // PCP / Simple: prey `ag` (x, y); MaterialTransport: zone load `ag` (bits)
@@ -591,7 +604,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     int el_raw = 0;
     if (env_ok) {
         steps_raw = q_steps[e];
-        if (!OBS_ONLY && a.auto_reset) rc_raw = q_rc[e];
+        if (!OBS_ONLY && *sv.auto_reset) rc_raw = q_rc[e];
         if constexpr (GYM) el_raw = q_el[e];
         if (ahead) nx_tag = q_nep[e];
         if (stats && ag == 0) {
@@ -1512,7 +1525,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         if (RG_ARG(a.auto_reset) && __any(env_ok & ended)) {
             Sync::sync();  // the wave's state stores are issued before the resetting lanes rewrite them
             if constexpr (AHEAD) load_next(env_st & ended & have_next & !next_early);  // ended some other way: fetched late
-            if (__any(env_ok & ended & !have_next)) reset_group<SCN, GW, Sync>(a, lds, e, g, ag, env_st & ended & !have_next, rc_raw);
+            if (__any(env_ok & ended & !have_next)) reset_group<SCN, GW, Sync>(RG_SAMPLER_ARGS, lds, e, g, ag, env_st & ended & !have_next, rc_raw, sv.seed);
             if (env_st & ended & have_next) {  // the same stores reset_group makes with commit = true
                 if (ag < N) {
                     const auto X = RG_ARG(a.st.poses) + eN * 3;
@@ -1570,7 +1583,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         if (AHEAD && ahead_e && !(replayed | __any(max_sweeps > 2)) && __any(env_ok & !ended & !have_next)) {
             const bool need = env_st & !ended & !have_next;
             Sync::sync();  // (LDS scratch of a reset above is free again)
-            reset_group<SCN, GW, Sync>(a, lds, e, g, ag, need, rc_raw, reset_dst_next(a, e));
+            reset_group<SCN, GW, Sync>(RG_SAMPLER_ARGS, lds, e, g, ag, need, rc_raw, reset_dst_next(RG_SAMPLER_ARGS, e), sv.seed);
             if (need && ag == 0) RG_ARG(a.st.next_episode)[e] = rc_raw;
         }
         RG_STAMP(6);  // reset done
@@ -1579,6 +1592,9 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
 }
 
 #undef RG_ARG
+#undef RG_ARG_BLOCK_OFF
+#undef RG_IMG
+#undef RG_SAMPLER_ARGS
 #undef RG_ARG_OFF
 #undef RG_ARG_OR
 #undef RG_OUT
@@ -1686,6 +1702,25 @@ template <int SCN, int GW, bool OBS_ONLY, int NT, bool ROLLOUT, int ROW, std::en
 __global__ __launch_bounds__(WAVE) void step_kernel(const KernelArgs a) {
     step_kernel_body<PlainFamily, SCN, GW, OBS_ONLY, NT, ROLLOUT, false, 0, true>(a);
 }
+#ifndef RG_HOST_SIM
+// RESIDENT: the row kernel again, taking the handle's resident image and the per-call arguments (kernel_args.h ResidentCall: the
+// parameters below are its members in its order).  The image is never written once a launch may read it -- a change takes a fresh
+// slot (robogym_capi.hip) -- so it is read through the CONSTANT address space: the compiler keeps scalar loads for its uniform
+// members, as it does for kernel arguments.  Instantiated in robogym_resident.hip alone, whose flags hand the leading
+// parameters over in scalar registers.  (A further overload: the by-value row kernels keep their names.)
+template <int SCN, int GW, bool OBS_ONLY, int NT, bool ROLLOUT, int ROW, bool RESIDENT, std::enable_if_t<ROW == 16 && RESIDENT, int> = 0>
+__global__ __launch_bounds__(WAVE) void step_kernel(const KernelArgs *image, const int32_t *actions, const uint64_t seed, const int32_t auto_reset,
+                                                    const int32_t grid, const rg_step_io io) {
+    static_assert(GW == 8 && !OBS_ONLY && !ROLLOUT, "the 16-lane rows: the single-step launch at GW 8");
+    typedef const __attribute__((address_space(4))) KernelArgs *ConstImage;
+    ConstImage ci = (ConstImage)image;
+    asm volatile("" : "+s"(ci));   // (opaque, as in kernarg_block: seen through, the cast folds away and the loads are global ones)
+    const KernelArgs &a = *(const KernelArgs *)ci;
+    __shared__ Lds<GW> lds;
+    const StepView sv = {actions, io, &auto_reset, &seed, grid};
+    step_once<SCN, GW, false, NT, true, false, 0, void, WgSync, false, false, true, false, true>(a, lds, sv);
+}
+#endif
 // generic agent count (NT = 0) throughout
 template <int SCN, int GW, bool OBS_ONLY, bool ROLLOUT, bool GYM, int QPM>
 __global__ __launch_bounds__(WAVE) void lidar_step_kernel(const LidarArgs la) {
@@ -1766,7 +1801,7 @@ static void launch_kernel(const typename F::Args &args, int grid, hipStream_t st
 // block's, the observation-only, the interior-point and every lidar and disturbance kernel are generic.  rows: the 16-lane-row
 // kernel instead.
 template <class F, int SCN, bool OBS_ONLY, bool ROLLOUT, bool GYM, int QPM>
-static hipError_t launch_gw(const typename F::Args &args, int gw, int n, bool rows, int grid, hipStream_t stream) {
+static hipError_t launch_gw(const typename F::Args &args, const GroupSide &side, int gw, int n, bool rows, int grid, hipStream_t stream) {
     constexpr bool EXACT = QPM == RG_QP_EXACT;
     constexpr bool BY_N = EXACT && !OBS_ONLY && !GYM && !F::LIDAR && !F::NOISE;
     constexpr bool ROWS = BY_N && !ROLLOUT && !F::TEAM && !kStampsBuild;
@@ -1787,6 +1822,10 @@ static hipError_t launch_gw(const typename F::Args &args, int gw, int n, bool ro
                 default: launch_kernel<F, SCN, 8, false, 8, ROLLOUT, false, QPM, R>(args, grid, stream); break;
             }
         };
+        if constexpr (ROWS) {
+            // rows, and the handle has a valid image: the resident form of the same kernel (robogym_resident.hip)
+            if (rows && side.image) return launch_step_resident(args, side, stream);
+        }
         if (ROWS && rows) by_n(std::integral_constant<bool, ROWS>());
         else by_n(std::false_type());
     } else {
@@ -1819,13 +1858,13 @@ static hipError_t launch_group(const KernelArgs &a_in, const GroupSide &side, hi
             const typename F::Args args = F::args(a, side);
             if constexpr (!OBS_ONLY && !ROLLOUT) {
                 if (a.io.elapsed)   // gymma block: its own instantiations
-                    return launch_gw<F, SCN, false, false, true, QPM>(args, gw, a.p.n_agents, false, wf.grid, stream);
+                    return launch_gw<F, SCN, false, false, true, QPM>(args, side, gw, a.p.n_agents, false, wf.grid, stream);
             }
             // at most 4 envs per wave (batches up to 4096 envs): each env on a 16-lane row, the upper half a replica that takes
             // over part of the order-free work (step_once SPAN; the plain family's exact single step at GW 8).  A negative
             // envs_per_wave on entry (rg_step under RG_STEP_SPAN=0, rg_create) keeps 8-lane groups.
             const bool rows = a_in.envs_per_wave >= 0 && wf.epw <= 4;
-            return launch_gw<F, SCN, OBS_ONLY, ROLLOUT, false, QPM>(args, gw, a.p.n_agents, rows, wf.grid, stream);
+            return launch_gw<F, SCN, OBS_ONLY, ROLLOUT, false, QPM>(args, side, gw, a.p.n_agents, rows, wf.grid, stream);
         }
     });
 }

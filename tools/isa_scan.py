@@ -245,6 +245,29 @@ def resources(code_object):
     return out
 
 
+def kernarg_preload(code_object):
+    """-> {kernel symbol: (length, offset)}: the dwords of kernel arguments each kernel descriptor asks the command processor to
+    preload into SGPRs, and the dword they start at (bytes 58..59 of the 64-byte descriptor `<kernel>.kd`: length in bits 0..6,
+    offset in bits 7..15)."""
+    readelf = _tool("llvm-readelf")
+    secs = {}
+    for line in subprocess.run([readelf, "-S", "--wide", code_object], check=True, capture_output=True, text=True).stdout.splitlines():
+        m = re.match(r"\s*\[\s*(\d+)\]\s+(\S*)\s+\S+\s+([0-9a-f]+)\s+([0-9a-f]+)\s+([0-9a-f]+)", line)
+        if m:
+            secs[int(m.group(1))] = (int(m.group(3), 16), int(m.group(4), 16))   # address, file offset
+    with open(code_object, "rb") as f:
+        blob = f.read()
+    out = {}
+    for line in subprocess.run([readelf, "-s", "--wide", code_object], check=True, capture_output=True, text=True).stdout.splitlines():
+        f = line.split()
+        if len(f) == 8 and f[7].endswith(".kd") and f[6].isdigit():
+            addr, off = secs[int(f[6])]
+            at = int(f[1], 16) - addr + off
+            word = int.from_bytes(blob[at + 58:at + 60], "little")
+            out[f[7][:-3]] = (word & 0x7F, word >> 7)
+    return out
+
+
 def scan_library(so_path):
     """-> {kernel: {"n_insts", "dots", "dot_hazards", "exec_prologue", "resources"}} over every code object of the library."""
     report = {}
