@@ -248,6 +248,26 @@ int rg_get_obs(rg_handle *h, float *obs);
  * query exists so that tests and profiles can say which one ran.  Negative: error. */
 int rg_step_kernel(const rg_handle *h);
 
+/* Which form the handle's last rg_step launch took (csrc/kernel_args.h ResidentCall, RG_REF_SHAPES).  All forms give bit-identical
+ * results; the query exists so that tests and profiles can say which one ran.
+ *   RG_FORM_NONE      no rg_step yet
+ *   RG_FORM_BY_VALUE  the whole argument block by value (every kernel but the 16-lane-row ones; RG_STEP_RESIDENT=0; no image)
+ *   RG_FORM_RESIDENT  a row kernel reading the handle's resident image, every parameter a run-time value
+ *   RG_FORM_SHAPE + s the resident row kernel of reference shape s >= 1: the handle's parameter block matched row s of the table
+ *                     field for field, and the kernel holds those fields as constants.  RG_STEP_SHAPE=0 at rg_create: never.
+ * Negative: error. */
+#define RG_FORM_NONE 0
+#define RG_FORM_BY_VALUE 1
+#define RG_FORM_RESIDENT 2
+#define RG_FORM_SHAPE 16
+int rg_step_form(const rg_handle *h);
+/* The reference shape a parameter block matches (1 ..), or 0.  Host code only: needs no device. */
+int rg_shape_match(const rg_scenario_params *params);
+/* Row `shape` of the table as ten ints: id, scenario, n_agents, then num_prey, obs_dim, num_neighbors, capability_aware,
+ * update_frequency, controller_period, penalize_violations as the shape's kernel holds them (-1: read at run time).
+ * 0, or negative where there is no such row. */
+int rg_shape_info(int32_t shape, int32_t *row);
+
 /* ---- lidar range observation (opt-in; out of parity scope: the reference has no lidar) --------------------------------
  * With rays > 0, every observation row the handle writes (rg_step, rg_rollout, rg_get_obs) carries `rays` floats at columns
  * offset .. offset + rays - 1 = obs_dim - 1, after the scenario's own columns.  Ray k of an agent at pose (x, y, theta) points

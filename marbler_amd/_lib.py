@@ -114,13 +114,32 @@ class RgDisturbanceParams(C.Structure):
     _fields_ = [("sigma_xy", C.c_float), ("sigma_theta", C.c_float), ("reserved", C.c_float * 2)]
 
 
+# rg_step_form: which form the last rg_step launch took (include/robogym.h RG_FORM_*)
+FORM_NONE, FORM_BY_VALUE, FORM_RESIDENT, FORM_SHAPE = 0, 1, 2, 16
+
+
+def reference_shapes():
+    """The library's table of reference shapes (csrc/kernel_args.h RG_REF_SHAPES): [{id, scenario, n_agents, num_prey, ...}],
+    a field the shape's kernel reads at run time is -1.  Host code: needs no GPU."""
+    lib = load()
+    names = ("id", "scenario", "n_agents", "num_prey", "obs_dim", "num_neighbors", "capability_aware", "update_frequency",
+             "controller_period", "penalize_violations")
+    out, row = [], (C.c_int32 * 10)()
+    while lib.rg_shape_info(len(out) + 1, C.byref(row)) == 0:
+        out.append(dict(zip(names, list(row))))
+    return out
+
+
 EXPORTS = ("rg_abi_version", "rg_last_error", "rg_sizeof_params", "rg_sizeof_state", "rg_sizeof_step_io", "rg_next_init_stride",
            "rg_create", "rg_destroy", "rg_bind_state", "rg_set_stream", "rg_reset", "rg_step", "rg_rollout", "rg_get_obs", "rg_step_kernel",
            "rg_actor_forward", "rg_actor_forward_explore", "rg_actor_pack_gru", "rg_actor_pack_gru_bf16x3", "rg_actor_pack_gru_f16x2", "rg_actor_last_error",
            "rg_sizeof_policy_io", "rg_policy_rollout", "rg_sizeof_lidar_params", "rg_set_lidar",
            "rg_sizeof_team_params", "rg_set_teams",
            "rg_actor_forward_sample", "rg_sizeof_policy_sample", "rg_policy_rollout_sample",
-           "rg_sizeof_disturbance_params", "rg_set_disturbance")
+           "rg_sizeof_disturbance_params", "rg_set_disturbance", "rg_step_form", "rg_shape_match", "rg_shape_info")
+# the queries a library of an earlier build lacks: tolerated in one loaded through ROBOGYM_LIB (an A/B run against it), never in
+# the package's own
+LATE_QUERIES = ("rg_step_form", "rg_shape_match", "rg_shape_info")
 
 _lib = None
 
@@ -141,6 +160,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name in EXPORTS:
         if not hasattr(lib, name):
+            if name in LATE_QUERIES and os.environ.get("ROBOGYM_LIB"):
+                continue
             raise RobogymError(f"{LIB_PATH} does not export {name}")
     lib.rg_abi_version.restype = C.c_int
     lib.rg_last_error.restype = C.c_char_p
@@ -157,6 +178,13 @@ def load():
     lib.rg_get_obs.argtypes = [C.c_void_p, C.c_void_p]
     lib.rg_step_kernel.argtypes = [C.c_void_p]
     lib.rg_step_kernel.restype = C.c_int
+    if hasattr(lib, "rg_step_form"):   # (LATE_QUERIES)
+        lib.rg_step_form.argtypes = [C.c_void_p]
+        lib.rg_step_form.restype = C.c_int
+        lib.rg_shape_match.argtypes = [C.POINTER(RgScenarioParams)]
+        lib.rg_shape_match.restype = C.c_int
+        lib.rg_shape_info.argtypes = [C.c_int32, C.POINTER(C.c_int32 * 10)]
+        lib.rg_shape_info.restype = C.c_int
     lib.rg_actor_forward.argtypes = [C.POINTER(RgActorWeights), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rg_actor_forward.restype = C.c_int

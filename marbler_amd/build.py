@@ -15,7 +15,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librobogym_hip.so")
-SOURCES = ["robogym_kernels.hip", "robogym_resident.hip", "robogym_rollout_group.hip", "robogym_kernels_ipm.hip", "robogym_rollout_group_ipm.hip",
+SOURCES = ["robogym_kernels.hip", "robogym_resident.hip", "robogym_resident_shapes.hip", "robogym_rollout_group.hip", "robogym_kernels_ipm.hip", "robogym_rollout_group_ipm.hip",
            "robogym_tpe.hip", "robogym_rollout_tpe.hip", "robogym_capi.hip", "actor_mfma.hip", "robogym_policy_h64.hip",
            "robogym_policy_h128.hip", "robogym_policy_sample_h64.hip", "robogym_policy_sample_h128.hip", "robogym_lidar.hip", "robogym_lidar_rollout.hip", "robogym_lidar_ipm.hip",
            "robogym_lidar_rollout_ipm.hip", "robogym_team.hip", "robogym_team_rollout.hip", "robogym_team_ipm.hip",
@@ -64,6 +64,8 @@ RESIDENT_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 FILE_FLAGS = {"robogym_tpe.hip": ["-fno-slp-vectorize"], "robogym_rollout_tpe.hip": ["-fno-slp-vectorize"],
               "robogym_kernels.hip": GROUP_SLP, "robogym_rollout_group.hip": GROUP_SLP,
               "robogym_resident.hip": GROUP_SLP + RESIDENT_PRELOAD,
+              # the reference shapes' resident kernels (kernel_args.h RG_REF_SHAPES): the same kernels, the same flags
+              "robogym_resident_shapes.hip": GROUP_SLP + RESIDENT_PRELOAD,
               "robogym_kernels_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_rollout_group_ipm.hip": GROUP_SLP + IPM_SCHED,
               "robogym_policy_h64.hip": GROUP_SLP, "robogym_policy_h128.hip": GROUP_SLP,
               "robogym_policy_sample_h64.hip": GROUP_SLP, "robogym_policy_sample_h128.hip": GROUP_SLP,

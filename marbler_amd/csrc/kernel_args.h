@@ -119,10 +119,11 @@ hipError_t launch_reset(const KernelArgs &a, hipStream_t stream);
 // An observation-only launch (rg_get_obs) runs no controller: it exists in the exact mode only and serves both.  The disturbance
 // family has none: rg_get_obs displaces nothing, and a disturbed handle's goes to the plain entry.
 enum GroupFamily { GROUP_PLAIN, GROUP_LIDAR, GROUP_TEAM, GROUP_DISTURB };
-enum GroupKind { GROUP_STEP, GROUP_ROLLOUT, GROUP_OBS, GROUP_STEP_RESIDENT };
+enum GroupKind { GROUP_STEP, GROUP_ROLLOUT, GROUP_OBS, GROUP_STEP_RESIDENT, GROUP_STEP_SHAPE };
 #define RG_GROUP_ENTRIES(X)                                              \
     X(launch_step, GROUP_PLAIN, RG_QP_EXACT, GROUP_STEP)                 \
     X(launch_step_resident, GROUP_PLAIN, RG_QP_EXACT, GROUP_STEP_RESIDENT) \
+    X(launch_step_shape, GROUP_PLAIN, RG_QP_EXACT, GROUP_STEP_SHAPE)     \
     X(launch_obs, GROUP_PLAIN, RG_QP_EXACT, GROUP_OBS)                   \
     X(launch_rollout, GROUP_PLAIN, RG_QP_EXACT, GROUP_ROLLOUT)           \
     X(launch_step_ipm, GROUP_PLAIN, RG_QP_CVXOPT, GROUP_STEP)            \
@@ -154,6 +155,7 @@ struct GroupSide {
     const rg_team_params *teams;
     const DisturbScale *disturb;
     const struct KernelArgs *image;   // the handle's resident image on the device (below), or null: the launch goes by value
+    int shape;                        // the reference shape the image's block matched (below: match_shape), or 0
 };
 
 // The resident form of the 16-lane-row step kernels (robogym_resident.hip).  What rg_create / rg_bind_state fix -- p, k, st, E,
@@ -173,6 +175,57 @@ struct ResidentCall {   // the kernel-argument segment of a resident kernel (its
 static_assert(sizeof(ResidentCall) <= 256, "the per-call arguments fit one register of dwords (device_common.h load_arg_regs_resident)");
 // the image of a handle's block: the per-call members cleared, envs_per_wave as launch_group sets it
 hipError_t resident_image(KernelArgs &a);
+
+// SHAPES.  Seven members of the parameter block are fixed by rg_create for the handle's life, yet a kernel that reads them at run
+// time pays for the question on every launch: loops with clamps over the prey and the neighbour rows, both observation formats,
+// the staging paths of more than 8 prey, the sub-step loop's bookkeeping.  A Shape names them as compile-time constants, the way
+// NT names the agent count; -1 = read at run time (NoShape: every kernel but the ones below).  P num_prey, D obs_dim,
+// M num_neighbors, CA capability_aware != 0, U update_frequency, PERIOD controller_period, PENALIZE penalize_violations != 0.
+template <int P_, int D_, int M_, int CA_, int U_, int PERIOD_, int PENALIZE_>
+struct Shape {
+    static constexpr int P = P_, D = D_, M = M_, CA = CA_, U = U_, PERIOD = PERIOD_, PENALIZE = PENALIZE_;
+};
+using NoShape = Shape<-1, -1, -1, -1, -1, -1, -1>;
+// The reference shapes -- the configurations of bench.py's bench_overrides(), values from configs/*.yaml through params.py --
+// in ONE table that the kernels (robogym_resident_shapes.hip), the dispatcher (match_shape below) and the tests (rg_shape_info)
+// all read: X(id, scenario, n_agents, P, D, M, CA, U, PERIOD, PENALIZE).  A field the scenario's kernel never reads stays -1.
+// Each row is a kernel to build and keep correct: no further ones.  Ids start at 1 (0 = no shape).
+// RG_SHAPE_FIELDS (A/B builds, listed in probes/diag.h): bit i clear = the table's field i stays a run-time value.
+#ifndef RG_SHAPE_FIELDS
+#define RG_SHAPE_FIELDS 127
+#endif
+#define RG_SF(bit, v) ((RG_SHAPE_FIELDS >> (bit)) & 1 ? (v) : -1)
+#define RG_REF_SHAPES(X)                                                                                                      \
+    X(1, RG_SCN_PREDATOR_CAPTURE_PREY, 5, RG_SF(0, 6), RG_SF(1, 16), RG_SF(2, 3), RG_SF(3, 0), RG_SF(4, 29), RG_SF(5, 15), RG_SF(6, 1)) \
+    X(2, RG_SCN_WAREHOUSE, 8, -1, RG_SF(1, 18), RG_SF(2, 5), -1, RG_SF(4, 29), RG_SF(5, 15), RG_SF(6, 1))                               \
+    X(3, RG_SCN_MATERIAL_TRANSPORT, 6, -1, RG_SF(1, 9), -1, RG_SF(3, 0), RG_SF(4, 74), RG_SF(5, 15), RG_SF(6, 1))
+// The shape of a parameter block, or 0: scenario and agent count, and EXACTLY every field the shape compiles in (the two flags
+// as the kernel reads them: zero or not).  The one place that decides; plain host code (the tests call it without a GPU).
+inline int match_shape(const rg_scenario_params &p) {
+#define RG_X(id, scn, n, P, D, M, CA, U, PERIOD, PENALIZE)                                                                       \
+    if (p.scenario == (scn) && p.n_agents == (n) && ((P) < 0 || p.num_prey == (P)) && ((D) < 0 || p.obs_dim == (D)) &&            \
+        ((M) < 0 || p.num_neighbors == (M)) && ((CA) < 0 || (p.capability_aware != 0) == ((CA) != 0)) &&                          \
+        ((U) < 0 || p.update_frequency == (U)) && ((PERIOD) < 0 || p.controller_period == (PERIOD)) &&                           \
+        ((PENALIZE) < 0 || (p.penalize_violations != 0) == ((PENALIZE) != 0)))                                                   \
+        return id;
+    RG_REF_SHAPES(RG_X)
+#undef RG_X
+    return 0;
+}
+// row `id` of the table as ten ints (id, scenario, n_agents, then the seven fields); false: no such row
+inline bool shape_row(int id, int32_t out[10]) {
+#define RG_X(i, scn, n, P, D, M, CA, U, PERIOD, PENALIZE)                          \
+    if (id == (i)) {                                                               \
+        const int32_t r[10] = {i, scn, n, P, D, M, CA, U, PERIOD, PENALIZE};       \
+        for (int c = 0; c < 10; ++c) out[c] = r[c];                                \
+        return true;                                                               \
+    }
+    RG_REF_SHAPES(RG_X)
+#undef RG_X
+    return false;
+}
+// (the resident launch of shape side.shape: launch_step_shape, robogym_resident_shapes.hip; GROUP_STEP_SHAPE is the dispatcher's
+// own kind, like GROUP_STEP_RESIDENT)
 typedef hipError_t GroupLaunch(const KernelArgs &a, const GroupSide &side, hipStream_t stream);
 #define RG_X(entry, family, mode, kind) GroupLaunch entry;
 RG_GROUP_ENTRIES(RG_X)

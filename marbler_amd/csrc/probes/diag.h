@@ -11,7 +11,7 @@
 //   RG_TPE_GUARD             thread-per-env kernel: stores through the LDS staging block are bounds-checked
 //   RG_HOST_SIM              the kernels compiled for the host (tests/sanitize/): 64 threads = 64 lanes
 // and the tuning constants RG_CHUNK, RG_MAX_WAVES, RG_ROW_ARG_REGS / SWAP_HALVES, RG_TPE_W4 / W5 / W78, RG_TPE_NO_W3
-// (A/B builds).
+// (A/B builds), and RG_SHAPE_FIELDS (kernel_args.h: which fields of the reference shapes are compiled in; 127 = all seven).
 // One-off probes of rounds 2-4 (shadow copies, RG_PROBE_*, RG_FIXED_U, RG_DENSE_PRETEST, RG_NT_STORES, RG_NO_XCD_REMAP,
 // RG_TPE_NO_DMAX_GUARD) were removed in round 5; what they measured is in NOTEBOOK.md and profiles/, the code in git history.
 #pragma once

@@ -40,6 +40,11 @@ struct rg_handle {
     rg::KernelArgs *image_slots; // device: RG_IMAGE_SLOTS slots of RG_IMAGE_STRIDE bytes (allocated with the first image)
     int32_t images_used;
     const rg::KernelArgs *image; // the image of the handle as it is now, or null
+    bool shapes;                 // RG_STEP_SHAPE=0 at rg_create: the generic kernels only (A/B runs, tests)
+    // The reference shape that `image`'s block matched (kernel_args.h match_shape; 0: none, or `shapes` is off): decided where the
+    // image is written, so a change that makes the image stale is matched again with the next one.
+    int32_t image_shape;
+    mutable int32_t last_form;   // rg_step_form: RG_FORM_* of the last rg_step launch
     bool image_stale;            // the handle has changed since `image` was written (or none was written yet)
 };
 constexpr int RG_IMAGE_SLOTS = 8;
@@ -48,6 +53,7 @@ static_assert(sizeof(rg::KernelArgs) <= RG_IMAGE_STRIDE, "an image slot holds th
 static void write_image(rg_handle *h);
 static void drop_image(rg_handle *h) {   // the handle changes: its image no longer describes it
     h->image = nullptr;
+    h->image_shape = 0;
     h->image_stale = true;
 }
 
@@ -270,6 +276,12 @@ rg_handle *rg_create(const rg_scenario_params *params, int32_t num_envs, int64_t
         const char *res = getenv("RG_STEP_RESIDENT");
         h->resident = !(res && !strcmp(res, "0")) && rg::resident_image && rg::launch_step_resident;
     }
+    {
+        const char *shp = getenv("RG_STEP_SHAPE");
+        h->shapes = !(shp && !strcmp(shp, "0")) && rg::launch_step_shape;
+    }
+    h->image_shape = 0;
+    h->last_form = RG_FORM_NONE;
     h->image_slots = nullptr;
     h->images_used = 0;
     h->image = nullptr;
@@ -396,6 +408,7 @@ static int fill_args(rg_handle *h, rg::KernelArgs &a);
 // stream is being captured.  Leaves h->image null where there is none: never an error.
 static void write_image(rg_handle *h) {
     h->image = nullptr;
+    h->image_shape = 0;
     if (!h->resident || !h->bound || h->use_tpe || !h->span || h->teams.n_sets || h->lidar.rays || h->disturbed ||
         h->params.qp_mode != RG_QP_EXACT) {
         h->image_stale = false;   // no row kernel serves this handle as it is; a change marks it stale again
@@ -435,6 +448,7 @@ static void write_image(rg_handle *h) {
         return;
     }
     h->image = slot;
+    h->image_shape = h->shapes ? rg::match_shape(a.p) : 0;
 }
 
 static int fill_args(rg_handle *h, rg::KernelArgs &a) {
@@ -481,6 +495,13 @@ static int launched(hipError_t err) {
     return 0;
 }
 
+// RG_FORM_*: the form a step launch takes in the dispatcher (step_group.h launch_gw).  A handle has an image only where the
+// dispatcher chooses rows for it (write_image: RG_STEP_SPAN allows them, resident_image has checked agent count and batch size), so
+// an image means the resident form, and its shape's kernel where one matched.
+static int32_t step_form(const rg::KernelArgs *image, int shape) {
+    return !image ? RG_FORM_BY_VALUE : shape ? RG_FORM_SHAPE + shape : RG_FORM_RESIDENT;
+}
+
 // The lane-group launch of a handle: the family its side blocks select (a pool, the lidar and the disturbance exclude one
 // another), the handle's solver mode -- an observation-only launch runs no controller and uses the exact mode's kernel in either,
 // and displaces nothing: a disturbed handle's is the plain family's -- and the launch kind.
@@ -488,7 +509,9 @@ static int launch_group_entry(const rg_handle *h, const rg::KernelArgs &a, int k
     const int family = h->teams.n_sets ? rg::GROUP_TEAM : h->lidar.rays ? rg::GROUP_LIDAR
                        : (h->disturbed && kind != rg::GROUP_OBS) ? rg::GROUP_DISTURB : rg::GROUP_PLAIN;
     const int mode = kind == rg::GROUP_OBS ? RG_QP_EXACT : h->params.qp_mode;
-    const rg::GroupSide side = {&h->lidar, &h->teams, &h->disturb, family == rg::GROUP_PLAIN ? image : nullptr};
+    const bool res = family == rg::GROUP_PLAIN && image;
+    const rg::GroupSide side = {&h->lidar, &h->teams, &h->disturb, res ? image : nullptr, res ? h->image_shape : 0};
+    if (kind == rg::GROUP_STEP) h->last_form = step_form(side.image, side.shape);
     for (const GroupEntry &g : g_group)
         if (g.family == family && g.mode == mode && g.kind == kind && g.launch) return launched(g.launch(a, side, h->stream));
     return fail(-100, "this build has no lane-group step kernels");
@@ -521,7 +544,10 @@ int rg_step(rg_handle *h, const int32_t *actions, const rg_step_io *io, int32_t 
     if (int rc = sync_seed(h, seed)) return rc;
     // (asks the plain family's dispatcher for 8-lane groups throughout: it sets the real value itself)
     if (!h->span && !h->teams.n_sets && !h->lidar.rays && !h->disturbed) a.envs_per_wave = -1;
-    if (h->use_tpe) return launched(rg::launch_step_tpe(a, h->stream));
+    if (h->use_tpe) {
+        h->last_form = RG_FORM_BY_VALUE;
+        return launched(rg::launch_step_tpe(a, h->stream));
+    }
     if (h->image_stale) write_image(h);
     // (the dispatcher takes the resident form where it chooses rows; the gymma block has kernels of its own)
     return launch_group_entry(h, a, rg::GROUP_STEP, io->elapsed ? nullptr : h->image);
@@ -652,6 +678,21 @@ int rg_set_teams(rg_handle *h, const rg_team_params *tp) {
 int rg_step_kernel(const rg_handle *h) {
     if (!h) return fail(-1, "handle is NULL");
     return h->use_tpe ? 1 : 0;
+}
+
+int rg_step_form(const rg_handle *h) {
+    if (!h) return fail(-1, "handle is NULL");
+    return h->last_form;
+}
+
+int rg_shape_match(const rg_scenario_params *params) {
+    if (!params) return fail(-1, "params is NULL");
+    return rg::match_shape(*params);
+}
+
+int rg_shape_info(int32_t shape, int32_t *row) {
+    if (!row) return fail(-1, "row is NULL");
+    return rg::shape_row(shape, row) ? 0 : fail(-80, "rg_shape_info: no such reference shape");
 }
 
 int rg_get_obs(rg_handle *h, float *obs) {

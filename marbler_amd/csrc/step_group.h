@@ -414,14 +414,18 @@ __device__ __forceinline__ void write_neighbour_obs(Lds<GW> &lds, int N, int Knb
 // where a result is brought across on purpose (row_ror:8, xor_lane_i<8>).
 // NOISE: the pose disturbance of `nz` (disturb.h): the step begins by displacing the poses it has just loaded.  Its own
 // instantiations (disturb_step_kernel).
+// SH: the members of the parameter block that are compile-time constants here (kernel_args.h Shape; NoShape: none).  The
+// resident form's reference shapes only (robogym_resident_shapes.hip); the host launches such a kernel for a handle whose
+// block holds exactly these values (match_shape).
 template <int SCN, int GW, bool OBS_ONLY, int NT, bool AHEAD, bool GYM, int QPM = 0, typename QpLds = void, typename Sync = WgSync,
-          bool LIDAR = false, bool TEAM = false, bool SPAN = false, bool NOISE = false, bool RES = false>
+          bool LIDAR = false, bool TEAM = false, bool SPAN = false, bool NOISE = false, bool RES = false, class SH = NoShape>
 __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, const StepView &sv, QpLds *qp_lds = nullptr,
                                           const rg_lidar_params *lid = nullptr, const rg_team_params *tm = nullptr,
                                           const DisturbScale *nz = nullptr) {
     static_assert(!SPAN || (GW == 8 && QPM == 0 && !GYM && !LIDAR && !TEAM && !NOISE), "the 16-lane rows: exact mode, GW = 8, no side blocks");
     static_assert(!NOISE || !OBS_ONLY, "an observation-only launch displaces nothing");
     static_assert(!RES || (SPAN && RG_ROW_ARG_REGS != 0), "the resident form: the 16-lane rows, arguments in vector registers");
+    static_assert(RES || std::is_same<SH, NoShape>::value, "shapes: the resident form only");
     constexpr int RW = SPAN ? 2 * GW : GW;  // lanes per env
     constexpr int EPW = WAVE / RW;  // envs per wave
     RG_STAMPS_BEGIN()
@@ -443,6 +447,8 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
 #define RG_ARG(f) (ARGV ? arg_reg<std::decay_t<decltype(f)>>(av, RG_ARG_OFF(f)) : (f))
 #define RG_ARG_OR(f, q) (ARGV ? arg_reg<std::decay_t<decltype(q)>>(av, RG_ARG_OFF(f)) : (q))
 #define RG_OUT(m) (ARGV ? arg_reg<std::decay_t<decltype(sv.io.m)>>(av, RG_ARG_OFF(a.io.m)) : (sv.io.m))
+    // RG_SHAPED(F, x): the shape's constant for field F where it has one, the run-time value x where not (NoShape: always x)
+#define RG_SHAPED(F, x) (SH::F >= 0 ? SH::F : (x))
     auto arg_elem = [&](const auto &array, int i) {   // element i of an int array of the block that lies in one register (ARGV only)
         const unsigned off = static_cast<unsigned>(reinterpret_cast<const char *>(&array) - reinterpret_cast<const char *>(&a));
         return __builtin_amdgcn_readlane(av[off >> 8], static_cast<int>((off >> 2) & 63) + i);
@@ -468,9 +474,13 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     const int32_t *q_rc = RG_IMG(a.st.reset_count), *q_nep = AHEAD ? RG_IMG(a.st.next_episode) : nullptr;
     const float *q_nin = AHEAD ? RG_IMG(a.st.next_init) : nullptr;
     const int q_nst = AHEAD ? a.next_stride : 0;
-    const int q_E = a.E, q_epw = a.envs_per_wave, q_P = p.num_prey, q_N = p.n_agents, q_G = RES ? sv.grid : gridDim.x;
+    const int q_E = a.E, q_epw = a.envs_per_wave, q_P = RG_SHAPED(P, p.num_prey), q_N = p.n_agents, q_G = RES ? sv.grid : gridDim.x;
+    if constexpr (SH::P < 0)
     asm volatile("" ::"s"(q_poses), "s"(q_carry), "s"(q_ret), "s"(q_sum), "s"(q_steps), "s"(q_act), "s"(q_cnt), "s"(q_stp),
                  "s"(q_E), "s"(q_epw), "s"(q_P), "s"(q_N), "s"(q_G), "s"(q_rc));
+    else   // (q_P is a constant: nothing to fetch)
+    asm volatile("" ::"s"(q_poses), "s"(q_carry), "s"(q_ret), "s"(q_sum), "s"(q_steps), "s"(q_act), "s"(q_cnt), "s"(q_stp),
+                 "s"(q_E), "s"(q_epw), "s"(q_N), "s"(q_G), "s"(q_rc));
     if constexpr (GYM) asm volatile("" ::"s"(q_el), "s"(q_tl));
     if constexpr (AHEAD) asm volatile("" ::"s"(q_nep), "s"(q_nin), "s"(q_nst));
     const float *q_prey = RG_IMG(a.st.prey_loc);
@@ -587,7 +597,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                 nx_pose[2] = nb[2 * N + ag];
             }
             if constexpr (SCN == RG_SCN_PREDATOR_CAPTURE_PREY || SCN == RG_SCN_SIMPLE) {
-                if (ag < RG_ARG_OR(p.num_prey, q_P)) {
+                if (ag < RG_SHAPED(P, RG_ARG_OR(p.num_prey, q_P))) {
                     nx_a = nb[3 * N + 2 * ag];
                     nx_b = nb[3 * N + 2 * ag + 1];
                 }
@@ -769,8 +779,8 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         // dt*v*(cos, sin) to the small displacement and the position is the single rounding bx + ox, so the
         // roundings of the 29..74 Euler updates do not pile up in x, y (float spec, oracle/oracle_core.h)
         float bx = x, by = y, ox = 0.0f, oy = 0.0f;
-        const bool penalize = p.penalize_violations != 0;
-        const int U = p.update_frequency, period = p.controller_period;
+        const bool penalize = RG_SHAPED(PENALIZE, p.penalize_violations) != 0;
+        const int U = RG_SHAPED(U, p.update_frequency), period = RG_SHAPED(PERIOD, p.controller_period);
         for (int it0 = 0; it0 < U; it0 += period) {
             const int n = (U - it0) < period ? (U - it0) : period;
             RG_HEADING_SINCOS(th, s, c);
@@ -989,7 +999,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     }
 
     // ---- scenario epilogue
-    const int D = RG_ARG(p.obs_dim);
+    const int D = RG_SHAPED(D, RG_ARG(p.obs_dim));
     const auto obs_row = RG_OUT(obs) + (eN + ag) * D;
     // (SPAN: the prologue's flags formed again from the registers, rather than fetched again)
     const bool ahead_e = ARGV ? AHEAD && (!OBS_ONLY) && RG_ARG(a.next_stride) > 0 && RG_ARG(a.auto_reset) : ahead;
@@ -1008,7 +1018,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     if constexpr (AHEAD) load_next(next_early & !helper);
 
     if constexpr (SCN == RG_SCN_PREDATOR_CAPTURE_PREY) {
-        const int P = RG_ARG_OR(p.num_prey, q_P);
+        const int P = RG_SHAPED(P, RG_ARG_OR(p.num_prey, q_P));
         if constexpr (TEAM) {
             RG_LATE(sr);
             RG_LATE(cr);
@@ -1184,7 +1194,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         }
         }
         RG_STAMP_E(0);  // prey tracked, nearest prey found
-        const int od = RG_ARG(p.capability_aware) ? 6 : 4;
+        const int od = RG_SHAPED(CA, RG_ARG(p.capability_aware)) ? 6 : 4;
         lds.own[lane][0] = x;
         lds.own[lane][1] = y;
         lds.own[lane][2] = qx;
@@ -1197,10 +1207,10 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
 #pragma unroll
                 for (int cc = 0; cc < 6; ++cc) obs_row[cc] = lds.own[lane][cc];
             }
-            write_neighbour_obs<GW, 6, NT, SPAN>(lds, N, RG_ARG(p.num_neighbors), ag, gbase, lane_nb, x, y, obs_row);
+            write_neighbour_obs<GW, 6, NT, SPAN>(lds, N, RG_SHAPED(M, RG_ARG(p.num_neighbors)), ag, gbase, lane_nb, x, y, obs_row);
         } else {
             if (lane_st) out_store4(obs_row, x, y, qx, qy);
-            write_neighbour_obs<GW, 4, NT, SPAN>(lds, N, RG_ARG(p.num_neighbors), ag, gbase, lane_nb, x, y, obs_row);
+            write_neighbour_obs<GW, 4, NT, SPAN>(lds, N, RG_SHAPED(M, RG_ARG(p.num_neighbors)), ag, gbase, lane_nb, x, y, obs_row);
         }
         RG_STAMP_E(1);  // observations written
         if constexpr (!OBS_ONLY) {  // a14 reward / termination (PredatorCapturePrey.py:155-176, 209-216)
@@ -1232,7 +1242,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             obs_row[1] = y;
             obs_row[2] = loaded ? 1.0f : 0.0f;
         }
-        write_neighbour_obs<GW, 3, NT, SPAN>(lds, N, RG_ARG(p.num_neighbors), ag, gbase, lane_nb, x, y, obs_row);
+        write_neighbour_obs<GW, 3, NT, SPAN>(lds, N, RG_SHAPED(M, RG_ARG(p.num_neighbors)), ag, gbase, lane_nb, x, y, obs_row);
         if constexpr (!OBS_ONLY) {
             if (viol) {
                 reward = RG_ARG(p.violation_reward);
@@ -1378,7 +1388,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             obs_row[4] = static_cast<float>(zone1);
 #pragma unroll
             for (int i = 0; i < 4; ++i) obs_row[5 + i] = static_cast<float>(msg[i]);
-            if (RG_ARG(p.capability_aware)) {
+            if (RG_SHAPED(CA, RG_ARG(p.capability_aware))) {
                 if constexpr (TEAM) obs_row[9] = static_cast<float>(tq_raw);
                 else obs_row[9] = static_cast<float>(p.torque[ag]);
                 obs_row[10] = agent_step;
@@ -1544,7 +1554,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                     }
                 }
                 if constexpr (SCN == RG_SCN_PREDATOR_CAPTURE_PREY || SCN == RG_SCN_SIMPLE) {
-                    const int P = RG_ARG_OR(p.num_prey, q_P);
+                    const int P = RG_SHAPED(P, RG_ARG_OR(p.num_prey, q_P));
                     const auto nb = RG_ARG_OR(a.st.next_init, q_nin) + static_cast<size_t>(e) * RG_ARG_OR(a.next_stride, q_nst) + 3 * N;
                     for (int i = ag; i < P; i += GW) {  // prey `ag` was prefetched; more than GW prey: the rest from the block
                         const auto pl = RG_ARG(a.st.prey_loc) + (static_cast<size_t>(e) * P + i) * 2;
@@ -1598,6 +1608,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
 #undef RG_ARG_OFF
 #undef RG_ARG_OR
 #undef RG_OUT
+#undef RG_SHAPED
 
 // ------------------------------------------------------------------ the step kernels: four families, one body
 // The step comes in four families of kernels: plain; with the lidar on (rg_set_lidar: the range block of lidar.h written at the
@@ -1720,6 +1731,21 @@ __global__ __launch_bounds__(WAVE) void step_kernel(const KernelArgs *image, con
     const StepView sv = {actions, io, &auto_reset, &seed, grid};
     step_once<SCN, GW, false, NT, true, false, 0, void, WgSync, false, false, true, false, true>(a, lds, sv);
 }
+// ... and the resident kernel of a reference shape (kernel_args.h RG_REF_SHAPES): SH's fields are constants of the body.  The same
+// parameters, image and flags; instantiated in robogym_resident_shapes.hip alone.  (One more overload: every kernel above keeps
+// its name, and these share the leading template arguments that the profile tools match the headline kernel by.)
+template <int SCN, int GW, bool OBS_ONLY, int NT, bool ROLLOUT, int ROW, bool RESIDENT, class SH, std::enable_if_t<ROW == 16 && RESIDENT, int> = 0>
+__global__ __launch_bounds__(WAVE) void step_kernel(const KernelArgs *image, const int32_t *actions, const uint64_t seed, const int32_t auto_reset,
+                                                    const int32_t grid, const rg_step_io io) {
+    static_assert(GW == 8 && !OBS_ONLY && !ROLLOUT, "the 16-lane rows: the single-step launch at GW 8");
+    typedef const __attribute__((address_space(4))) KernelArgs *ConstImage;
+    ConstImage ci = (ConstImage)image;
+    asm volatile("" : "+s"(ci));
+    const KernelArgs &a = *(const KernelArgs *)ci;
+    __shared__ Lds<GW> lds;
+    const StepView sv = {actions, io, &auto_reset, &seed, grid};
+    step_once<SCN, GW, false, NT, true, false, 0, void, WgSync, false, false, true, false, true, SH>(a, lds, sv);
+}
 #endif
 // generic agent count (NT = 0) throughout
 template <int SCN, int GW, bool OBS_ONLY, bool ROLLOUT, bool GYM, int QPM>
@@ -1823,8 +1849,9 @@ static hipError_t launch_gw(const typename F::Args &args, const GroupSide &side,
             }
         };
         if constexpr (ROWS) {
-            // rows, and the handle has a valid image: the resident form of the same kernel (robogym_resident.hip)
-            if (rows && side.image) return launch_step_resident(args, side, stream);
+            // rows, and the handle has a valid image: the resident form of the same kernel (robogym_resident.hip), or, where the
+            // image's block matched a reference shape (kernel_args.h match_shape), that shape's (robogym_resident_shapes.hip)
+            if (rows && side.image) return side.shape ? launch_step_shape(args, side, stream) : launch_step_resident(args, side, stream);
         }
         if (ROWS && rows) by_n(std::integral_constant<bool, ROWS>());
         else by_n(std::false_type());

@@ -387,6 +387,15 @@ class VecRobotariumEnv(object):
         (robogym_capi.hip: tpe_min_envs; RG_STEP_KERNEL forces one).  Results are bit-identical either way."""
         return "tpe" if self.lib.rg_step_kernel(self._h) == 1 else "group"
 
+    @property
+    def step_form(self):
+        """Which form the last `step` launch took (_lib.FORM_*): by value, resident, or resident with a reference shape's id added
+        to FORM_SHAPE."""
+        form = self.lib.rg_step_form(self._h)
+        if form < 0:
+            _lib.check(form, "rg_step_form")
+        return form
+
     def step_raw(self, actions_ptr):
         """Hot-loop entry: one rg_step on a pre-validated device pointer to int32 [E,N]; results are
         in self.obs / reward / done_u8 / dist_travelled / violation / remaining.  Launches on the stream of
