@@ -35,6 +35,20 @@ struct Consts {
 //    change times the offset), so |f_i(u) - f_j(u)| >= |f_i(u0) - f_j(u0)| - 2 (u - u0) max(m): one test of sub-step u0
 //    against lin_pre + 2 span max(m) stands for sub-steps u0 .. u0 + span.  Valid while the widened threshold stays
 //    below 0.24 m (the binary16 difference is then below 0.25 m per axis, where its own rounding is <= 2^-14 m).
+// WHERE "never misses" holds.  The collision bound is computed for collision points within the arena's largest |coordinate|
+// plus 0.25 m (make_consts below) and for the constants rg_create admits (include/robogym.h, rps constants): arena corners within
+// 100 m of the origin, collision limits up to 1 m, |collision_offset| + |dt v| <= 0.25 m -- so a robot inside the arena, or one
+// sub-step beyond a wall, has its collision point inside that range.  Over that domain tests/test_physical_regimes.py emulates
+// the rounding and finds the figure below thr_pre with about half the margin to spare.  A robot FARTHER out can only have been
+// put there (rg_bind_state, a restored snapshot: poses are state, not parameters): at |x| >= 4 m the default arena's bound is
+// already too small, near 1000 m a robot shares a binary16 cell with a ghost point, beyond 65504 m every point rounds to the
+// same one.  Such a robot is outside the arena when the step begins, so the boundary pre-test fires, the step's first chunk
+// reaches the exact replay, and the boundary test ends the env in the step's FIRST sub-step.  That sub-step is the only one in
+// which the binary16 figure can be wrong, and the lane-group kernel's replay runs its exact pair rounds there whenever a robot
+// of the wave is outside the arena, whatever the figure says (step_group.h).  Every later sub-step keeps consulting the figure
+// (which sub-steps need pair rounds), and that rests on the domain rule above: a robot that WALKS out is tested one sub-step
+// past the wall, |collision_offset| + |dt v| <= 0.25 m from the arena, where the bound still holds, and its env ends there.
+// The thread-per-env kernel's replay runs the whole exact test anyway.  A needless replay is all a far robot otherwise costs.
 constexpr float PRE_SLACK = 2e-6f;  // roundings of the position updates and of xc / xh
 inline float pre_margin(float max_abs_coordinate) {
     float spacing = 0.0009765625f;  // 2^-10: binary16 spacing in [1, 2)

@@ -112,6 +112,44 @@ static int fail(int code, const char *fmt, const char *detail = "") {
     return code;
 }
 
+// The rps constants' admitted domain (include/robogym.h "rps constants"): every limit is stated there with its reason.
+// !(v > lo) also refuses a NaN; the message names the field.
+static int check_constants(const rg_scenario_params *p) {
+    const char *const msg = "rps constant %s is outside its admitted domain (include/robogym.h, rps constants)";
+    const struct {
+        const char *name;
+        float v, hi;
+    } positive[] = {{"time_step", p->time_step, 1.0f},
+                    {"bound_w", p->bound_w, 200.0f},
+                    {"bound_h", p->bound_h, 200.0f},
+                    {"robot_diameter", p->robot_diameter, 1.0f},
+                    {"wheel_radius", p->wheel_radius, 1.0f},
+                    {"max_linear_velocity", p->max_linear_velocity, 2.0f},
+                    {"collision_diameter", p->collision_diameter, 1.0f},
+                    {"projection_distance", p->projection_distance, 1.0f},
+                    {"angular_velocity_limit", p->angular_velocity_limit, 100.0f},
+                    {"position_velocity_limit", p->position_velocity_limit, 2.0f}};
+    for (const auto &f : positive)
+        if (!(f.v > 0.0f && f.v <= f.hi)) return fail(-15, msg, f.name);
+    if (!(p->projection_distance >= 1e-4f)) return fail(-15, msg, "projection_distance");
+    // the arena: every corner coordinate within 100 m of the origin (the binary16 pre-test, csrc/kernel_args.h)
+    if (!(fabsf(p->bound_x0) <= 100.0f)) return fail(-15, msg, "bound_x0");
+    if (!(fabsf(p->bound_y0) <= 100.0f)) return fail(-15, msg, "bound_y0");
+    if (!(fabsf(p->bound_x0 + p->bound_w) <= 100.0f)) return fail(-15, msg, "bound_w");
+    if (!(fabsf(p->bound_y0 + p->bound_h) <= 100.0f)) return fail(-15, msg, "bound_h");
+    // a collision point stays within 0.25 m of the arena until the boundary test has fired: one sub-step's travel + the offset
+    if (!(fabsf(p->collision_offset) + p->time_step * p->max_linear_velocity <= 0.25f)) return fail(-15, msg, "collision_offset");
+    // the heading advances min(update_frequency, controller_period) sub-steps at once and is wrapped once: at most one turn
+    const float wmax = 2.0f * (p->wheel_radius / p->robot_diameter) * (p->max_linear_velocity / p->wheel_radius);
+    if (!(wmax > 0.0f && wmax <= 1e6f))
+        return fail(-15, msg, "wheel_radius / robot_diameter / max_linear_velocity (wmax = 2 (wheel_radius / robot_diameter)(max_linear_velocity / wheel_radius) must lie in (0, 1e6])");
+    const float w = fminf(p->angular_velocity_limit, wmax);
+    const int n = p->update_frequency < p->controller_period ? p->update_frequency : p->controller_period;
+    if (!(static_cast<float>(n) * p->time_step * w <= 6.2831853f))
+        return fail(-15, "rps constant %s: a controller period turns a robot by more than 2 pi (include/robogym.h, rps constants)", "time_step");
+    return 0;
+}
+
 static int check_params(const rg_scenario_params *p) {
     if (!p) return fail(-1, "params is NULL");
     if (p->scenario < RG_SCN_PREDATOR_CAPTURE_PREY || p->scenario > RG_SCN_ARCTIC_TRANSPORT)
@@ -156,7 +194,7 @@ static int check_params(const rg_scenario_params *p) {
     } else {
         if (p->obs_dim < (p->capability_aware ? 11 : 9)) return fail(-10, "obs_dim too small for MaterialTransport");
     }
-    return 0;
+    return check_constants(p);
 }
 
 // rg_policy_rollout's kernels live in their own translation units (robogym_policy_h64.hip, robogym_policy_h128.hip).  Declared

@@ -921,7 +921,15 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                         const bool bnd = lane_ok & !dead & ((rx < k.xmin) | (rx > k.xmax) | (ry < k.ymin) | (ry > k.ymax));
                         const float fx = __builtin_fmaf(k.coll_off, rc, rx), fy = __builtin_fmaf(k.coll_off, rs, ry);
                         bool col = false;
-                        if (!__any(dmin_u[u] <= thr_pre)) {
+                        // The binary16 figure is a bound for collision points within 0.25 m of the arena only (kernel_args.h).
+                        // A robot farther out was put there before the step (a loaded pose; one that walks out ends its env
+                        // at the wall) and ends its env in the step's FIRST sub-step: there, with a robot of the wave outside
+                        // the arena, the pair rounds run whatever the figure says.
+                        bool pairs = __any(dmin_u[u] <= thr_pre);
+                        if constexpr (u == 0) {
+                            if ((it0 | j0) == 0) pairs = pairs || __any(bnd);
+                        }
+                        if (!pairs) {
                             // no pair of this sub-step is within the pre-test band: no collision possible
                         } else if constexpr (GW == 8 && NT >= 5 && NT <= 7) {  // same pair cover as the pre-test: 3 + (N-4) rounds
                             static_for<1, 4>([&](auto KK) {

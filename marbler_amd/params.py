@@ -33,6 +33,13 @@ QP_RTOL = 1.25e-6
 QP_MAX_SWEEPS = 40
 
 
+# the rps constants of rg_scenario_params (the simulated GRITSBot and its arena) and their values
+RPS_CONSTANTS = {"time_step": 0.033, "bound_x0": -1.6, "bound_y0": -1.0, "bound_w": 3.2, "bound_h": 2.0,
+                 "robot_diameter": 0.11, "wheel_radius": 0.016, "max_linear_velocity": 0.2,
+                 "collision_offset": 0.025, "collision_diameter": 0.135,
+                 "projection_distance": 0.05, "angular_velocity_limit": math.pi, "position_velocity_limit": 0.15}
+
+
 def default_config_path(scenario):
     return os.path.join(CONFIG_DIR, scenario + ".yaml")
 
@@ -120,11 +127,13 @@ def make_params(scenario, cfg):
     p.qp_rtol = float(cfg.get("qp_rtol", QP_RTOL))
     p.qp_max_sweeps = int(cfg.get("qp_max_sweeps", QP_MAX_SWEEPS))
     p.collision_variant = COLLISION_VARIANTS[cfg.get("collision_variant", DEFAULT_COLLISION_VARIANT)]
-    p.time_step = 0.033
-    p.bound_x0, p.bound_y0, p.bound_w, p.bound_h = -1.6, -1.0, 3.2, 2.0
-    p.robot_diameter, p.wheel_radius, p.max_linear_velocity = 0.11, 0.016, 0.2
-    p.collision_offset, p.collision_diameter = 0.025, 0.135
-    p.projection_distance, p.angular_velocity_limit, p.position_velocity_limit = 0.05, math.pi, 0.15
+    # the rps constants: config keys of the block's own field names override them; the library states and
+    # checks the domain each admits (include/robogym.h "rps constants", rg_create)
+    for key, val in RPS_CONSTANTS.items():
+        v = cfg.get(key, val)
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{key} must be a number (got {v!r})")
+        setattr(p, key, float(v))
     L, R, U, D = cfg["LEFT"], cfg["RIGHT"], cfg["UP"], cfg["DOWN"]
     p.left, p.right, p.up, p.down = L, R, U, D
     height = D - U

@@ -71,6 +71,12 @@ QP_RTOL = {"float32": 1.25e-6, "float64": 5e-12}
 QP_MAX_SWEEPS = {"float32": 40, "float64": 200}
 
 
+RPS_CONSTANTS = {"time_step": 0.033, "bound_x0": -1.6, "bound_y0": -1.0, "bound_w": 3.2, "bound_h": 2.0,
+                 "robot_diameter": 0.11, "wheel_radius": 0.016, "max_linear_velocity": 0.2,
+                 "collision_offset": 0.025, "collision_diameter": 0.135,
+                 "projection_distance": 0.05, "angular_velocity_limit": np.pi, "position_velocity_limit": 0.15}
+
+
 def params_from_config(scenario, cfg, collision_variant="offset", dtype=np.float64):
     """YAML keys of the reference's scenario config.yaml -> orc_params (Appendix A/B constants)."""
     p = OrcParams()
@@ -96,11 +102,10 @@ def params_from_config(scenario, cfg, collision_variant="offset", dtype=np.float
     p.unsafe_barrier_gain = cfg.get("unsafe_barrier_gain", 1e6)
     p.barrier_magnitude_limit = cfg.get("magnitude_limit", 0.2)
     p.collision_variant = {"center": 0, "offset": 1}[cfg.get("collision_variant", collision_variant)]
-    p.time_step = 0.033
-    p.bound_x0, p.bound_y0, p.bound_w, p.bound_h = -1.6, -1.0, 3.2, 2.0
-    p.robot_diameter, p.wheel_radius, p.max_linear_velocity = 0.11, 0.016, 0.2
-    p.collision_offset, p.collision_diameter = 0.025, 0.135
-    p.projection_distance, p.angular_velocity_limit, p.position_velocity_limit = 0.05, np.pi, 0.15
+    # the rps constants: a config key of the field's own name replaces the value (tests/physical_cases.py); oracle_core.h reads
+    # every one of them from the block
+    for key, val in RPS_CONSTANTS.items():
+        setattr(p, key, float(cfg.get(key, val)))
     p.left, p.right, p.up, p.down = cfg["LEFT"], cfg["RIGHT"], cfg["UP"], cfg["DOWN"]
     if scenario == "PredatorCapturePrey":
         npred, ncap = int(cfg["predator"]), int(cfg["capture"])

@@ -38,7 +38,8 @@ def _check_against_twin(obs, poses, env, L=1.0, max_degenerate=1e-3, exact_zero=
     """obs [E, N, D] (device), poses [E, 3, N] the stored poses the step built it from.  Returns the number of rays compared."""
     R, off = int(env.lidar.rays), int(env.lidar.offset)
     got = obs[..., off:off + R].double().cpu().numpy()
-    want, deg = lidar_batch(poses.cpu().numpy(), R, L, RHO, bounds_of(env.params))
+    rho = float(np.float32(0.5) * np.float32(env.params.robot_diameter))   # (= RHO at the default constants)
+    want, deg = lidar_batch(poses.cpu().numpy(), R, L, rho, bounds_of(env.params))
     ok = ~deg
     assert deg.sum() <= max_degenerate * deg.size, (int(deg.sum()), deg.size)
     err = np.abs(got - want)[ok]

@@ -60,13 +60,19 @@ def test_rollout_bit_exact(scenario, ov, n_act, steps, oracle_lib):
     _rollout_bit_exact(scenario, ov, n_act, steps, oracle_lib, 192)
 
 
-def _rollout_bit_exact(scenario, ov, n_act, steps, oracle_lib, E, require_done=True):
+def _rollout_bit_exact(scenario, ov, n_act, steps, oracle_lib, E, require_done=True, constants=None, after_step=None):
+    """constants: the rps constants among `ov` (tests/physical_cases.py): both sides' parameter blocks are held to them, and to the
+    defaults elsewhere, before the first step.  after_step(env, t): what a caller asserts about the launch (rg_step_form)."""
     import torch
     from marbler_amd import VecRobotariumEnv
     seed = 99
     env = VecRobotariumEnv(scenario, E, overrides=ov, seed=seed, auto_reset=True, collect_qp_stats=True)
     cfg = dict(env.cfg)
     orc = oracle_lib.OracleVecEnv(scenario, cfg, E, dtype=np.float32)
+    if constants is not None:
+        from physical_cases import check_constants
+        check_constants(env.params, constants)
+        check_constants(orc.p, constants)
     rp = oracle_reset_params(oracle_lib, env.params)
     env.reset()
     episodes = np.zeros(E, np.int64)
@@ -109,6 +115,8 @@ def _rollout_bit_exact(scenario, ov, n_act, steps, oracle_lib, E, require_done=T
         # state after the (possibly reset) step
         assert np.array_equal(env.poses.cpu().numpy().view(np.uint32), orc.poses.view(np.uint32)), t
         assert np.array_equal(env.episode_steps.cpu().numpy(), orc.steps), t
+        if after_step is not None:
+            after_step(env, t)
     assert n_done > 0 or E < 8 or not require_done
     assert np.array_equal(env.done_count.cpu().numpy(), episodes)
     assert np.array_equal(env.done_return_sum.cpu().numpy().view(np.uint32), ret_sum.view(np.uint32))

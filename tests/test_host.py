@@ -9,6 +9,8 @@ import socket
 import numpy as np
 import pytest
 
+from physical_cases import ARENAS, CHOICES, REGIMES, arena
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -65,6 +67,36 @@ def test_create_rejects_bad_parameters_without_touching_a_gpu():
     q.agent_grid.ny = 2
     assert not lib.rg_create(ctypes.byref(q), 4, 0, 0, None) and b"reset grid" in lib.rg_last_error()
     assert not lib.rg_create(ctypes.byref(base()), 0, 0, 0, None) and b"num_envs" in lib.rg_last_error()
+    # the rps constants' admitted domain (include/robogym.h): per field a NaN, a value at or below its lower limit (zero or
+    # negative where the field must be positive; the three signed fields: far below) and one beyond its upper limit
+    for field, low, high in (("time_step", 0.0, 1.5), ("bound_x0", -1e3, 150.0), ("bound_y0", -1e3, 150.0),
+                             ("bound_w", 0.0, 250.0), ("bound_h", -2.0, 250.0), ("robot_diameter", 0.0, 1.5),
+                             ("wheel_radius", -0.016, 1.5), ("max_linear_velocity", 0.0, 2.5), ("collision_offset", -0.5, 0.5),
+                             ("collision_diameter", 0.0, 1.5), ("projection_distance", 0.0, 1.5),
+                             ("angular_velocity_limit", -3.14, 150.0), ("position_velocity_limit", 0.0, 2.5)):
+        for value in (float("nan"), low, high, float("inf")):
+            q = base()
+            setattr(q, field, value)
+            assert not lib.rg_create(ctypes.byref(q), 4, 0, 0, None), (field, value)
+            err = lib.rg_last_error()
+            assert b"rps constant" in err and field.encode() in err, (field, value, err)
+    # relations between fields: a sub-step's travel plus the offset beyond 0.25 m; a controller period of more than one turn
+    for changes, field in (({"time_step": 0.5, "max_linear_velocity": 0.5, "update_frequency": 1}, b"collision_offset"),
+                           ({"time_step": 0.2, "angular_velocity_limit": 3.0}, b"time_step")):
+        q = base()
+        for k, v in changes.items():
+            setattr(q, k, v)
+        assert not lib.rg_create(ctypes.byref(q), 4, 0, 0, None), changes
+        assert b"rps constant" in lib.rg_last_error() and field in lib.rg_last_error(), (changes, lib.rg_last_error())
+    # ... and every value of the GPU tier's tables lies inside (tests/physical_cases.py): the refusal is then the missing device
+    sets = [dict(r[1], **{k: v for k, v in r[2].items() if k == "update_frequency"}) for r in REGIMES]
+    sets += [{k: v} for k, vals in CHOICES.items() for v in vals] + [arena(*a) for a in ARENAS]
+    for consts in sets:
+        q = make_params("PredatorCapturePrey", load_config("PredatorCapturePrey", overrides=consts))
+        h = lib.rg_create(ctypes.byref(q), 4, 0, 0, None)
+        assert h or b"rps constant" not in lib.rg_last_error(), (consts, lib.rg_last_error())
+        if h:
+            lib.rg_destroy(h)
 
 
 def test_actor_entry_points_reject_bad_arguments_without_touching_a_gpu():
