@@ -13,7 +13,6 @@
 
 namespace rg {
 
-constexpr int WAVE = 64;
 constexpr int MAX_DRAWS = 128;  // u32 draws per reset: 4 + 2N + P <= 4 + 32 + 64, rounded up to blocks
 
 // ------------------------------------------------------------------ workgroup -> env chunk (XCD-aware)

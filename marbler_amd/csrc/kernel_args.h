@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "../../include/robogym.h"
+#include "launch_plan.h"
 
 namespace rg {
 
@@ -94,7 +95,7 @@ struct KernelArgs {
     const int32_t *actions;
     const uint8_t *reset_mask;
     int32_t E;
-    int32_t envs_per_wave; // lane-group kernel: env slots used per wavefront (0 = all 64/GW; fewer for small batches, see wave_fill)
+    int32_t envs_per_wave; // lane-group kernel: env slots used per wavefront (0 = all 64/GW); set from LaunchPlan::envs_per_wave (launch_plan.h)
     int32_t num_steps;  // env steps per launch (rg_step: 1); io and actions carry a leading dimension of this size
     int32_t auto_reset;
     int32_t reset_flags;  // rg_reset: RG_RESET_*
@@ -131,9 +132,8 @@ hipError_t launch_reset(const KernelArgs &a, hipStream_t stream);
 // pool (rg_set_teams), with the pose disturbance (rg_set_disturbance) -- and every (family, solver mode, launch kind) has a translation unit of its own with ONE entry, so that
 // they compile side by side and each gets its mode's flags (build.py FILE_FLAGS).  The list: X(entry, family, qp_mode, kind).
 // An observation-only launch (rg_get_obs) runs no controller: it exists in the exact mode only and serves both.  The disturbance
-// family has none: rg_get_obs displaces nothing, and a disturbed handle's goes to the plain entry.
-enum GroupFamily { GROUP_PLAIN, GROUP_LIDAR, GROUP_TEAM, GROUP_DISTURB };
-enum GroupKind { GROUP_STEP, GROUP_ROLLOUT, GROUP_OBS, GROUP_STEP_RESIDENT, GROUP_STEP_SHAPE };
+// family has none: rg_get_obs displaces nothing, and a disturbed handle's goes to the plain entry.  (GroupFamily, GroupKind and
+// the plan that selects a row: launch_plan.h.)
 #define RG_GROUP_ENTRIES(X)                                              \
     X(launch_step, GROUP_PLAIN, RG_QP_EXACT, GROUP_STEP)                 \
     X(launch_step_resident, GROUP_PLAIN, RG_QP_EXACT, GROUP_STEP_RESIDENT) \
@@ -168,16 +168,16 @@ struct GroupSide {
     const rg_lidar_params *lidar;
     const rg_team_params *teams;
     const DisturbScale *disturb;
-    const struct KernelArgs *image;   // the handle's resident image on the device (below), or null: the launch goes by value
-    int shape;                        // the reference shape the image's block matched (below: match_shape), or 0
+    const struct KernelArgs *image;   // the handle's resident image on the device (below), or null; read where plan.resident
+    const LaunchPlan &plan;           // the launch as plan_launch named it (launch_plan.h): every launcher reads it and derives nothing
 };
 
 // The resident form of the 16-lane-row step kernels (robogym_resident.hip).  What rg_create / rg_bind_state fix -- p, k, st, E,
-// envs_per_wave as the dispatcher computes it, next_stride, env_offset -- lies in an IMAGE of the block in device memory that the
+// envs_per_wave as the plan names it, next_stride, env_offset -- lies in an IMAGE of the block in device memory that the
 // handle owns, written where one of them changes and never again once a launch may read it (a change takes a fresh slot), and
 // the kernel takes the image's address and the per-call arguments alone: 136 bytes of kernel arguments instead of 0.8 KB, the
-// leading ones handed over in scalar registers (build.py RESIDENT_PRELOAD).  GROUP_STEP_RESIDENT is the dispatcher's own kind
-// (step_group.h launch_gw calls it where it chooses rows and has an image); rg_step never asks for it.
+// leading ones handed over in scalar registers (build.py RESIDENT_PRELOAD).  GROUP_STEP_RESIDENT is the plan's own kind
+// (launch_plan.h: rows, and the handle has an image); no call asks for it.
 struct ResidentCall {   // the kernel-argument segment of a resident kernel (its parameters in this order)
     const KernelArgs *image;
     const int32_t *actions;
@@ -187,8 +187,8 @@ struct ResidentCall {   // the kernel-argument segment of a resident kernel (its
     rg_step_io io;
 };
 static_assert(sizeof(ResidentCall) <= 256, "the per-call arguments fit one register of dwords (device_common.h load_arg_regs_resident)");
-// the image of a handle's block: the per-call members cleared, envs_per_wave as launch_group sets it
-hipError_t resident_image(KernelArgs &a);
+// the image of a handle's block: the per-call members cleared, envs_per_wave as the handle's plain single step's plan names it
+void resident_image(KernelArgs &a, const LaunchPlan &plan);
 
 // SHAPES.  Seven members of the parameter block are fixed by rg_create for the handle's life, yet a kernel that reads them at run
 // time pays for the question on every launch: loops with clamps over the prey and the neighbour rows, both observation formats,
@@ -238,8 +238,8 @@ inline bool shape_row(int id, int32_t out[10]) {
 #undef RG_X
     return false;
 }
-// (the resident launch of shape side.shape: launch_step_shape, robogym_resident_shapes.hip; GROUP_STEP_SHAPE is the dispatcher's
-// own kind, like GROUP_STEP_RESIDENT)
+// (the resident launch of shape plan.shape: launch_step_shape, robogym_resident_shapes.hip; GROUP_STEP_SHAPE is the plan's own
+// kind, like GROUP_STEP_RESIDENT)
 typedef hipError_t GroupLaunch(const KernelArgs &a, const GroupSide &side, hipStream_t stream);
 #define RG_X(entry, family, mode, kind) GroupLaunch entry;
 RG_GROUP_ENTRIES(RG_X)

@@ -79,7 +79,7 @@ __global__ __launch_bounds__(64 * (H / 32)) void policy_rollout_sample_kernel(co
 template <int SCN, int H, bool SAMPLE>
 static hipError_t launch_policy_scn(const PolicyArgs &pa_in, hipStream_t stream) {
     PolicyArgs pa = pa_in;
-    const int gw = SCN == RG_SCN_ARCTIC_TRANSPORT ? 4 : group_width(pa.k.p.n_agents);
+    const int gw = group_width(pa.k.p.n_agents);
     pa.k.envs_per_wave = WAVE / gw;
     const int grid = (pa.k.E + WAVE / gw - 1) / (WAVE / gw);
     const dim3 block(64 * (H / 32));

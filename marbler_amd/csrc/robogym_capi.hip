@@ -22,26 +22,26 @@ struct rg_handle {
     int32_t device;
     hipStream_t stream;
     bool bound;
-    bool use_tpe;  // step with the thread-per-env kernel (robogym_tpe.hip) instead of the lane-group kernel
+    // What the launch plan (launch_plan.h) takes from the handle: the side block that is on and the switches rg_create read from
+    // the environment (RG_STEP_KERNEL, RG_STEP_SPAN, RG_STEP_RESIDENT, RG_STEP_SHAPE), and what refresh() caches of its answer.
+    rg::PlanHandle sw;
+    bool use_tpe;      // step with the thread-per-env kernel (robogym_tpe.hip) instead of the lane-group kernel
+    bool want_image;   // the handle's plain single step takes 16-lane rows: it can use a resident image
     bool seed_seen;      // the precomputed-reset blocks (rg_state.next_init) were drawn with last_seed
     uint64_t last_seed;
-    bool default_tpe;    // use_tpe as rg_create chose it (restored when the lidar, the team pool and the disturbance are all off)
     rg_lidar_params lidar;   // rays == 0: off (rg_set_lidar)
     rg_team_params teams;    // n_sets == 0: no pool (rg_set_teams)
     bool disturbed;          // the pose disturbance is on (rg_set_disturbance), with the scales below
     rg::DisturbScale disturb;
-    bool span;           // rg_step's lane-group launch may put an env on a 16-lane row (step_group.h); RG_STEP_SPAN=0 forces 8-lane groups
     // The resident image of the argument block (kernel_args.h ResidentCall): what rg_create / rg_bind_state fix, in device memory
     // of the handle's device, for the resident form of the row kernels.  An image is IMMUTABLE once written: a launch -- or a
     // captured graph that replays one -- may read it at any later time.  Whatever alters it (a re-bind; rg_set_*) makes the
     // current one stale, and the next one is written into a fresh slot; the slots live until rg_destroy.  No valid image (the
     // slots used up, no memory, a write due while the stream is being captured, RG_STEP_RESIDENT=0): the launch goes by value.
-    bool resident;               // RG_STEP_RESIDENT=0 at rg_create: by-value launches only
     rg::KernelArgs *image_slots; // device: RG_IMAGE_SLOTS slots of RG_IMAGE_STRIDE bytes (allocated with the first image)
     int32_t images_used;
     const rg::KernelArgs *image; // the image of the handle as it is now, or null
-    bool shapes;                 // RG_STEP_SHAPE=0 at rg_create: the generic kernels only (A/B runs, tests)
-    // The reference shape that `image`'s block matched (kernel_args.h match_shape; 0: none, or `shapes` is off): decided where the
+    // The reference shape that `image`'s block matched (kernel_args.h match_shape; 0: none, or RG_STEP_SHAPE=0): decided where the
     // image is written, so a change that makes the image stale is matched again with the next one.
     int32_t image_shape;
     mutable int32_t last_form;   // rg_step_form: RG_FORM_* of the last rg_step launch
@@ -56,34 +56,17 @@ static void drop_image(rg_handle *h) {   // the handle changes: its image no lon
     h->image_shape = 0;
     h->image_stale = true;
 }
-
-// Which step kernel: both give identical results.  The lane-group kernel has the shorter chain for
-// small batches and is linear in the batch; the thread-per-env kernel's time is a step function of how many
-// generations of wavefronts the batch needs (65 536 envs per generation and wave slot per SIMD), so it takes
-// over where one of its steps undercuts the line.  Measured cross-overs on MI355X, final kernels of round 3
-// (tools/crossover_probe.py, profiles/r3_crossover_probe.txt): the sparse collision pre-test made
-// the lane-group kernel 5-8 % faster at these batch sizes and moved every threshold up from round 2's 53 248 / 65 536;
-// the one-division restart of the barrier QP then favoured the lane-group kernel at N = 6, where the thread-per-env kernel
-// runs on spilled registers, and compiling the thread-per-env files without the SLP vectoriser (build.py FILE_FLAGS: 57 fewer
-// spilled values at N = 6, -22 %) gave most of that back: the table below is the last measurement of round 3.
-// For N >= 7 the per-lane register footprint (28 pairs) leaves one wave per SIMD and the lane-group kernel -- at
-// 92 % VALU issue there -- stays ahead at every batch size.  RG_STEP_KERNEL=group|tpe forces one (tests, profiling).
-static int32_t tpe_min_envs(const rg_scenario_params &p) {
-    const bool mt = p.scenario == RG_SCN_MATERIAL_TRANSPORT, pcp = p.scenario == RG_SCN_PREDATOR_CAPTURE_PREY;
-    // RG_QP_CVXOPT: the launch is the interior-point iteration, one wave per SIMD in either kernel.  A lane group carries one env
-    // through it in ~0.7 x the time a single lane needs, a wavefront of lanes carries eight times as many: the lane-group kernel
-    // while its waves fit the chip at once (8 192 envs), the other one from the second generation on.  Measured ladder, round 5
-    // (tools/ipm_probe.py --cross, profiles/r5_ipm_crossover.jsonl): N = 5  8 192 envs 166 vs 211 us, 16 384 290 vs 215;
-    // N = 4  16 384 95 vs 95, 24 576 157 vs 99; at 65 536 x 5 981 vs 260 us.
-    if (p.qp_mode == RG_QP_CVXOPT) return p.n_agents == 5 ? 12288 : 20480;
-    switch (p.n_agents) {
-        case 2: return 65536;
-        case 3: return pcp ? 98304 : 65536;
-        case 4: return p.scenario == RG_SCN_SIMPLE ? 393216 : p.scenario == RG_SCN_ARCTIC_TRANSPORT ? 131072 : 196608;
-        case 5: return mt ? 49152 : 65536;
-        case 6: return mt ? 65536 : p.scenario == RG_SCN_WAREHOUSE ? 262144 : pcp ? 98304 : 131072;
-        default: return INT32_MAX;
-    }
+// The plan of a launch of the handle as it is now.
+static rg::LaunchPlan plan(const rg_handle *h, int kind, bool gym = false) {
+    return rg::plan_launch(h->params, h->num_envs, h->sw, rg::PlanCall{kind, gym, h->image != nullptr, h->image_shape});
+}
+// The handle has changed (rg_create, rg_set_*, rg_bind_state): what it caches of the plan is computed again, and its image no
+// longer describes it.
+static void refresh(rg_handle *h) {
+    h->sw.side = h->teams.n_sets ? rg::GROUP_TEAM : h->lidar.rays ? rg::GROUP_LIDAR : h->disturbed ? rg::GROUP_DISTURB : rg::GROUP_PLAIN;
+    drop_image(h);
+    h->use_tpe = plan(h, rg::GROUP_STEP).tpe;
+    h->want_image = rg::image_wanted(h->params, h->num_envs, h->sw);
 }
 
 static thread_local char g_err[512] = "";
@@ -214,7 +197,7 @@ hipError_t launch_policy_rollout_sample_h128(const KernelArgs &, const rg_actor_
 RG_GROUP_ENTRIES(RG_X)
 #undef RG_X
 hipError_t launch_team_index(const KernelArgs &, const rg_team_params &, hipStream_t) __attribute__((weak));
-hipError_t resident_image(KernelArgs &) __attribute__((weak));
+void resident_image(KernelArgs &, const LaunchPlan &) __attribute__((weak));
 }  // namespace rg
 
 // The scenario's own observation width: the columns its builder writes (the lidar block may start at or after it).
@@ -300,34 +283,24 @@ rg_handle *rg_create(const rg_scenario_params *params, int32_t num_envs, int64_t
     h->bound = false;
     h->seed_seen = false;
     h->last_seed = 0;
-    h->use_tpe = rg::tpe_supported(*params) && num_envs >= tpe_min_envs(*params);
-    if (const char *force = getenv("RG_STEP_KERNEL")) {
-        if (!strcmp(force, "group")) h->use_tpe = false;
-        else if (!strcmp(force, "tpe") && rg::tpe_supported(*params)) h->use_tpe = true;
-    }
-    h->default_tpe = h->use_tpe;
-    {
-        const char *span = getenv("RG_STEP_SPAN");
-        h->span = !(span && !strcmp(span, "0"));
-    }
-    {
-        const char *res = getenv("RG_STEP_RESIDENT");
-        h->resident = !(res && !strcmp(res, "0")) && rg::resident_image && rg::launch_step_resident;
-    }
-    {
-        const char *shp = getenv("RG_STEP_SHAPE");
-        h->shapes = !(shp && !strcmp(shp, "0")) && rg::launch_step_shape;
-    }
-    h->image_shape = 0;
+    const auto on = [](const char *name) {   // a switch that only "0" turns off
+        const char *v = getenv(name);
+        return !(v && !strcmp(v, "0"));
+    };
+    const char *force = getenv("RG_STEP_KERNEL");
+    h->sw.force = !force ? rg::KERNEL_DEFAULT : !strcmp(force, "group") ? rg::KERNEL_GROUP : !strcmp(force, "tpe") ? rg::KERNEL_TPE : rg::KERNEL_DEFAULT;
+    h->sw.tpe_supported = rg::tpe_supported(*params);
+    h->sw.span = on("RG_STEP_SPAN");
+    h->sw.resident = on("RG_STEP_RESIDENT") && rg::resident_image && rg::launch_step_resident;
+    h->sw.shapes = on("RG_STEP_SHAPE") && rg::launch_step_shape;
     h->last_form = RG_FORM_NONE;
     h->image_slots = nullptr;
     h->images_used = 0;
-    h->image = nullptr;
-    h->image_stale = true;
     memset(&h->lidar, 0, sizeof(h->lidar));
     memset(&h->teams, 0, sizeof(h->teams));
     h->disturbed = false;
     h->disturb = rg::DisturbScale{0.0f, 0.0f};
+    refresh(h);
     return h;
 }
 
@@ -335,8 +308,7 @@ int rg_set_lidar(rg_handle *h, const rg_lidar_params *lp) {
     if (!h) return fail(-1, "handle is NULL");
     if (!lp || lp->rays == 0) {
         memset(&h->lidar, 0, sizeof(h->lidar));
-        h->use_tpe = (h->teams.n_sets || h->disturbed) ? false : h->default_tpe;
-        drop_image(h);
+        refresh(h);
         return 0;
     }
     if (h->disturbed) return fail(-57, "rg_set_lidar: the handle has the pose disturbance on (rg_set_disturbance); the disturbance and the lidar do not combine");
@@ -350,8 +322,7 @@ int rg_set_lidar(rg_handle *h, const rg_lidar_params *lp) {
     if (!(lp->range > 0.0f && lp->range <= 3.402823466e38f)) return fail(-53, "rg_set_lidar: range must be positive and finite");
     if (!group_family_built(rg::GROUP_LIDAR)) return fail(-100, "rg_set_lidar: this build has no lidar kernels");
     h->lidar = *lp;
-    h->use_tpe = false;   // the lidar is built into the lane-group kernel only
-    drop_image(h);
+    refresh(h);
     return 0;
 }
 
@@ -360,8 +331,7 @@ int rg_set_disturbance(rg_handle *h, const rg_disturbance_params *dp) {
     if (!dp || (dp->sigma_xy == 0.0f && dp->sigma_theta == 0.0f)) {
         h->disturbed = false;
         h->disturb = rg::DisturbScale{0.0f, 0.0f};
-        h->use_tpe = (h->lidar.rays || h->teams.n_sets) ? false : h->default_tpe;
-        drop_image(h);
+        refresh(h);
         return 0;
     }
     // (a NaN fails both comparisons)
@@ -374,8 +344,7 @@ int rg_set_disturbance(rg_handle *h, const rg_disturbance_params *dp) {
     if (!group_family_built(rg::GROUP_DISTURB)) return fail(-100, "rg_set_disturbance: this build has no disturbance kernels");
     h->disturb = rg::DisturbScale{rg::disturb_scale(dp->sigma_xy), rg::disturb_scale(dp->sigma_theta)};
     h->disturbed = true;
-    h->use_tpe = false;   // the disturbance is built into the lane-group kernel only
-    drop_image(h);
+    refresh(h);
     return 0;
 }
 
@@ -427,7 +396,7 @@ int rg_bind_state(rg_handle *h, const rg_state *st) {
     if (reinterpret_cast<uintptr_t>(st->next_init) & 15u) return fail(-26, "next_init must be 16-byte aligned");
     h->state = *st;
     h->bound = true;
-    drop_image(h);
+    refresh(h);
     write_image(h);   // (no image is no error: the steps go by value until one can be written)
     // whatever the rebound next_init / next_episode arrays hold was not drawn by this handle under a seed it knows:
     // the first rg_step / rg_rollout after a bind marks every block stale (sync_seed), whatever the caller put there
@@ -447,9 +416,8 @@ static int fill_args(rg_handle *h, rg::KernelArgs &a);
 static void write_image(rg_handle *h) {
     h->image = nullptr;
     h->image_shape = 0;
-    if (!h->resident || !h->bound || h->use_tpe || !h->span || h->teams.n_sets || h->lidar.rays || h->disturbed ||
-        h->params.qp_mode != RG_QP_EXACT) {
-        h->image_stale = false;   // no row kernel serves this handle as it is; a change marks it stale again
+    if (!h->sw.resident || !h->bound || !h->want_image) {
+        h->image_stale = false;   // no row kernel serves this handle as it is (launch_plan.h image_wanted); a change marks it stale again
         return;
     }
     if (h->images_used >= RG_IMAGE_SLOTS) {
@@ -457,10 +425,8 @@ static void write_image(rg_handle *h) {
         return;
     }
     rg::KernelArgs a;
-    if (fill_args(h, a) != 0 || rg::resident_image(a) != hipSuccess) {
-        h->image_stale = false;   // (not a shape of the row kernels)
-        return;
-    }
+    (void)fill_args(h, a);   // (bound: it cannot fail)
+    rg::resident_image(a, plan(h, rg::GROUP_STEP));
     DeviceGuard guard(h->device);
     if (guard.err != hipSuccess) return;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -486,7 +452,7 @@ static void write_image(rg_handle *h) {
         return;
     }
     h->image = slot;
-    h->image_shape = h->shapes ? rg::match_shape(a.p) : 0;
+    h->image_shape = h->sw.shapes ? rg::match_shape(a.p) : 0;
 }
 
 static int fill_args(rg_handle *h, rg::KernelArgs &a) {
@@ -533,25 +499,12 @@ static int launched(hipError_t err) {
     return 0;
 }
 
-// RG_FORM_*: the form a step launch takes in the dispatcher (step_group.h launch_gw).  A handle has an image only where the
-// dispatcher chooses rows for it (write_image: RG_STEP_SPAN allows them, resident_image has checked agent count and batch size), so
-// an image means the resident form, and its shape's kernel where one matched.
-static int32_t step_form(const rg::KernelArgs *image, int shape) {
-    return !image ? RG_FORM_BY_VALUE : shape ? RG_FORM_SHAPE + shape : RG_FORM_RESIDENT;
-}
-
-// The lane-group launch of a handle: the family its side blocks select (a pool, the lidar and the disturbance exclude one
-// another), the handle's solver mode -- an observation-only launch runs no controller and uses the exact mode's kernel in either,
-// and displaces nothing: a disturbed handle's is the plain family's -- and the launch kind.
-static int launch_group_entry(const rg_handle *h, const rg::KernelArgs &a, int kind, const rg::KernelArgs *image = nullptr) {
-    const int family = h->teams.n_sets ? rg::GROUP_TEAM : h->lidar.rays ? rg::GROUP_LIDAR
-                       : (h->disturbed && kind != rg::GROUP_OBS) ? rg::GROUP_DISTURB : rg::GROUP_PLAIN;
-    const int mode = kind == rg::GROUP_OBS ? RG_QP_EXACT : h->params.qp_mode;
-    const bool res = family == rg::GROUP_PLAIN && image;
-    const rg::GroupSide side = {&h->lidar, &h->teams, &h->disturb, res ? image : nullptr, res ? h->image_shape : 0};
-    if (kind == rg::GROUP_STEP) h->last_form = step_form(side.image, side.shape);
+// The lane-group launch that `pl` names: its row of RG_GROUP_ENTRIES, the block with envs_per_wave as the kernel is to see it.
+static int launch_group_entry(const rg_handle *h, rg::KernelArgs &a, const rg::LaunchPlan &pl) {
+    a.envs_per_wave = pl.envs_per_wave;
+    const rg::GroupSide side = {&h->lidar, &h->teams, &h->disturb, h->image, pl};
     for (const GroupEntry &g : g_group)
-        if (g.family == family && g.mode == mode && g.kind == kind && g.launch) return launched(g.launch(a, side, h->stream));
+        if (g.family == pl.family && g.mode == pl.mode && g.kind == pl.kind && g.launch) return launched(g.launch(a, side, h->stream));
     return fail(-100, "this build has no lane-group step kernels");
 }
 
@@ -580,15 +533,11 @@ int rg_step(rg_handle *h, const int32_t *actions, const rg_step_io *io, int32_t 
     a.seed = seed;
     RG_ON_DEVICE(h);
     if (int rc = sync_seed(h, seed)) return rc;
-    // (asks the plain family's dispatcher for 8-lane groups throughout: it sets the real value itself)
-    if (!h->span && !h->teams.n_sets && !h->lidar.rays && !h->disturbed) a.envs_per_wave = -1;
-    if (h->use_tpe) {
-        h->last_form = RG_FORM_BY_VALUE;
-        return launched(rg::launch_step_tpe(a, h->stream));
-    }
     if (h->image_stale) write_image(h);
-    // (the dispatcher takes the resident form where it chooses rows; the gymma block has kernels of its own)
-    return launch_group_entry(h, a, rg::GROUP_STEP, io->elapsed ? nullptr : h->image);
+    const rg::LaunchPlan pl = plan(h, rg::GROUP_STEP, io->elapsed != nullptr);
+    h->last_form = pl.form;   // (the struct that selects the kernel)
+    if (pl.tpe) return launched(rg::launch_step_tpe(a, h->stream));
+    return launch_group_entry(h, a, pl);
 }
 
 int rg_rollout(rg_handle *h, const int32_t *actions, int32_t num_steps, const rg_step_io *io, int32_t auto_reset,
@@ -610,7 +559,8 @@ int rg_rollout(rg_handle *h, const int32_t *actions, int32_t num_steps, const rg
     a.seed = seed;
     RG_ON_DEVICE(h);
     if (int rc = sync_seed(h, seed)) return rc;
-    if (!h->use_tpe) return launch_group_entry(h, a, rg::GROUP_ROLLOUT);
+    const rg::LaunchPlan pl = plan(h, rg::GROUP_ROLLOUT);
+    if (!pl.tpe) return launch_group_entry(h, a, pl);
     // thread-per-env: the multi-step kernel holds more values live (313 VGPRs at N = 5: one wave per
     // SIMD); it pays while the batch is at most one wave per SIMD (the latency regime), beyond that
     // num_steps single-step launches are faster (measured at 524288 envs: 166 vs 197 us per step)
@@ -684,8 +634,7 @@ int rg_set_teams(rg_handle *h, const rg_team_params *tp) {
     if (!h) return fail(-1, "handle is NULL");
     if (!tp || tp->n_sets == 0) {
         memset(&h->teams, 0, sizeof(h->teams));
-        h->use_tpe = (h->lidar.rays || h->disturbed) ? false : h->default_tpe;
-        drop_image(h);
+        refresh(h);
         return 0;
     }
     if (h->disturbed) return fail(-65, "rg_set_teams: the handle has the pose disturbance on (rg_set_disturbance); the disturbance and a pool do not combine");
@@ -708,8 +657,7 @@ int rg_set_teams(rg_handle *h, const rg_team_params *tp) {
         if (int rc = launched(rg::launch_team_index(a, *tp, h->stream))) return rc;
     }
     h->teams = *tp;
-    h->use_tpe = false;   // the pool is built into the lane-group kernel only
-    drop_image(h);
+    refresh(h);
     return 0;
 }
 
@@ -740,7 +688,7 @@ int rg_get_obs(rg_handle *h, float *obs) {
     if (reinterpret_cast<uintptr_t>(obs) & 15u) return fail(-26, "obs must be 16-byte aligned");
     a.io.obs = obs;
     RG_ON_DEVICE(h);
-    return launch_group_entry(h, a, rg::GROUP_OBS);
+    return launch_group_entry(h, a, plan(h, rg::GROUP_OBS));
 }
 
 }  // extern "C"

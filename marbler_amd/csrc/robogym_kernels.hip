@@ -15,8 +15,8 @@ hipError_t launch_obs(const KernelArgs &a, const GroupSide &side, hipStream_t st
 hipError_t launch_reset(const KernelArgs &a, hipStream_t stream) {
     return for_scenario(a.p.scenario, [&](auto scn) -> hipError_t {
         constexpr int SCN = decltype(scn)::value;
-        const int gw = SCN == RG_SCN_ARCTIC_TRANSPORT ? 4 : group_width(a.p.n_agents);
-        const int grid = (a.E + WAVE / gw - 1) / (WAVE / gw);
+        const LaunchPlan pl = plan_launch(a.p, a.E, PlanHandle{}, PlanCall{GROUP_RESET, false, false, 0});   // (the same for every handle)
+        const int gw = pl.gw, grid = pl.grid;
         if (gw == 4) hipLaunchKernelGGL((reset_kernel<SCN, 4>), dim3(grid), dim3(WAVE), 0, stream, a);
         else if constexpr (SCN != RG_SCN_ARCTIC_TRANSPORT) {
             if (gw == 8) hipLaunchKernelGGL((reset_kernel<SCN, 8>), dim3(grid), dim3(WAVE), 0, stream, a);

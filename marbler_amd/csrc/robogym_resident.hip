@@ -5,7 +5,7 @@
 
 namespace rg {
 
-hipError_t resident_image(KernelArgs &a) {
+void resident_image(KernelArgs &a, const LaunchPlan &plan) {
     a.io = rg_step_io{};
     a.actions = nullptr;
     a.reset_mask = nullptr;
@@ -13,13 +13,11 @@ hipError_t resident_image(KernelArgs &a) {
     a.reset_flags = 0;
     a.seed = 0;
     a.num_steps = 1;
-    if (a.p.scenario == RG_SCN_ARCTIC_TRANSPORT || group_width(a.p.n_agents) != 8) return hipErrorInvalidValue;   // no row kernel
-    a.envs_per_wave = wave_fill(a.E, 8).epw;
-    return a.envs_per_wave <= 4 ? hipSuccess : hipErrorInvalidValue;   // (more than 4096 envs: 8-lane groups)
+    a.envs_per_wave = plan.envs_per_wave;
 }
 
 // `a`: the launch's block as rg_step filled it (its per-call members are the kernel's arguments); side.image: the image of the
-// same handle.  Called by the dispatcher where it has chosen rows (step_group.h launch_gw).
+// same handle.  The entry of a plan with `resident` and no shape (launch_plan.h).
 hipError_t launch_step_resident(const KernelArgs &a, const GroupSide &side, hipStream_t stream) {
     if constexpr (kStampsBuild) {
         return hipErrorInvalidValue;   // (a stamps build has no row kernels)
@@ -29,9 +27,9 @@ hipError_t launch_step_resident(const KernelArgs &a, const GroupSide &side, hipS
             if constexpr (SCN == RG_SCN_ARCTIC_TRANSPORT) {
                 return hipErrorInvalidValue;
             } else {
-                const int grid = wave_fill(a.E, 8).grid;
+                const int grid = side.plan.grid;
                 const dim3 g(grid), b(WAVE);
-                switch (a.p.n_agents) {
+                switch (side.plan.nt) {
                     case 5: hipLaunchKernelGGL((step_kernel<SCN, 8, false, 5, false, 16, true>), g, b, 0, stream, side.image, a.actions, a.seed, a.auto_reset, grid, a.io); break;
                     case 6: hipLaunchKernelGGL((step_kernel<SCN, 8, false, 6, false, 16, true>), g, b, 0, stream, side.image, a.actions, a.seed, a.auto_reset, grid, a.io); break;
                     case 7: hipLaunchKernelGGL((step_kernel<SCN, 8, false, 7, false, 16, true>), g, b, 0, stream, side.image, a.actions, a.seed, a.auto_reset, grid, a.io); break;

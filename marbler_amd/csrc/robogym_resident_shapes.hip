@@ -6,16 +6,16 @@
 
 namespace rg {
 
-// `a`, `side` as launch_step_resident takes them; side.shape: the row of the table that the image's block matched (match_shape:
+// `a`, `side` as launch_step_resident takes them; side.plan.shape: the row of the table that the image's block matched (match_shape:
 // the host has compared every field the kernel assumes).  A shape this build does not hold is an error, not a fall-back.
 hipError_t launch_step_shape(const KernelArgs &a, const GroupSide &side, hipStream_t stream) {
     if constexpr (kStampsBuild) {
         return hipErrorInvalidValue;   // (a stamps build has no row kernels)
     } else {
-        const int grid = wave_fill(a.E, 8).grid;
+        const int grid = side.plan.grid;
         const dim3 g(grid), b(WAVE);
 #define RG_X(id, scn, n, P, D, M, CA, U, PERIOD, PENALIZE)                                                                            \
-    if (side.shape == (id)) {                                                                                                        \
+    if (side.plan.shape == (id)) {                                                                                                      \
         if (a.p.scenario != (scn) || a.p.n_agents != (n)) return hipErrorInvalidValue;                                               \
         hipLaunchKernelGGL((step_kernel<scn, 8, false, n, false, 16, true, Shape<P, D, M, CA, U, PERIOD, PENALIZE>>), g, b, 0, stream, \
                            side.image, a.actions, a.seed, a.auto_reset, grid, a.io);                                                 \

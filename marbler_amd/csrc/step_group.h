@@ -1801,24 +1801,9 @@ __global__ __launch_bounds__(WAVE) void reset_kernel(const KernelArgs a) {
 
 
 // ------------------------------------------------------------------ host side: launch dispatch
+// A switch from the values of the launch's plan (launch_plan.h: the one place that decides) to template arguments.  Nothing is
+// derived here; the `if constexpr` guards only keep instantiations that no plan names out of the build.
 namespace rg {
-
-inline int group_width(int N) { return N <= 4 ? 4 : N <= 8 ? 8 : 16; }
-
-// A batch that leaves SIMDs idle with full wavefronts runs with partly filled ones instead (more
-// waves, each carrying fewer envs, as long as there is at most one wave per SIMD: 1024): a wave's
-// time is the maximum over its envs (QP sweeps, replays, resets), and the idle SIMDs are free.
-// (A stamps build keeps full waves: its eight slots are the wave's first eight envs.)
-struct WaveFill {
-    int epw, grid;   // env slots used per wave, waves
-};
-inline WaveFill wave_fill(int E, int gw) {
-    int epw = WAVE / gw;
-    if constexpr (!kStampsBuild) {
-        while (epw >= 2 && (E + epw / 2 - 1) / (epw / 2) <= RG_MAX_WAVES) epw /= 2;
-    }
-    return {epw, (E + epw - 1) / epw};
-}
 
 // one launch of family F's __global__ template (ROWS: the plain family's 16-lane-row overload)
 template <class F, int SCN, int GW, bool OBS_ONLY, int NT, bool ROLLOUT, bool GYM, int QPM, bool ROWS = false>
@@ -1830,76 +1815,54 @@ static void launch_kernel(const typename F::Args &args, int grid, hipStream_t st
     else hipLaunchKernelGGL((step_kernel<SCN, GW, OBS_ONLY, NT, ROLLOUT, GYM, QPM>), dim3(grid), dim3(WAVE), 0, stream, args);
 }
 
-// The kernel of (family, scenario, launch kind, mode) at group width gw.  Generic agent count (NT = 0), except GW 8 of the exact
-// mode's step and rollout in the plain and team families: bodies specialised for the agent count (NT = N, 5..8).  The gymma
-// block's, the observation-only, the interior-point and every lidar and disturbance kernel are generic.  rows: the 16-lane-row
-// kernel instead.
+// The kernel of (family, scenario, launch kind, mode) at pl.gw, pl.nt and pl.rows.  (The resident forms of a row kernel are
+// entries of their own, robogym_resident*.hip: the plan's kind selects them.)
 template <class F, int SCN, bool OBS_ONLY, bool ROLLOUT, bool GYM, int QPM>
-static hipError_t launch_gw(const typename F::Args &args, const GroupSide &side, int gw, int n, bool rows, int grid, hipStream_t stream) {
+static hipError_t launch_gw(const typename F::Args &args, const LaunchPlan &pl, hipStream_t stream) {
     constexpr bool EXACT = QPM == RG_QP_EXACT;
     constexpr bool BY_N = EXACT && !OBS_ONLY && !GYM && !F::LIDAR && !F::NOISE;
     constexpr bool ROWS = BY_N && !ROLLOUT && !F::TEAM && !kStampsBuild;
-    if (gw == 4) {
-        launch_kernel<F, SCN, 4, OBS_ONLY, 0, ROLLOUT, GYM, QPM>(args, grid, stream);
+    if (pl.gw == 4) {
+        launch_kernel<F, SCN, 4, OBS_ONLY, 0, ROLLOUT, GYM, QPM>(args, pl.grid, stream);
     } else if constexpr (SCN == RG_SCN_ARCTIC_TRANSPORT) {
         return hipErrorInvalidValue;   // (rg_create admits exactly 4 agents)
-    } else if (gw == 16) {
-        if constexpr (EXACT) launch_kernel<F, SCN, 16, OBS_ONLY, 0, ROLLOUT, GYM, QPM>(args, grid, stream);
+    } else if (pl.gw == 16) {
+        if constexpr (EXACT) launch_kernel<F, SCN, 16, OBS_ONLY, 0, ROLLOUT, GYM, QPM>(args, pl.grid, stream);
         else return hipErrorInvalidValue;   // (rg_create admits n_agents <= 8 in the interior-point mode)
     } else if constexpr (BY_N) {
         auto by_n = [&](auto rows_c) {
             constexpr bool R = decltype(rows_c)::value;
-            switch (n) {
-                case 5: launch_kernel<F, SCN, 8, false, 5, ROLLOUT, false, QPM, R>(args, grid, stream); break;
-                case 6: launch_kernel<F, SCN, 8, false, 6, ROLLOUT, false, QPM, R>(args, grid, stream); break;
-                case 7: launch_kernel<F, SCN, 8, false, 7, ROLLOUT, false, QPM, R>(args, grid, stream); break;
-                default: launch_kernel<F, SCN, 8, false, 8, ROLLOUT, false, QPM, R>(args, grid, stream); break;
+            switch (pl.nt) {
+                case 5: launch_kernel<F, SCN, 8, false, 5, ROLLOUT, false, QPM, R>(args, pl.grid, stream); break;
+                case 6: launch_kernel<F, SCN, 8, false, 6, ROLLOUT, false, QPM, R>(args, pl.grid, stream); break;
+                case 7: launch_kernel<F, SCN, 8, false, 7, ROLLOUT, false, QPM, R>(args, pl.grid, stream); break;
+                default: launch_kernel<F, SCN, 8, false, 8, ROLLOUT, false, QPM, R>(args, pl.grid, stream); break;
             }
         };
-        if constexpr (ROWS) {
-            // rows, and the handle has a valid image: the resident form of the same kernel (robogym_resident.hip), or, where the
-            // image's block matched a reference shape (kernel_args.h match_shape), that shape's (robogym_resident_shapes.hip)
-            if (rows && side.image) return side.shape ? launch_step_shape(args, side, stream) : launch_step_resident(args, side, stream);
-        }
-        if (ROWS && rows) by_n(std::integral_constant<bool, ROWS>());
+        if (ROWS && pl.rows) by_n(std::integral_constant<bool, ROWS>());
         else by_n(std::false_type());
     } else {
-        launch_kernel<F, SCN, 8, OBS_ONLY, 0, ROLLOUT, GYM, QPM>(args, grid, stream);
+        launch_kernel<F, SCN, 8, OBS_ONLY, 0, ROLLOUT, GYM, QPM>(args, pl.grid, stream);
     }
     return hipGetLastError();
 }
 
 // The lane-group launch of family F: every translation unit's entry is one instantiation of this (OBS_ONLY exists for the single
-// launch of the exact mode only: an observation runs no controller).
+// launch of the exact mode only: an observation runs no controller).  `a` as the caller filled it, envs_per_wave from the plan.
 template <class F, bool OBS_ONLY, bool ROLLOUT, int QPM>
-static hipError_t launch_group(const KernelArgs &a_in, const GroupSide &side, hipStream_t stream) {
+static hipError_t launch_group(const KernelArgs &a, const GroupSide &side, hipStream_t stream) {
     static_assert(!OBS_ONLY || (!ROLLOUT && QPM == RG_QP_EXACT), "rg_get_obs is a single launch of the exact mode's kernel");
     static_assert(!OBS_ONLY || !F::NOISE, "rg_get_obs of a disturbed handle is the plain family's launch");
-    return for_scenario(a_in.p.scenario, [&](auto scn) -> hipError_t {
+    return for_scenario(a.p.scenario, [&](auto scn) -> hipError_t {
         constexpr int SCN = decltype(scn)::value;
-        constexpr bool ARCTIC = SCN == RG_SCN_ARCTIC_TRANSPORT;
-        if constexpr (ARCTIC && F::TEAM) {
+        if constexpr (SCN == RG_SCN_ARCTIC_TRANSPORT && F::TEAM) {
             return hipErrorInvalidValue;   // refused by rg_set_teams: the scenario fixes its agent types
         } else {
-            KernelArgs a = a_in;
-            // ArcticTransport: four agents, full waves, envs_per_wave as it came
-            int gw = 4;
-            WaveFill wf = {WAVE / 4, (a.E + 15) / 16};
-            if constexpr (!ARCTIC) {
-                gw = group_width(a.p.n_agents);
-                wf = wave_fill(a.E, gw);
-                if constexpr (!kStampsBuild) a.envs_per_wave = wf.epw;
-            }
             const typename F::Args args = F::args(a, side);
             if constexpr (!OBS_ONLY && !ROLLOUT) {
-                if (a.io.elapsed)   // gymma block: its own instantiations
-                    return launch_gw<F, SCN, false, false, true, QPM>(args, side, gw, a.p.n_agents, false, wf.grid, stream);
+                if (side.plan.gym) return launch_gw<F, SCN, false, false, true, QPM>(args, side.plan, stream);   // gymma block: its own instantiations
             }
-            // at most 4 envs per wave (batches up to 4096 envs): each env on a 16-lane row, the upper half a replica that takes
-            // over part of the order-free work (step_once SPAN; the plain family's exact single step at GW 8).  A negative
-            // envs_per_wave on entry (rg_step under RG_STEP_SPAN=0, rg_create) keeps 8-lane groups.
-            const bool rows = a_in.envs_per_wave >= 0 && wf.epw <= 4;
-            return launch_gw<F, SCN, OBS_ONLY, ROLLOUT, false, QPM>(args, side, gw, a.p.n_agents, rows, wf.grid, stream);
+            return launch_gw<F, SCN, OBS_ONLY, ROLLOUT, false, QPM>(args, side.plan, stream);
         }
     });
 }

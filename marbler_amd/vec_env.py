@@ -384,7 +384,7 @@ class VecRobotariumEnv(object):
     @property
     def step_kernel(self):
         """'group' (a lane group per env) or 'tpe' (one lane per env): the kernel this env's handle launches
-        (robogym_capi.hip: tpe_min_envs; RG_STEP_KERNEL forces one).  Results are bit-identical either way."""
+        (launch_plan.h: tpe_min_envs; RG_STEP_KERNEL forces one).  Results are bit-identical either way."""
         return "tpe" if self.lib.rg_step_kernel(self._h) == 1 else "group"
 
     @property

@@ -27,7 +27,7 @@ MODES = {
     "msan": ["-fsanitize=memory", "-fsanitize-memory-track-origins=2", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"],
     "plain": [],
 }
-DEPS = [os.path.join(CSRC, h) for h in ("step_tpe.h", "device_common.h", "kernel_args.h", "sim_math.h")] + \
+DEPS = [os.path.join(CSRC, h) for h in ("step_tpe.h", "device_common.h", "kernel_args.h", "launch_plan.h", "sim_math.h")] + \
        [os.path.join(ROOT, "include", "robogym.h"), os.path.join(ROOT, "oracle", "oracle.c"), os.path.join(ROOT, "oracle", "oracle_core.h"),
         os.path.join(ROOT, "oracle", "oracle.h"), os.path.join(HERE, "tpe_host.cpp"), os.path.join(HERE, "tpe_host_inst.cpp"),
         os.path.join(HERE, "hip_shim", "hip", "hip_runtime.h"), os.path.abspath(__file__)]

@@ -1,7 +1,7 @@
 """BASELINE.json's batch shapes and every dispatch width of the lane-group kernel against the float32 oracle.
 
 The lane-group launch picks the number of env slots a wavefront uses from the batch size (`wave_fill`,
-csrc/step_group.h): at 8 lanes per env a batch of <= 1024 envs runs 1 env per wave, 2048 -> 2, 4096 -> 4 (the
+csrc/launch_plan.h): at 8 lanes per env a batch of <= 1024 envs runs 1 env per wave, 2048 -> 2, 4096 -> 4 (the
 headline: 1024 workgroups through the XCD-aware chunk map), >= 8192 -> 8; at 4 lanes per env the steps are 1 / 2 / 4 /
 8 / 16.  The other oracle-checked rollouts (tests/test_gpu_rollout.py) stay below 1024 envs = one env per wave, so
 these cases put the lane -> env map the driver's bench line times -- and the per-GPU shapes of configs[2] .. [4] --
@@ -47,7 +47,7 @@ CASES = [
 
 
 def expected_slots(N, E):
-    """wave_fill's rule (csrc/step_group.h), restated: halve the env slots per wave while the batch still fits 1024 waves."""
+    """wave_fill's rule (csrc/launch_plan.h), restated: halve the env slots per wave while the batch still fits 1024 waves."""
     gw = 4 if N <= 4 else 8 if N <= 8 else 16
     epw = 64 // gw
     while epw >= 2 and (E + epw // 2 - 1) // (epw // 2) <= 1024:

@@ -186,7 +186,7 @@ def test_step_is_deterministic_and_shard_invariant():
     ("MaterialTransport", {"n_agents": 6, "n_fast_agents": 3, "n_slow_agents": 3, "start_dist": 0.25}, 20, 98304, "tpe"),
     ("Warehouse", {"n_agents": 8}, 5, 65536, "group")])                                        # N >= 7: always the lane-group kernel
 def test_large_batch_dispatch_matches_lane_group_kernel(scenario, ov, n_act, E, auto_kernel, monkeypatch):
-    """The library's own kernel choice at large batches (robogym_capi.hip: tpe_min_envs; `rg_step_kernel` says which one
+    """The library's own kernel choice at large batches (launch_plan.h: tpe_min_envs; `rg_step_kernel` says which one
     a handle launches) and the thread-per-env kernel forced, against the lane-group kernel forced: every output and the
     whole state bit for bit, over steps that include auto-resets.  Warehouse 65536 x 8: N >= 7 runs the lane-group kernel
     whatever is asked for (the thread-per-env instantiations for N = 7, 8 left the library in round 4)."""

@@ -1,6 +1,6 @@
 """Every lane-group kernel family with several envs sharing a wavefront.
 
-`wave_fill` (csrc/step_group.h) gives a batch of up to 1024 envs one env per wave; a wave carries 2, 4, 8 or 16 envs only above
+`wave_fill` (csrc/launch_plan.h) gives a batch of up to 1024 envs one env per wave; a wave carries 2, 4, 8 or 16 envs only above
 1024 / 2048 / 4096 / 8192 envs (by group width), and only then can one env's lanes disturb another's: DPP and ballots confined to
 `gbase`, LDS rows indexed by `g`, the interior-point workspace `qp->ws[lane / GW]`, `team_index[e]` and `elapsed[e]` fetched per
 env, one env's lanes masked while its neighbours still iterate.  tests/test_gpu_baseline_shapes.py holds the plain family's exact

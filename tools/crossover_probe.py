@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where the thread-per-env kernel overtakes the lane-group kernel, per agent count: us per step of both at a ladder
-of batch sizes (robogym_capi.hip: tpe_min_envs).    python tools/crossover_probe.py [N ...]"""
+of batch sizes (launch_plan.h: tpe_min_envs).    python tools/crossover_probe.py [N ...]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -24,7 +24,7 @@ SHAPES = [("PredatorCapturePrey", {"predator": 3, "capture": 2, "n_agents": 5}, 
 
 def cross(steps=30):
     """Both step kernels in the interior-point mode over a ladder of batch sizes (RG_STEP_KERNEL is read by rg_create): where the
-    one-lane-per-env kernel takes over (robogym_capi.hip tpe_min_envs)."""
+    one-lane-per-env kernel takes over (launch_plan.h tpe_min_envs)."""
     dev = torch.device("cuda", 0)
     for scenario, ov, n_act in (("PredatorCapturePrey", {"predator": 3, "capture": 2, "n_agents": 5}, 5), ("PredatorCapturePrey", {}, 5)):
         for E in (4096, 8192, 16384, 24576, 32768, 65536, 131072):
