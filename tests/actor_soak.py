@@ -10,14 +10,13 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import test_gpu_actor as T  # noqa: E402
+from gpu_helpers import fused_actor_random_shape  # noqa: E402
 
 draws = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
 first = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
 t0 = time.time()
-fn = getattr(T.test_fused_actor_random_shapes, "__wrapped__", T.test_fused_actor_random_shapes)
 for i in range(draws):
-    fn(first + i)
+    fused_actor_random_shape(first + i)
     if (i + 1) % 250 == 0:
         print(f"{i + 1} draws ok ({time.time() - t0:.0f} s)", flush=True)
 print(f"actor soak: {draws} draws from seed {first}: all within 1e-5, greedy actions equal")

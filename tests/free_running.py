@@ -73,12 +73,10 @@ def compare(a, b, what="", nsigma=3.0, skip=()):
 
 def run_oracle(oracle_lib, scenario, cfg, rg_params, E, steps, n_act, dtype, seed, action_seed, threads=8):
     """The C oracle free-running with the reset twin (float-spec sampler; its values are exact in float64 too)."""
-    from helpers import oracle_reset, oracle_reset_params
-    orc = oracle_lib.OracleVecEnv(scenario, cfg, E, dtype=dtype)
-    rp = oracle_reset_params(oracle_lib, rg_params)
-    for e in range(E):
-        oracle_reset(oracle_lib, orc, rp, seed, e, 0)
-    episodes = np.zeros(E, np.int64)
+    from oracle_check import FreeRunningOracle
+    side = FreeRunningOracle(oracle_lib, scenario, cfg, E, rg_params, seed, dtype=dtype)
+    side.reset()
+    orc = side.orc
     rng = np.random.RandomState(action_seed)
     tally = Tally(E, int(cfg["max_episode_steps"]) + 1)
     shared = bool(rg_params.shared_reward)
@@ -86,9 +84,7 @@ def run_oracle(oracle_lib, scenario, cfg, rg_params, E, steps, n_act, dtype, see
         a = rng.randint(0, n_act, size=(E, orc.N)).astype(np.int32)
         obs, rew, done, info = orc.step(a, threads=threads)
         tally.add(rew[:, 0].astype(np.float64) if shared else rew.astype(np.float64).sum(axis=1), done, info["violation"], info["remaining"])
-        for e in np.nonzero(done)[0]:
-            episodes[e] += 1
-            oracle_reset(oracle_lib, orc, rp, seed, e, int(episodes[e]))
+        side.reset_ended()
     return tally.summary()
 
 

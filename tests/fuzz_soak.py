@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""One-off fuzz campaign on a GPU box: draws [first, first + count) of tests/test_gpu_config_fuzz.py's EXTENDED generator,
+"""One-off fuzz campaign on a GPU box: draws [first, first + count) of tests/fuzz_cases.py's EXTENDED generator,
 each a free-running rollout of the HIP kernels against the float32 oracle, bit for bit.
     python tests/fuzz_soak.py [first] [count] [seconds] [--ipm]   (stops at the time budget; prints one summary line)
---ipm: the draws of test_gpu_config_fuzz.draw_interior_point instead (barrier_solver: cvxopt, n_agents <= 8, certificate family and
+--ipm: the draws of fuzz_cases.draw_interior_point instead (barrier_solver: cvxopt, n_agents <= 8, certificate family and
 cvxopt's own options drawn too)."""
 import os
 import sys
@@ -23,9 +23,9 @@ def main():
     budget = float(argv[3]) if len(argv) > 3 else 600.0
     from oracle import c_oracle
     c_oracle.build_library()
-    from test_gpu_config_fuzz import draw_config_extended, draw_interior_point
+    from fuzz_cases import draw_config_extended, draw_interior_point
     draw = draw_interior_point if ipm else draw_config_extended
-    from test_gpu_rollout import _rollout_bit_exact
+    from rollout_harness import rollout_bit_exact
     from marbler_amd.params import load_config, make_params
     t0, done, rejected, env_steps, failures = time.time(), 0, 0, 0, []
     per_scn = {}
@@ -41,7 +41,7 @@ def main():
         os.environ["RG_STEP_KERNEL"] = kernel
         steps = 30 if scenario != "MaterialTransport" else 20
         try:
-            _rollout_bit_exact(scenario, ov, n_act, steps, c_oracle, E, require_done=False)
+            rollout_bit_exact(scenario, ov, n_act, steps, c_oracle, E, require_done=False)
         except AssertionError as exc:
             failures.append((i, scenario, ov, E, kernel, str(exc)[:300]))
             print("FAIL", failures[-1], flush=True)

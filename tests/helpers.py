@@ -5,11 +5,9 @@ import os
 
 import numpy as np
 
+from oracle_check import GPU_NAME, STATE_KEYS, load_oracle  # noqa: F401  (the key tables live there; re-exported)
+
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-STATE_KEYS = ("poses", "carry", "steps", "prey_loc", "prey_sensed", "prey_captured", "loaded", "load",
-              "zone_load", "messages", "grid", "goal_col", "pixel_type", "reached_goal")
-GPU_NAME = {"carry": "carry_dist", "steps": "episode_steps"}
-FLAT = ("goal_col",)
 
 
 def golden_files():
@@ -31,9 +29,7 @@ def oracle_from_state(c_oracle, scenario, cfg, state, dtype):
     """One oracle env per fixture row, loaded with the row's pre-step state."""
     T = len(state["poses"])
     env = c_oracle.OracleVecEnv(scenario, cfg, T, dtype=dtype)
-    for k, v in state.items():
-        arr = getattr(env, k)
-        arr[...] = np.asarray(v).astype(arr.dtype).reshape(arr.shape)
+    load_oracle(env, state)
     return env
 
 

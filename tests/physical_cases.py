@@ -11,7 +11,7 @@ RPS_DEFAULTS = {"time_step": 0.033, "bound_x0": -1.6, "bound_y0": -1.0, "bound_w
                 "robot_diameter": 0.11, "wheel_radius": 0.016, "max_linear_velocity": 0.2,
                 "collision_offset": 0.025, "collision_diameter": 0.135,
                 "projection_distance": 0.05, "angular_velocity_limit": float(np.pi), "position_velocity_limit": 0.15}
-SEED, ACTION_SEED = 99, 5                      # test_gpu_rollout._rollout_bit_exact's own
+SEED, ACTION_SEED = 99, 5                      # rollout_harness.rollout_bit_exact's own
 STEPS, EPISODE = 30, 10
 
 PCP4 = {"predator": 2, "capture": 2, "n_agents": 4}
@@ -120,6 +120,15 @@ def draw_physical(rng, draw_config):
     ov = dict(ov, **draw_constants(rng))
     ov["max_episode_steps"] = int(rng.choice([3, 7, 12]))
     return scenario, ov, n_act, E, kernel
+
+
+def _fuzz_cases():
+    from fuzz_cases import draw_config, draw_interior_point
+    return ([draw_physical(np.random.RandomState(9000 + i), draw_config) for i in range(96)],
+            [draw_physical(np.random.RandomState(9500 + i), draw_interior_point) for i in range(24)])
+
+
+CASES, IPM_CASES = _fuzz_cases()          # the seeded fuzz over all 13 constants, exact and interior-point mode
 
 
 # ---------------------------------------------------------------- binary16, as the collision pre-test rounds (csrc/kernel_args.h)

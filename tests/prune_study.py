@@ -5,7 +5,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from oracle import c_oracle
-from helpers import oracle_reset, oracle_reset_params
+from oracle_check import FreeRunningOracle
 from marbler_amd.params import load_config, make_params
 
 c_oracle.build_library()
@@ -13,11 +13,9 @@ scenario, ov, n_act = "PredatorCapturePrey", {"predator": 3, "capture": 2, "n_ag
 cfg = load_config(scenario, None, ov)
 p = make_params(scenario, cfg)
 E, T = 4096, 120
-env = c_oracle.OracleVecEnv(scenario, cfg, E, dtype=np.float32)
-rp = oracle_reset_params(c_oracle, p)
-for e in range(E):
-    oracle_reset(c_oracle, env, rp, 0, e, 0)
-episodes = np.zeros(E, np.int64)
+side = FreeRunningOracle(c_oracle, scenario, cfg, E, p, 0)
+side.reset()
+env = side.orc
 rng = np.random.RandomState(1)
 N = env.N
 iu = np.triu_indices(N, 1)
@@ -37,9 +35,7 @@ for t in range(T):
     act = rng.randint(0, n_act, size=(E, N)).astype(np.int32)
     env.step(act, threads=8)
     rows.append((keep.sum(1), unsafe, env.qp_sweeps.copy(), keep_env))
-    for e in np.nonzero(env.done)[0]:
-        episodes[e] += 1
-        oracle_reset(c_oracle, env, rp, 0, e, int(episodes[e]))
+    side.reset_ended()
 kept = np.concatenate([r[0] for r in rows]); unsafe = np.concatenate([r[1] for r in rows]); sw = np.concatenate([r[2] for r in rows])
 keep_env = np.concatenate([r[3] for r in rows])
 print("pairs kept per env (of 10): mean %.2f; hist" % kept.mean(), np.bincount(kept, minlength=11))

@@ -7,14 +7,14 @@ import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))   # (this file lives in tests/: only tests may use the oracle)
-import test_gpu_baseline_shapes as T
+import rollout_harness as T
 from oracle import c_oracle
 c_oracle.build_library()
 ipm = "--ipm" in sys.argv
 argv = [a for a in sys.argv if a != "--ipm"]
 steps = int(argv[1]) if len(argv) > 1 else 2000
 total = 0
-for name, scenario, ov, n_act, E, _, kernel, slots in T.CASES:
+for name, scenario, ov, n_act, E, _, kernel, slots in T.SHAPE_CASES:
     if name not in ("pcp-4096x5-headline", "pcp-2048x5", "pcp-32768x5", "pcp-4095x5-ragged", "warehouse-4096x8", "mt-2048x6", "mt-4096x6",
                     "pcp-65536x5-auto"):
         continue

@@ -11,25 +11,22 @@ import torch
 
 from disturb_cases import ACTION_SEED, N_ACT, REGIME_CASES, SEED, Regime, check_regime
 from disturb_twin import displace
-from helpers import oracle_reset, oracle_reset_params
+from oracle_check import FreeRunningOracle
 
 from marbler_amd.params import QP_MAX_SWEEPS, load_config, make_params
 
 
 def oracle_alone(oracle_lib, scenario, ov, solver, sigma, E, T, episode_steps, seed=SEED, action_seed=ACTION_SEED):
     cfg = load_config(scenario, overrides=dict(ov, barrier_solver=solver, max_episode_steps=episode_steps))
-    params = make_params(scenario, cfg)
-    orc = oracle_lib.OracleVecEnv(scenario, cfg, E, dtype=np.float32)
-    rp = oracle_reset_params(oracle_lib, params)
-    for e in range(E):
-        oracle_reset(oracle_lib, orc, rp, seed, e, 0)
-    reset_count = np.ones(E, np.int64)
+    side = FreeRunningOracle(oracle_lib, scenario, cfg, E, make_params(scenario, cfg), seed)
+    side.reset()
+    orc = side.orc
     g = torch.Generator(device="cpu").manual_seed(action_seed)           # test_gpu_disturb.py _actions
     acts = torch.randint(0, N_ACT.get(scenario, 5), (T, E, orc.N), generator=g, dtype=torch.int32).numpy()
     r = Regime()
     for t in range(T):
         before = orc.poses.copy()
-        orc.poses[...] = displace(before, seed, 0, reset_count, orc.steps, sigma[0], sigma[1])
+        orc.poses[...] = displace(before, seed, 0, side.episodes + 1, orc.steps, sigma[0], sigma[1])
         if sigma[0] == 0.0:
             assert np.array_equal(orc.poses[:, :2].view(np.uint32), before[:, :2].view(np.uint32))
         if sigma[1] == 0.0:
@@ -38,9 +35,7 @@ def oracle_alone(oracle_lib, scenario, ov, solver, sigma, E, T, episode_steps, s
         obs, rew, done, info = orc.step(acts[t])
         r.see_step(done, info["violation"], orc.qp_sweeps)
         assert all(np.isfinite(a).all() for a in (obs, rew, info["dist_travelled"], orc.poses)), (t, "the oracle left the finite numbers")
-        for e in np.nonzero(done)[0]:
-            oracle_reset(oracle_lib, orc, rp, seed, e, int(reset_count[e]))
-            reset_count[e] += 1
+        side.reset_ended()
     return r
 
 

@@ -59,8 +59,8 @@ def test_evaluate_cli_on_a_model_zoo_shaped_checkpoint(tmp_path):
     the reference), default PredatorCapturePrey config (4 agents, 16 + 4 inputs)."""
     import json
     from marbler_amd import evaluate
-    from test_gpu_actor import _random_actor
-    sd = _random_actor(1, 20, 64, 5, True, seed=11)
+    from gpu_helpers import random_actor
+    sd = random_actor(1, 20, 64, 5, True, seed=11)
     torch.save(sd, tmp_path / "qmix.th")
     (tmp_path / "qmix.json").write_text(json.dumps({"use_rnn": True, "obs_agent_id": True, "hidden_dim": 64, "agent": "rnn"}))
     argv = ["--scenario", "PredatorCapturePrey", "--model-file", str(tmp_path / "qmix.th"),

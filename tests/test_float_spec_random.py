@@ -18,7 +18,7 @@ What this measures, and what it found (round 3; numbers in DESIGN.md section 2):
 import numpy as np
 import pytest
 
-from helpers import oracle_reset, oracle_reset_params
+from oracle_check import FreeRunningOracle, load_oracle
 
 CASES = [("PredatorCapturePrey", {"predator": 3, "capture": 2, "n_agents": 5}, 5),
          ("PredatorCapturePrey", {}, 5),
@@ -31,19 +31,14 @@ CASES = [("PredatorCapturePrey", {"predator": 3, "capture": 2, "n_agents": 5}, 5
 def measure(oracle_lib, scenario, ov, n_act, E, T, threads=4):
     from marbler_amd.params import load_config, make_params
     cfg = load_config(scenario, None, ov)
-    p = make_params(scenario, cfg)
-    a = oracle_lib.OracleVecEnv(scenario, cfg, E, dtype=np.float64)      # drives the trajectory
+    side = FreeRunningOracle(oracle_lib, scenario, cfg, E, make_params(scenario, cfg), 5, dtype=np.float64)
+    side.reset()
+    a = side.orc                                                         # drives the trajectory
     b = oracle_lib.OracleVecEnv(scenario, cfg, E, dtype=np.float32)      # re-seeded from a's state before every step
-    rp = oracle_reset_params(oracle_lib, p)
-    for e in range(E):
-        oracle_reset(oracle_lib, a, rp, 5, e, 0)
-    episodes = np.zeros(E, np.int64)
     rng = np.random.RandomState(11)
     xy, flips, rows_over, rows, worst_obs = [], 0, 0, 0, 0.0
     for t in range(T):
-        for k in a.STATE_KEYS:
-            src, dst = getattr(a, k), getattr(b, k)
-            dst[...] = src.astype(dst.dtype)
+        load_oracle(b, a.get_state(slice(None)))
         act = rng.randint(0, n_act, size=(E, a.N)).astype(np.int32)
         a.step(act, threads=threads)
         b.step(act, threads=threads)
@@ -60,13 +55,11 @@ def measure(oracle_lib, scenario, ov, n_act, E, T, threads=4):
         rows_over += int(over.sum())
         if (~over).any():
             worst_obs = max(worst_obs, float(d[~over].max()))
-        for e in np.nonzero(a.done)[0]:
-            episodes[e] += 1
-            oracle_reset(oracle_lib, a, rp, 5, e, int(episodes[e]))
+        side.reset_ended()
     xy = np.concatenate(xy)
     return {"env_steps": E * T, "decision_flips": flips, "xy_over_1e-5": int((xy > 1e-5).sum()), "xy_max": float(xy.max()),
             "xy_q999": float(np.quantile(xy, 0.999)), "obs_rows": rows, "obs_rows_over_1e-5": rows_over, "obs_max_rest": worst_obs,
-            "episodes": int(episodes.sum())}
+            "episodes": int(side.episodes.sum())}
 
 
 @pytest.mark.parametrize("scenario,ov,n_act", CASES)

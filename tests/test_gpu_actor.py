@@ -8,24 +8,10 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import fused_actor_random_shape, random_actor
+
 pytestmark = pytest.mark.gpu
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def _random_actor(n_sets, I, H, A, use_rnn, seed):
-    g = torch.Generator().manual_seed(seed)
-    r = lambda *s: (torch.rand(*s, generator=g) * 2 - 1) * 0.3  # noqa: E731
-    sd = {}
-    for i in range(n_sets):
-        pre = f"agents.{i}." if n_sets > 1 else ""
-        sd[pre + "fc1.weight"], sd[pre + "fc1.bias"] = r(H, I), r(H)
-        if use_rnn:
-            sd[pre + "rnn.weight_ih"], sd[pre + "rnn.weight_hh"] = r(3 * H, H), r(3 * H, H)
-            sd[pre + "rnn.bias_ih"], sd[pre + "rnn.bias_hh"] = r(3 * H), r(3 * H)
-        else:
-            sd[pre + "rnn.weight"], sd[pre + "rnn.bias"] = r(H, H), r(H)
-        sd[pre + "fc2.weight"], sd[pre + "fc2.bias"] = r(A, H), r(A)
-    return sd
 
 
 @pytest.mark.parametrize("shared,H,E,N,D,A,use_rnn,append", [
@@ -50,7 +36,7 @@ def test_fused_actor_matches_torch(shared, H, E, N, D, A, use_rnn, append):
     pack = {None: False, "f32": "f32"}.get(append, True)     # True: the default, three bfloat16 planes (rg_actor_pack_gru_bf16x3)
     append = True if append in (None, "f32") else append
     I = D + (N if append else 0)
-    sd = _random_actor(1 if shared else N, I, H, A, use_rnn, seed=H + E)
+    sd = random_actor(1 if shared else N, I, H, A, use_rnn, seed=H + E)
     actor = BatchedActor(sd, N, use_rnn=use_rnn, device=dev, pack_gru=pack)
     assert actor.fused_supported()
     g = torch.Generator(device=dev).manual_seed(1)
@@ -93,53 +79,12 @@ def test_fused_actor_on_the_reference_vectors(name):
             assert np.abs(hidden[e].cpu().numpy() - g["h"][t]).max() < 1e-5
 
 
-def _draw_actor_case(rng):
-    H = int(rng.choice([64, 128]))
-    shared = bool(rng.rand() < 0.6)
-    N = int(rng.randint(1, 9))
-    append = bool(rng.rand() < 0.6)
-    D = int(rng.randint(1, 64 - (N if append else 0) + 1))          # input width D (+ N) <= 64
-    A = int(rng.choice([1, 2, 5, 7, 20, 31, 32]))
-    E = int(rng.choice([1, 2, 31, 32, 33, 100, 257]))
-    use_rnn = bool(rng.rand() < 0.8)
-    pack = [True, "f32", False][int(rng.randint(0, 3))]
-    if rng.rand() < 0.4:     # (drawn after everything else: the cases of earlier rounds keep their shapes)
-        pack = "f16x2" if pack is True else "bf16x3" if pack == "f32" else pack
-    return shared, H, E, N, D, A, use_rnn, append, pack
-
-
 @pytest.mark.parametrize("seed", range(96))
 def test_fused_actor_random_shapes(seed):
     """Shapes nobody listed: every input width up to 64 (ragged fc1 rows, agent id on or off), 1 ... 32 actions (fc2's padded tile,
     the all-thread arg-max), ragged and tiny batches, shared / per-agent weights, GRU in all three weight forms / the MLP layer --
     against the torch evaluation: 1e-5 on q and hidden, greedy actions equal where the top two values are 1e-4 apart."""
-    from marbler_amd.evaluate import BatchedActor
-    rng = np.random.RandomState(7000 + seed)
-    shared, H, E, N, D, A, use_rnn, append, pack = _draw_actor_case(rng)
-    dev = "cuda:0"
-    I = D + (N if append else 0)
-    actor = BatchedActor(_random_actor(1 if shared else N, I, H, A, use_rnn, seed), N, use_rnn=use_rnn, device=dev, pack_gru=pack)
-    g = torch.Generator(device=dev).manual_seed(seed)
-    hidden = torch.rand(E, N, H, generator=g, device=dev) * 2 - 1
-    h_ref = hidden.clone()
-    eye = torch.eye(N, device=dev).unsqueeze(0).expand(E, N, N)
-    for step in range(2):
-        obs = torch.rand(E, N, D, generator=g, device=dev) * 3 - 1.5
-        restart = (torch.rand(E, generator=g, device=dev) < 0.3).to(torch.uint8)
-        fresh = restart.bool()[:, None, None]
-        obs_seen = torch.where(fresh, torch.zeros_like(obs), obs)
-        q_ref, h_ref = actor.forward(torch.cat([obs_seen, eye], dim=2) if append else obs_seen, torch.where(fresh, torch.zeros_like(h_ref), h_ref))
-        q, act = actor.forward_fused(obs, hidden, append_agent_id=append, restart=restart)
-        torch.cuda.synchronize()
-        case = (shared, H, E, N, D, A, use_rnn, append, pack, step)
-        assert float((q - q_ref).abs().max()) < 1e-5, case
-        assert float((hidden - h_ref).abs().max()) < 1e-5, case
-        if A > 1:
-            top2 = q_ref.topk(2, dim=2).values
-            clear = (top2[..., 0] - top2[..., 1]) > 1e-4
-            assert torch.equal(act[clear].long(), q_ref.argmax(dim=2)[clear]), case
-        else:
-            assert int(act.abs().sum()) == 0, case
+    fused_actor_random_shape(seed)
 
 
 @pytest.mark.parametrize("A", [1, 5, 20, 32])
@@ -151,7 +96,7 @@ def test_greedy_action_is_a_valid_index_on_non_finite_rows(A):
     from marbler_amd.evaluate import BatchedActor
     dev = "cuda:0"
     N, H, D = 6, 64, 7
-    sd = _random_actor(N, D, H, A, True, 5)
+    sd = random_actor(N, D, H, A, True, 5)
     b2 = [k for k in sd if k.endswith("fc2.bias")]
     assert len(b2) == N, sorted(sd)
     nan, ninf = float("nan"), float("-inf")
@@ -194,7 +139,7 @@ def test_epsilon_greedy_selection_inside_the_launch(shared, H, A, eps):
     from marbler_amd.evaluate import BatchedActor, explore_select
     dev = "cuda:0"
     E, N, D = 3000, 4, 9
-    actor = BatchedActor(_random_actor(1 if shared else N, D + N, H, A, True, 8), N, use_rnn=True, device=dev)
+    actor = BatchedActor(random_actor(1 if shared else N, D + N, H, A, True, 8), N, use_rnn=True, device=dev)
     g = torch.Generator(device=dev).manual_seed(11)
     hidden = torch.rand(E, N, H, generator=g, device=dev) * 2 - 1
     obs = torch.rand(E, N, D, generator=g, device=dev)
@@ -235,7 +180,7 @@ def test_two_binary16_planes_match_torch_and_the_three_plane_form(shared, H, E, 
     own) to 3e-6 -- a float32 GEMM's own roundings are of that size."""
     from marbler_amd.evaluate import BatchedActor
     dev = "cuda:0"
-    sd = _random_actor(1 if shared else N, D + N, H, A, True, seed=H + E)
+    sd = random_actor(1 if shared else N, D + N, H, A, True, seed=H + E)
     fast, fine = (BatchedActor(sd, N, use_rnn=True, device=dev, pack_gru=p) for p in ("f16x2", "bf16x3"))
     g = torch.Generator(device=dev).manual_seed(2)
     hidden = torch.rand(E, N, H, generator=g, device=dev) * 2 - 1
@@ -262,7 +207,7 @@ def test_two_binary16_planes_on_values_outside_binary16s_normal_range():
     from marbler_amd.evaluate import BatchedActor
     dev = "cuda:0"
     E, N, D, H, A = 64, 4, 12, 128, 5
-    sd = _random_actor(1, D + N, H, A, True, seed=21)
+    sd = random_actor(1, D + N, H, A, True, seed=21)
     g0 = torch.Generator().manual_seed(4)
     for k in ("rnn.weight_hh", "rnn.weight_ih"):
         w = sd[k]
@@ -302,7 +247,7 @@ def test_two_binary16_planes_saturate_beyond_binary16s_range_and_keep_nans():
     E, N, D, H, A = 40, 4, 12, 128, 5
     outs = []
     for bias in (1e5, 65504.0):
-        sd = _random_actor(1, D + N, H, A, True, seed=31)
+        sd = random_actor(1, D + N, H, A, True, seed=31)
         sd["fc1.weight"][3] = 0.0
         sd["fc1.bias"][3] = bias
         sd["rnn.weight_ih"][:, 3] *= 1e-3          # (keeps the gates' pre-activations in a range where the outputs still move)

@@ -8,17 +8,16 @@
    the CPU that the inputs get there).
 3. Several envs per wavefront: 4, 8 and 16 env slots, both solver modes, through an auto-reset inside the shared wave.
 4. The high words of the draw's counter and key: an env offset and a seed beyond 2^32.
-Every comparison is word for word."""
-import numpy as np
+Every comparison is word for word (tests/oracle_check.py)."""
 import pytest
 import torch
 
 from disturb_cases import BOUNDS, FORM_CASES, N_ACT, PCP5, REGIME_CASES, check_regime
-from helpers import STATE_KEYS
-from test_gpu_baseline_shapes import expected_slots
-from test_gpu_disturb import OUT_KEYS, _actions, _env, _gpu_state, _noise, _oracle_step, _same, _words, disturbed_vs_oracle
-from test_gpu_shared_waves import PCP12
-from test_gpu_wrapper import fused_time_limit_vs_composed
+from disturb_harness import OUT_KEYS, disturbed_vs_oracle, make_env as _env, noise as _noise, oracle_step as _oracle_step, plain_oracle
+from gpu_helpers import (expected_slots, fused_time_limit_vs_composed, random_actions as _actions, rollout_equals_single_steps,
+                         same_bits as _same)
+from oracle_check import assert_outputs, assert_state, gpu_outputs, gpu_state as _gpu_state
+from physical_cases import PCP12
 
 from marbler_amd.params import QP_MAX_SWEEPS
 
@@ -94,8 +93,7 @@ def test_a_zero_scale_leaves_signed_zeros_alone(sigma, oracle_lib):
     stored words (tests/test_disturb_regimes.py) -- x + 0 * c would have made a -0.0 a +0.0."""
     E = 67
     env = _env("PredatorCapturePrey", E, PCP5, sigma=sigma, seed=4, auto_reset=False, collect_qp_stats=True)
-    cfg = {k: v for k, v in env.cfg.items() if k not in _noise(sigma)}
-    orc = oracle_lib.OracleVecEnv("PredatorCapturePrey", cfg, E, dtype=np.float32)
+    orc = plain_oracle(oracle_lib, env)
     env.reset()
     env.poses[0::3, 2, :] = -0.0                 # headings; one agent's x, another's y (no two robots on one spot)
     env.poses[1::3, 2, :] = 0.0
@@ -105,14 +103,9 @@ def test_a_zero_scale_leaves_signed_zeros_alone(sigma, oracle_lib):
     acts = _actions(env, 1, seed=6)
     pre, rc = _gpu_state(env), env.reset_count.cpu().numpy()
     env.step(acts[0])
-    o_obs, o_rew, o_done, o_info = _oracle_step(orc, env, pre, rc, acts[0].cpu().numpy(), sigma=sigma)
-    for k, want in (("obs", o_obs), ("reward", o_rew), ("done_u8", o_done), ("dist_travelled", o_info["dist_travelled"]),
-                    ("violation", o_info["violation"]), ("remaining", o_info["remaining"]), ("qp_sweeps", orc.qp_sweeps)):
-        got = getattr(env, k).cpu().numpy()
-        assert np.array_equal(_words(got), _words(np.asarray(want).astype(got.dtype))), k
-    post = _gpu_state(env)
-    for k in STATE_KEYS:
-        assert np.array_equal(_words(post[k]), _words(getattr(orc, k).astype(post[k].dtype).reshape(post[k].shape))), k
+    _oracle_step(orc, env, pre, rc, acts[0].cpu().numpy(), sigma=sigma)
+    assert_outputs(gpu_outputs(env), orc, "signed zeros")
+    assert_state(_gpu_state(env), orc, label="signed zeros")      # auto_reset off: every env, ended or not
     env.close()
 
 
@@ -145,14 +138,7 @@ def test_a_rollout_of_envs_sharing_a_wave_equals_the_steps(solver):
     s, r = _env("PredatorCapturePrey", E, ov, seed=21), _env("PredatorCapturePrey", E, ov, seed=21)
     s.reset()
     r.reset()
-    acts = _actions(s, K, seed=6)
-    out = r.rollout(acts)
-    for t in range(K):
-        s.step(acts[t])
-        for k in OUT_KEYS:
-            assert _same(getattr(s, k), out[ROLLOUT_KEY.get(k, k)][t]), (t, k)
-    for k in s.STATE_KEYS:
-        assert _same(getattr(s, k), getattr(r, k)), k
+    out = rollout_equals_single_steps(s, r, _actions(s, K, seed=6))
     assert int(out["done"].sum()) >= E
     s.close()
     r.close()

@@ -8,7 +8,7 @@ reference's own Python: tests/test_ipm_spec.py, tests/test_oracle_golden.py -- C
 import numpy as np
 import pytest
 
-from test_gpu_rollout import _rollout_bit_exact, _rollout_equals_steps
+from rollout_harness import rollout_bit_exact, rollout_equals_steps
 
 pytestmark = pytest.mark.gpu
 IPM = {"barrier_solver": "cvxopt"}
@@ -44,7 +44,7 @@ def test_interior_point_mode_rollout_is_bit_exact(scenario, ov, n_act, steps, E,
     n, which = probe.N, probe.step_kernel
     probe.close()
     assert which == (kernel if (kernel == "group" or 2 <= n <= 5) else "group"), (n, which)
-    _rollout_bit_exact(scenario, dict(ov, **IPM), n_act, steps, oracle_lib, E, require_done=False)
+    rollout_bit_exact(scenario, dict(ov, **IPM), n_act, steps, oracle_lib, E, require_done=False)
 
 
 @pytest.mark.parametrize("scenario,ov,n_act,E", [("PredatorCapturePrey", {"predator": 3, "capture": 2, "n_agents": 5}, 5, 130),
@@ -53,7 +53,7 @@ def test_interior_point_mode_rollout_is_bit_exact(scenario, ov, n_act, steps, E,
 @pytest.mark.parametrize("kernel", ["group", "tpe"])
 def test_interior_point_mode_multi_step_launch_equals_single_steps(scenario, ov, n_act, E, kernel, monkeypatch):
     monkeypatch.setenv("RG_STEP_KERNEL", kernel)
-    _rollout_equals_steps(scenario, dict(ov, **IPM), n_act, E, K=10, reps=3, require_done=False)
+    rollout_equals_steps(scenario, dict(ov, **IPM), n_act, E, K=10, reps=3, require_done=False)
 
 
 def test_interior_point_mode_picks_the_kernel_by_batch_size():

@@ -10,7 +10,7 @@ import ctypes as C
 
 import pytest
 
-from test_gpu_shape_kernels import OUTS, SHAPE_IDS, _actions, _differing, _make
+from shape_kernel_harness import OUTS, SHAPE_IDS, actions as _actions, differing as _differing, make as _make
 from test_shape_kernels import REFERENCE
 
 pytestmark = pytest.mark.gpu

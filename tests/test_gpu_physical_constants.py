@@ -6,9 +6,9 @@ tests/physical_cases.py, and tests/test_physical_regimes.py shows on the CPU tha
 for:
 
  (a) directed regimes x every dispatch of the step (lane groups of 4, 8, 16; the 16-lane rows by value, resident and shaped;
-     the thread-per-env kernel; both QP modes where built), free-running with auto-reset: every output, `qp_sweeps`, the poses
-     and the statistics word for word (test_gpu_rollout._rollout_bit_exact);
- (b) a seeded fuzz over all 13 constants on top of test_gpu_config_fuzz.draw_config;
+     the thread-per-env kernel; both QP modes where built), free-running with auto-reset: what tests/oracle_check.py
+     compares for a free-running harness (rollout_harness.rollout_bit_exact);
+ (b) a seeded fuzz over all 13 constants on top of fuzz_cases.draw_config;
  (c) the lidar, team-pool and pose-disturbance families at one off-default point each;
  (d) stray poses: colliding pairs loaded far outside the arena, where the collision pre-test's binary16 figure is no bound, and
      a colliding pair inside the large arena that a rounding bound sized for the default arena would miss.
@@ -18,10 +18,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import disturb_harness
+import lidar_harness
 import physical_cases as pc
-from helpers import GPU_NAME, STATE_KEYS, gpu_from_state
-from test_gpu_config_fuzz import draw_config, draw_interior_point
-from test_gpu_rollout import _rollout_bit_exact, _rollout_equals_steps
+import team_harness
+from helpers import gpu_from_state
+from oracle_check import FreeRunningOracle, assert_outputs, assert_state, gpu_outputs, gpu_state
+from physical_cases import CASES, IPM_CASES
+from rollout_harness import fuzz_case_bit_exact, rollout_bit_exact, rollout_equals_steps
 
 pytestmark = pytest.mark.gpu
 
@@ -56,45 +60,27 @@ def test_regime_is_bit_exact_on_every_dispatch(regime, dispatch, oracle_lib, mon
         else:
             assert got == {"by-value": _lib.FORM_BY_VALUE, "resident": _lib.FORM_RESIDENT}[form], (t, got)
 
-    _rollout_bit_exact(scenario, ov, pc.N_ACT.get(scenario, 5), pc.STEPS, oracle_lib, E, constants=consts, after_step=launched_as_named)
+    rollout_bit_exact(scenario, ov, pc.N_ACT.get(scenario, 5), pc.STEPS, oracle_lib, E, constants=consts, after_step=launched_as_named)
 
 
 # ---------------------------------------------------------------- (b) the seeded fuzz
-CASES = [pc.draw_physical(np.random.RandomState(9000 + i), draw_config) for i in range(96)]
-IPM_CASES = [pc.draw_physical(np.random.RandomState(9500 + i), draw_interior_point) for i in range(24)]
-
-
-def _constants_of(ov):
-    return {k: ov[k] for k in pc.RPS_DEFAULTS}
-
-
 @pytest.mark.parametrize("i", range(len(CASES)))
 def test_random_constants_are_bit_exact(i, oracle_lib, monkeypatch):
-    scenario, ov, n_act, E, kernel = CASES[i]
-    _dispatch_env(monkeypatch, kernel)
-    steps = 40 if scenario != "MaterialTransport" else 25
-    try:
-        _rollout_bit_exact(scenario, ov, n_act, steps, oracle_lib, E, require_done=False, constants=_constants_of(ov))
-    except AssertionError as exc:
-        raise AssertionError(f"case {i}: {scenario} {ov} E={E} kernel={kernel}: {exc}") from exc
+    _dispatch_env(monkeypatch, CASES[i][4])
+    fuzz_case_bit_exact(i, CASES[i], (25, 40), oracle_lib, constants={k: CASES[i][1][k] for k in pc.RPS_DEFAULTS})
 
 
 @pytest.mark.parametrize("i", range(len(IPM_CASES)))
 def test_random_constants_are_bit_exact_in_the_interior_point_mode(i, oracle_lib, monkeypatch):
-    scenario, ov, n_act, E, kernel = IPM_CASES[i]
-    _dispatch_env(monkeypatch, kernel)
-    steps = 30 if scenario != "MaterialTransport" else 16
-    try:
-        _rollout_bit_exact(scenario, ov, n_act, steps, oracle_lib, E, require_done=False, constants=_constants_of(ov))
-    except AssertionError as exc:
-        raise AssertionError(f"case {i}: {scenario} {ov} E={E} kernel={kernel}: {exc}") from exc
+    _dispatch_env(monkeypatch, IPM_CASES[i][4])
+    fuzz_case_bit_exact(i, IPM_CASES[i], (16, 30), oracle_lib, constants={k: IPM_CASES[i][1][k] for k in pc.RPS_DEFAULTS})
 
 
 @pytest.mark.parametrize("i", range(0, len(CASES), 4))
 def test_random_constants_multi_step_launch_equals_single_steps(i, monkeypatch):
     scenario, ov, n_act, E, kernel = CASES[i]
     _dispatch_env(monkeypatch, kernel)
-    _rollout_equals_steps(scenario, ov, n_act, E, K=12, reps=2, require_done=False)
+    rollout_equals_steps(scenario, ov, n_act, E, K=12, reps=2, require_done=False)
 
 
 # ---------------------------------------------------------------- (c) the opt-in families
@@ -109,40 +95,32 @@ def _group(monkeypatch):
 
 def test_lidar_with_a_wide_robot_in_the_off_centre_arena(_group):
     """tests/lidar_twin.py reads the arena from the parameter block; the robots' radius follows robot_diameter."""
-    import test_gpu_lidar as lidar
-    lidar.ranges_vs_twin("PredatorCapturePrey", 16, E=65, T=4, ov=dict(OFF_CENTRE, robot_diameter=0.15))
+    lidar_harness.ranges_vs_twin("PredatorCapturePrey", 16, E=65, T=4, ov=dict(OFF_CENTRE, robot_diameter=0.15))
 
 
 @pytest.mark.parametrize("solver", ["exact", "cvxopt"])
 def test_team_pool_through_the_wide_angle_heading_step(solver, oracle_lib, _group):
-    import test_gpu_teams as teams
-    teams.mixed_teams_vs_oracle("PredatorCapturePrey", dict(pc.PCP5, **WIDE), solver, oracle_lib, 65, 30, 10)
+    team_harness.mixed_teams_vs_oracle("PredatorCapturePrey", dict(pc.PCP5, **WIDE), solver, oracle_lib, 65, 30, 10)
 
 
 @pytest.mark.parametrize("solver", ["exact", "cvxopt"])
 def test_pose_disturbance_at_its_bounds_with_a_long_time_step(solver, oracle_lib, _group):
-    import test_gpu_disturb as disturb
-    disturb.disturbed_vs_oracle("PredatorCapturePrey", dict(pc.PCP5, **WIDE), solver, 67, 12, oracle_lib, sigma=(0.1, 0.5))
+    disturb_harness.disturbed_vs_oracle("PredatorCapturePrey", dict(pc.PCP5, **WIDE), solver, 67, 12, oracle_lib, sigma=(0.1, 0.5))
 
 
 # ---------------------------------------------------------------- (d) stray poses
 def _oracle_with_reset_states(oracle_lib, scenario, cfg, E):
-    from helpers import oracle_reset, oracle_reset_params
     from marbler_amd.params import make_params
-    orc = oracle_lib.OracleVecEnv(scenario, cfg, E, dtype=np.float32)
-    rp = oracle_reset_params(oracle_lib, make_params(scenario, cfg))
-    for e in range(E):
-        oracle_reset(oracle_lib, orc, rp, pc.SEED, e, 0)
-    return orc
+    return FreeRunningOracle.at_reset(oracle_lib, scenario, cfg, E, make_params(scenario, cfg), pc.SEED)
 
 
 def _one_step_from_loaded_state(scenario, cfg, orc, expected):
     """The oracle steps first and must report `expected` (None: whatever it reports) in every env: a placement error cannot pass
-    as agreement.  Then the same state and the no-op action on the GPU: every output and the stored state, word for word."""
+    as agreement.  Then the same state and the no-op action on the GPU: every output and the stored state (tests/oracle_check.py)."""
     import torch
     state = orc.get_state(slice(None))
     acts = np.full((orc.E, orc.N), pc.NO_OP, np.int32)
-    o_obs, o_rew, o_done, o_info = orc.step(acts)
+    o_info = orc.step(acts)[3]
     codes = set(o_info["violation"].tolist())
     if expected is not None:
         assert codes == {expected}, codes
@@ -153,13 +131,8 @@ def _one_step_from_loaded_state(scenario, cfg, orc, expected):
     got_viol = env.violation.cpu().numpy()
     assert np.array_equal(got_viol, o_info["violation"]), \
         f"violation: {np.bincount(got_viol, minlength=4).tolist()} (codes 0..3) on the GPU, the oracle reports {sorted(codes)} in all {orc.E} envs"
-    for k, want in (("done_u8", o_done), ("remaining", o_info["remaining"]), ("qp_sweeps", orc.qp_sweeps), ("obs", o_obs),
-                    ("reward", o_rew), ("dist_travelled", o_info["dist_travelled"])):
-        got = getattr(env, k).cpu().numpy()
-        assert np.array_equal(got.view(np.uint8), np.asarray(want).astype(got.dtype).view(np.uint8)), k
-    for k in STATE_KEYS:
-        got = getattr(env, GPU_NAME.get(k, k)).cpu().numpy()
-        assert np.array_equal(got.view(np.uint8), getattr(orc, k).astype(got.dtype).reshape(got.shape).view(np.uint8)), k
+    assert_outputs(gpu_outputs(env), orc, scenario)
+    assert_state(gpu_state(env), orc, label=scenario)
     env.close()
     return codes.pop()
 

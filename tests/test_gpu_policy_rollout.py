@@ -4,7 +4,7 @@ env state."""
 import pytest
 import torch
 
-from test_gpu_actor import _random_actor
+from gpu_helpers import random_actor, runners_agree as _assert_same
 
 pytestmark = pytest.mark.gpu
 
@@ -25,21 +25,9 @@ def _runner(key, ov, E, H, shared, epsilon, limit=12, pack_gru=True):
     from marbler_amd.gymma import BatchedRunner, GymmaVecEnv
     v = GymmaVecEnv(key, E, time_limit=limit, seed=5, overrides=ov)
     N = v.n_agents
-    actor = BatchedActor(_random_actor(1 if shared else N, v.obs_size + N, H, v.n_actions, True, seed=4), N, device=v.env.device,
+    actor = BatchedActor(random_actor(1 if shared else N, v.obs_size + N, H, v.n_actions, True, seed=4), N, device=v.env.device,
                          pack_gru=pack_gru)
     return v, BatchedRunner(v, actor, epsilon=epsilon, seed=9)
-
-
-def _assert_same(r1, r2):
-    (v1, a), (v2, b) = r1, r2
-    torch.cuda.synchronize()
-    assert torch.equal(a.hidden, b.hidden) and torch.equal(a._restart, b._restart)
-    assert torch.equal(v1.get_obs(), v2.get_obs()) and torch.equal(v1._ended, v2._ended)
-    assert torch.equal(v1.env.done_count, v2.env.done_count)
-    assert v1.get_stats() == v2.get_stats()
-    s1, s2 = v1.env.state_dict(), v2.env.state_dict()
-    for k in s1:
-        assert torch.equal(s1[k], s2[k]), k
 
 
 @pytest.mark.parametrize("epsilon", [0.0, 0.1])
@@ -83,7 +71,7 @@ def test_run_eval_one_launch_equals_fused(scenario, ov, H):
     outs, envs = [], []
     for one in (False, True):
         env = VecRobotariumEnv(scenario, 130, seed=3, overrides=ov)
-        actor = BatchedActor(_random_actor(1, env.D + env.N, H, 20 if scenario == "MaterialTransport" else 5, True, seed=2), env.N,
+        actor = BatchedActor(random_actor(1, env.D + env.N, H, 20 if scenario == "MaterialTransport" else 5, True, seed=2), env.N,
                              device=env.device)
         outs.append(run_eval(env, actor, 150, fused=True, one_launch=one))
         envs.append(env)
@@ -105,7 +93,7 @@ def test_refusals():
     with pytest.raises(ValueError, match="binary16"):
         r.run(2, one_launch=True)
     v = GymmaVecEnv(key, 8, time_limit=10, seed=1)
-    actor = BatchedActor(_random_actor(1, v.obs_size + v.n_agents, 64, v.n_actions, True, seed=4), v.n_agents, device=v.env.device)
+    actor = BatchedActor(random_actor(1, v.obs_size + v.n_agents, 64, v.n_actions, True, seed=4), v.n_agents, device=v.env.device)
     with pytest.raises(ValueError, match="inputs per agent"):
         BatchedRunner(v, actor, obs_agent_id=False).run(2, one_launch=True)
 

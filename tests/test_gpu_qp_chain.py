@@ -8,10 +8,9 @@ oracle alone, with the helper's seeds (env seed 99, action seed 5)."""
 import numpy as np
 import pytest
 
-from test_gpu_rollout import _rollout_bit_exact
+from physical_cases import MT6, PCP5
+from rollout_harness import rollout_bit_exact
 
-PCP5 = {"predator": 3, "capture": 2, "n_agents": 5}
-MT6 = {"n_agents": 6, "n_fast_agents": 3, "n_slow_agents": 3, "start_dist": 0.25}
 
 
 class _SweepHistogram(object):
@@ -28,8 +27,8 @@ class _SweepHistogram(object):
         orc = self._lib.OracleVecEnv(*args, **kwargs)
         step = orc.step
 
-        def recording_step(actions):
-            out = step(actions)
+        def recording_step(actions, **kw):
+            out = step(actions, **kw)
             self.hist += np.bincount(orc.qp_sweeps, minlength=128)[:128]
             return out
         orc.step = recording_step
@@ -40,7 +39,7 @@ def _run(scenario, ov, n_act, steps, E, oracle_lib, monkeypatch):
     monkeypatch.setenv("RG_STEP_KERNEL", "group")
     monkeypatch.delenv("RG_STEP_SPAN", raising=False)
     rec = _SweepHistogram(oracle_lib)
-    _rollout_bit_exact(scenario, ov, n_act, steps, rec, E, require_done=False)
+    rollout_bit_exact(scenario, ov, n_act, steps, rec, E, require_done=False)
     assert rec.hist.sum() == steps * E
     print(scenario, ov, E, steps, "qp_sweeps histogram:", {int(k): int(v) for k, v in enumerate(rec.hist) if v})
     return rec.hist

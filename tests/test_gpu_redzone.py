@@ -10,71 +10,11 @@ those of an ordinary env (separate allocations, always the lane-group kernel) bi
 
 Reference surface whose outputs these arrays are: wrapper.py:41-44.
 """
-import numpy as np
 import pytest
 
+from gpu_helpers import SENTINEL, guarded_class
+
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 0xA5
-ZONE = 1024
-
-
-def _guarded_class():
-    import torch
-    from marbler_amd import VecRobotariumEnv
-
-    class GuardedEnv(VecRobotariumEnv):
-        """All arrays from one slab, red zones between them."""
-
-        def __init__(self, *a, slab_bytes=1 << 26, **kw):
-            dev = torch.device(kw.get("device", "cuda:0"))
-            self._slab = torch.full((slab_bytes,), SENTINEL, dtype=torch.uint8, device=dev)
-            self._cursor = 0
-            self._regions = []
-            super().__init__(*a, **kw)
-
-        def _alloc(self, shape, dtype, fill=0):
-            nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-            lo = (self._cursor + ZONE + 255) // 256 * 256
-            hi = lo + nbytes
-            if hi + ZONE > self._slab.numel():
-                raise MemoryError("guard slab too small")
-            self._cursor = hi
-            self._regions.append((lo, hi))
-            t = self._slab[lo:hi].view(dtype).view(tuple(shape))
-            t.fill_(fill)
-            return t
-
-        def _alloc_outputs(self):   # one array each (the product packs them into one arena, 16-byte aligned, no gaps)
-            E, N, D = self.E, self.N, self.D
-            f32, i32, u8 = torch.float32, torch.int32, torch.uint8
-            self.obs = self._alloc((E, N, D), f32)
-            self.reward = self._alloc((E, N), f32)
-            self.dist_travelled = self._alloc((E, N), f32)
-            self.remaining = self._alloc((E,), i32, fill=-1)
-            self.done_u8 = self._alloc((E,), u8)
-            self.done = self.done_u8.view(torch.bool)
-            self.violation = self._alloc((E,), u8)
-            self._out_arena, self._out_offsets = None, {}
-
-        def red_zones_intact(self):
-            keep = torch.ones(self._slab.numel(), dtype=torch.bool, device=self._slab.device)
-            for lo, hi in self._regions:
-                keep[lo:hi] = False
-            bad = torch.nonzero(keep & (self._slab != SENTINEL)).flatten()
-            return bad.cpu().numpy()
-
-        def owner_of(self, off):
-            """Nearest array below a damaged byte (diagnostics)."""
-            names = {}
-            for k, v in self.__dict__.items():
-                if isinstance(v, torch.Tensor) and v.device == self._slab.device and v.untyped_storage().data_ptr() == self._slab.untyped_storage().data_ptr():
-                    names[v.data_ptr() - self._slab.data_ptr()] = k
-            below = [o for o in names if o <= off]
-            return names[max(below)] if below else "<slab start>"
-
-    return GuardedEnv
-
 
 def _configs():
     """(id, scenario, overrides, action count)"""
@@ -116,7 +56,7 @@ def test_no_store_outside_the_bound_arrays(name, scenario, ov, n_act, kernel, mo
     import torch
     from marbler_amd import VecRobotariumEnv
     monkeypatch.setenv("RG_STEP_KERNEL", kernel)
-    Guarded = _guarded_class()
+    Guarded = guarded_class()
     STEPS, K = 50, 16
     for E in SIZES:
         with monkeypatch.context() as m:   # the unguarded twin always runs the lane-group kernel: the two mappings must agree
@@ -163,7 +103,7 @@ def test_gymma_block_stays_inside_its_arrays(kernel, monkeypatch):
     """The fused TimeLimit / reduction outputs (rg_step_io's gymma block)."""
     import torch
     monkeypatch.setenv("RG_STEP_KERNEL", kernel)
-    Guarded = _guarded_class()
+    Guarded = guarded_class()
     for scenario, ov, n_act in (("PredatorCapturePrey", {"predator": 3, "capture": 2, "n_agents": 5}, 5),
                                 ("Warehouse", {"n_agents": 8}, 5), ("MaterialTransport", {}, 20), ("ArcticTransport", {}, 5)):
         for E in (1, 65, 4097):
@@ -183,7 +123,7 @@ def test_gymma_block_stays_inside_its_arrays(kernel, monkeypatch):
 def test_the_detector_detects():
     """A deliberate one-byte store just past an array must be reported (the test of the test)."""
     import torch
-    Guarded = _guarded_class()
+    Guarded = guarded_class()
     env = Guarded("Warehouse", 65, overrides={}, seed=0)
     assert env.red_zones_intact().size == 0
     off = env.reward.data_ptr() - env._slab.data_ptr() + env.reward.numel() * 4

@@ -14,8 +14,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_gpu_baseline_shapes import expected_slots
-from test_gpu_redzone import _guarded_class
+from gpu_helpers import expected_slots, guarded_class, lane_group_kernel  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,11 +30,6 @@ SCRATCH = ("next_init", "next_episode")
 OUTS = ("obs", "reward", "done_u8", "dist_travelled", "violation", "remaining", "qp_sweeps")
 
 
-@pytest.fixture(autouse=True)
-def _lane_group_kernel(monkeypatch):
-    monkeypatch.setenv("RG_STEP_KERNEL", "group")
-
-
 def _make(config, E, resident, monkeypatch, guarded=False, auto_reset=True):
     from marbler_amd import VecRobotariumEnv
     scenario, ov, _ = config
@@ -45,7 +39,7 @@ def _make(config, E, resident, monkeypatch, guarded=False, auto_reset=True):
         else:
             m.setenv("RG_STEP_RESIDENT", "0")
         kw = dict(overrides=ov, seed=7, auto_reset=auto_reset, collect_qp_stats=True)
-        env = _guarded_class()(scenario, E, slab_bytes=E * 8192 + (8 << 20), **kw) if guarded else VecRobotariumEnv(scenario, E, **kw)
+        env = guarded_class()(scenario, E, slab_bytes=E * 8192 + (8 << 20), **kw) if guarded else VecRobotariumEnv(scenario, E, **kw)
     env.reset()
     assert env.step_kernel == "group" and 5 <= env.N <= 8 and expected_slots(env.N, E) <= 4, "the case no longer dispatches a row kernel"
     return env

@@ -1,31 +1,13 @@
 """Free-running rollouts on the GPU (auto-reset on) against the float32 oracle stepping the same
-envs on the CPU with the oracle's reset twin: every output of every step, bit for bit, over whole
+envs on the CPU with the oracle's reset twin (what is compared: tests/oracle_check.py), over whole
 episodes including violations, captures, loading/unloading and resets.  Plus size-independent
 properties at the bench size (4096 envs)."""
 import numpy as np
 import pytest
 
-from helpers import oracle_reset as _oracle_reset, oracle_reset_params
+from rollout_harness import ROLLOUT_CASES as CASES, rollout_bit_exact, rollout_equals_steps
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("step_kernel")]
-
-CASES = [("PredatorCapturePrey", {"predator": 3, "capture": 2, "n_agents": 5}, 5, 260),
-         ("PredatorCapturePrey", {"num_neighbors": 2, "capability_aware": True}, 5, 120),
-         ("Warehouse", {"n_agents": 8}, 5, 230),
-         ("Warehouse", {}, 5, 120),
-         ("MaterialTransport", {"n_agents": 6, "n_fast_agents": 3, "n_slow_agents": 3, "start_dist": 0.25}, 20, 160),
-         ("MaterialTransport", {}, 20, 100),
-         ("PredatorCapturePrey", {"predator": 6, "capture": 6, "n_agents": 12, "num_prey": 10, "start_dist": 0.25,
-                                  "num_neighbors": 4}, 5, 60),
-         ("PredatorCapturePrey", {"predator": 3, "capture": 2, "collision_variant": "center"}, 5, 150),
-         ("Warehouse", {"n_agents": 8, "barrier_certificate": "default"}, 5, 150),
-         ("PredatorCapturePrey", {"predator": 3, "capture": 2, "penalize_violations": False}, 5, 120),
-         ("MaterialTransport", {"capability_aware": True, "qp_max_sweeps": 6}, 20, 80),
-         ("PredatorCapturePrey", {"predator": 3, "capture": 2, "n_agents": 5, "num_prey": 12}, 5, 150),   # > 8 prey: LDS / loop paths
-         ("PredatorCapturePrey", {"predator": 2, "capture": 2, "n_agents": 4, "num_prey": 33, "step_dist": 0.16}, 5, 100),  # > 32 prey: both flag words
-         ("Simple", {}, 5, 130),
-         ("Simple", {"n_agents": 6}, 5, 80),
-         ("ArcticTransport", {}, 5, 200)]
 
 
 # ragged and extreme shapes: batch sizes that do not fill a wavefront (1, 7, 65, 130 envs), the
@@ -52,76 +34,12 @@ EDGE_CASES = [("PredatorCapturePrey", {"predator": 3, "capture": 2, "n_agents": 
 
 @pytest.mark.parametrize("scenario,ov,n_act,steps,E", EDGE_CASES)
 def test_rollout_bit_exact_ragged_and_extreme_shapes(scenario, ov, n_act, steps, E, oracle_lib):
-    _rollout_bit_exact(scenario, ov, n_act, steps, oracle_lib, E)
+    rollout_bit_exact(scenario, ov, n_act, steps, oracle_lib, E)
 
 
 @pytest.mark.parametrize("scenario,ov,n_act,steps", CASES)
 def test_rollout_bit_exact(scenario, ov, n_act, steps, oracle_lib):
-    _rollout_bit_exact(scenario, ov, n_act, steps, oracle_lib, 192)
-
-
-def _rollout_bit_exact(scenario, ov, n_act, steps, oracle_lib, E, require_done=True, constants=None, after_step=None):
-    """constants: the rps constants among `ov` (tests/physical_cases.py): both sides' parameter blocks are held to them, and to the
-    defaults elsewhere, before the first step.  after_step(env, t): what a caller asserts about the launch (rg_step_form)."""
-    import torch
-    from marbler_amd import VecRobotariumEnv
-    seed = 99
-    env = VecRobotariumEnv(scenario, E, overrides=ov, seed=seed, auto_reset=True, collect_qp_stats=True)
-    cfg = dict(env.cfg)
-    orc = oracle_lib.OracleVecEnv(scenario, cfg, E, dtype=np.float32)
-    if constants is not None:
-        from physical_cases import check_constants
-        check_constants(env.params, constants)
-        check_constants(orc.p, constants)
-    rp = oracle_reset_params(oracle_lib, env.params)
-    env.reset()
-    episodes = np.zeros(E, np.int64)
-    for e in range(E):
-        _oracle_reset(oracle_lib, orc, rp, seed, e, 0)
-    rng = np.random.RandomState(5)
-    n_done = n_viol = 0
-    ret = np.zeros(E, np.float32)
-    ret_sum = np.zeros(E, np.float32)
-    for t in range(steps):
-        a = rng.randint(0, n_act, size=(E, env.N)).astype(np.int32)
-        obs, rew, done, info = env.step(torch.as_tensor(a, device=env.device))
-        o_obs, o_rew, o_done, o_info = orc.step(a)
-        g = {"obs": obs.cpu().numpy(), "reward": rew.cpu().numpy(), "done": done.cpu().numpy().astype(np.uint8),
-             "dist": info["dist_travelled"].cpu().numpy(), "viol": info["violation"].cpu().numpy(),
-             "remaining": info["remaining"].cpu().numpy()}
-        assert np.array_equal(g["done"], o_done), t
-        assert np.array_equal(g["viol"], o_info["violation"]), t
-        assert np.array_equal(g["remaining"], o_info["remaining"]), t
-        assert np.array_equal(g["obs"].view(np.uint32), o_obs.view(np.uint32)), t
-        assert np.array_equal(g["reward"].view(np.uint32), o_rew.view(np.uint32)), t
-        assert np.array_equal(g["dist"].view(np.uint32), o_info["dist_travelled"].view(np.uint32)), t
-        assert np.array_equal(env.qp_sweeps.cpu().numpy(), orc.qp_sweeps), t
-        # rollout statistics (misc.py:178-185)
-        r = o_rew[:, 0] if env.params.shared_reward else o_rew.sum(axis=1, dtype=np.float32) if False else None
-        if env.params.shared_reward:
-            ret = ret + o_rew[:, 0]
-        else:
-            s = np.zeros(E, np.float32)
-            for k in range(env.N):
-                s = s + o_rew[:, k]
-            ret = ret + s
-        for e in np.nonzero(o_done)[0]:
-            ret_sum[e] = ret_sum[e] + ret[e]
-            ret[e] = 0
-            episodes[e] += 1
-            _oracle_reset(oracle_lib, orc, rp, seed, e, int(episodes[e]))
-        n_done += int(o_done.sum())
-        n_viol += int((o_info["violation"] > 0).sum())
-        # state after the (possibly reset) step
-        assert np.array_equal(env.poses.cpu().numpy().view(np.uint32), orc.poses.view(np.uint32)), t
-        assert np.array_equal(env.episode_steps.cpu().numpy(), orc.steps), t
-        if after_step is not None:
-            after_step(env, t)
-    assert n_done > 0 or E < 8 or not require_done
-    assert np.array_equal(env.done_count.cpu().numpy(), episodes)
-    assert np.array_equal(env.done_return_sum.cpu().numpy().view(np.uint32), ret_sum.view(np.uint32))
-    assert np.array_equal(env.ep_return.cpu().numpy().view(np.uint32), ret.view(np.uint32))
-    env.close()
+    rollout_bit_exact(scenario, ov, n_act, steps, oracle_lib, 192)
 
 
 def test_bench_size_properties():
@@ -236,32 +154,4 @@ def test_large_batch_dispatch_matches_lane_group_kernel(scenario, ov, n_act, E, 
 def test_rollout_entry_equals_repeated_steps(scenario, ov, n_act, E):
     """rg_rollout (K steps in one launch, envs advancing independently) against K rg_step launches:
     every per-step output and the final state, bit for bit, across auto-resets."""
-    _rollout_equals_steps(scenario, ov, n_act, E)
-
-
-def _rollout_equals_steps(scenario, ov, n_act, E, K=48, reps=3, require_done=True, time_limit=None):
-    import torch
-    from marbler_amd import VecRobotariumEnv
-    a = VecRobotariumEnv(scenario, E, overrides=ov, seed=21)
-    b = VecRobotariumEnv(scenario, E, overrides=ov, seed=21)
-    g = torch.Generator(device=a.device)
-    g.manual_seed(4)
-    a.reset()
-    b.reset()
-    for rep in range(reps):   # several launches of K steps: the state carries over between launches
-        acts = torch.randint(0, n_act, (K, E, a.N), generator=g, device=a.device, dtype=torch.int32)
-        out = a.rollout(acts)
-        for k in range(K):
-            obs, rew, done, info = b.step(acts[k])
-            assert torch.equal(out["obs"][k].view(torch.int32), obs.view(torch.int32)), (rep, k)
-            assert torch.equal(out["reward"][k].view(torch.int32), rew.view(torch.int32)), (rep, k)
-            assert torch.equal(out["done"][k].bool(), done), (rep, k)
-            assert torch.equal(out["dist_travelled"][k].view(torch.int32), info["dist_travelled"].view(torch.int32))
-            assert torch.equal(out["violation"][k], info["violation"]) and torch.equal(out["remaining"][k], info["remaining"])
-    sa, sb = a.state_dict(), b.state_dict()
-    for key in sa:
-        assert torch.equal(sa[key], sb[key]), key
-    assert torch.equal(a.done_count, b.done_count) and (int(a.done_count.sum()) > 0 or not require_done)
-    assert torch.equal(a.done_return_sum.view(torch.int32), b.done_return_sum.view(torch.int32))
-    a.close()
-    b.close()
+    rollout_equals_steps(scenario, ov, n_act, E)

@@ -15,9 +15,7 @@ import itertools
 import numpy as np
 import pytest
 
-from test_gpu_baseline_shapes import expected_slots
-from test_gpu_redzone import _guarded_class
-from test_gpu_span16_epilogue import OUTS, STATE
+from gpu_helpers import ROW_STATE as STATE, STEP_OUTS as OUTS, expected_slots, guarded_class, lane_group_kernel  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -30,11 +28,6 @@ CONFIGS = [("pcp-n5", "PredatorCapturePrey", {"predator": 3, "capture": 2, "n_ag
            ("simple-n7", "Simple", {"n_agents": 7}, 5)]
 FLAGS = ("stats", "shared_reward", "qp_stats", "auto_reset", "capability_aware")
 CASES = [(c, E) for c in CONFIGS for E in SLOTS]
-
-
-@pytest.fixture(autouse=True)
-def _lane_group_kernel(monkeypatch):
-    monkeypatch.setenv("RG_STEP_KERNEL", "group")
 
 
 def _unbind_statistics(env):
@@ -55,7 +48,7 @@ def _make(scenario, ov, E, span, flags, monkeypatch):
     else:
         monkeypatch.setenv("RG_STEP_SPAN", "0")
     if span and E == 2049:
-        env = _guarded_class()(scenario, E, slab_bytes=E * 8192 + (8 << 20), **kw)
+        env = guarded_class()(scenario, E, slab_bytes=E * 8192 + (8 << 20), **kw)
     else:
         env = VecRobotariumEnv(scenario, E, **kw)
     monkeypatch.delenv("RG_STEP_SPAN", raising=False)

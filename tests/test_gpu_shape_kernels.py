@@ -12,62 +12,18 @@ the chunk replays and the long QPs all ran.
 """
 import ctypes as C
 
-import numpy as np
 import pytest
 
-from test_gpu_baseline_shapes import expected_slots
-from test_gpu_redzone import _guarded_class
-from test_shape_kernels import REFERENCE, SCENARIOS, _match, _params, perturbed_cases, table
+from gpu_helpers import expected_slots, lane_group_kernel  # noqa: F401  (the fixture)
+from shape_kernel_harness import OUTS, SHAPE_IDS, actions as _actions, differing as _differing, make as _make
+from test_shape_kernels import REFERENCE, _match, _params, perturbed_cases
 
 pytestmark = pytest.mark.gpu
 
 STEPS = 100
-N_ACT = {"PredatorCapturePrey": 5, "Warehouse": 5, "MaterialTransport": 20}
 STRESS = {"PredatorCapturePrey": {"max_episode_steps": 8, "start_dist": 0.2}, "Warehouse": {"max_episode_steps": 8, "start_dist": 0.3},
           "MaterialTransport": {"max_episode_steps": 8, "start_dist": 0.2}}
-OUTS = ("obs", "reward", "done_u8", "dist_travelled", "violation", "remaining", "qp_sweeps")
 PERTURBED = perturbed_cases()
-
-
-class _ShapeIds(dict):   # scenario -> the id of its row of the library's table (read on first use, not at collection)
-    def __missing__(self, scenario):
-        self.update({SCENARIOS[r["scenario"]]: r["id"] for r in table()})
-        return self[scenario]
-
-
-SHAPE_IDS = _ShapeIds()
-
-
-@pytest.fixture(autouse=True)
-def _lane_group_kernel(monkeypatch):
-    monkeypatch.setenv("RG_STEP_KERNEL", "group")
-
-
-def _make(scenario, ov, E, monkeypatch, env_vars=(), guarded=False, seed=7):
-    from marbler_amd import VecRobotariumEnv
-    with monkeypatch.context() as m:   # read by rg_create
-        for k in ("RG_STEP_SHAPE", "RG_STEP_SPAN", "RG_STEP_RESIDENT"):
-            m.delenv(k, raising=False)
-        for k, v in env_vars:
-            m.setenv(k, v)
-        kw = dict(overrides=ov, seed=seed, auto_reset=True, collect_qp_stats=True)
-        env = _guarded_class()(scenario, E, slab_bytes=E * 8192 + (8 << 20), **kw) if guarded else VecRobotariumEnv(scenario, E, **kw)
-    env.reset()
-    assert env.step_kernel == "group"
-    return env
-
-
-def _actions(env, scenario, count, seed=11):
-    import torch
-    rng = np.random.RandomState(seed)
-    return [torch.as_tensor(rng.randint(0, N_ACT[scenario], size=(env.E, env.N)).astype(np.int32), device=env.device) for _ in range(count)]
-
-
-def _differing(a, b):
-    import torch
-    bad = [k for k in OUTS if not torch.equal(getattr(a, k), getattr(b, k))]
-    bad += [k for k in a.STATE_KEYS if not torch.equal(getattr(a, k), getattr(b, k))]
-    return bad
 
 
 class _Happened:

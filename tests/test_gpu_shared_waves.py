@@ -17,26 +17,18 @@ import os
 import pytest
 import torch
 
-import test_gpu_lidar as lidar
-import test_gpu_teams as teams
-from test_gpu_baseline_shapes import expected_slots, shape_rollout_vs_oracle
-from test_gpu_wrapper import fused_time_limit_vs_composed
+import lidar_harness as lidar
+import team_harness as teams
+from gpu_helpers import expected_slots, fused_time_limit_vs_composed, lane_group_kernel, random_actions  # noqa: F401  (the fixture)
+from physical_cases import MT6, PCP5, PCP12, WH8
+from rollout_harness import shape_rollout_vs_oracle
 
 pytestmark = pytest.mark.gpu
 
 EP = {"max_episode_steps": 8}
 IPM = {"barrier_solver": "cvxopt"}
-PCP5 = {"predator": 3, "capture": 2, "n_agents": 5}
-WH8 = {"n_agents": 8}
-MT6 = {"n_agents": 6, "n_fast_agents": 3, "n_slow_agents": 3, "start_dist": 0.25}
-PCP12 = {"predator": 6, "capture": 6, "n_agents": 12, "num_prey": 10, "start_dist": 0.25, "num_neighbors": 4}
 SIMPLE12 = {"n_agents": 12, "start_dist": 0.2}
 MT10 = {"n_agents": 10, "n_fast_agents": 5, "n_slow_agents": 5, "start_dist": 0.25, "capability_aware": True}
-
-
-@pytest.fixture(autouse=True)
-def _lane_group_kernel(monkeypatch):
-    monkeypatch.setenv("RG_STEP_KERNEL", "group")
 
 
 # ---------------------------------------------------------------- 1. bit-exact against the float32 oracle
@@ -139,14 +131,14 @@ def test_get_obs_returns_the_observation_of_the_step(family):
     E = 2049
     assert expected_slots(5, E) == 4
     if family == "lidar":
-        env = lidar._env("PredatorCapturePrey", E, 16, seed=4, auto_reset=False)
+        env = lidar.make_env("PredatorCapturePrey", E, 16, seed=4, auto_reset=False)
     else:
-        env = teams._env("PredatorCapturePrey", E, teams=teams._pool4("PredatorCapturePrey", 5) if family == "team" else None,
+        env = teams.make_env("PredatorCapturePrey", E, teams=teams.pool4("PredatorCapturePrey", 5) if family == "team" else None,
                          seed=4, auto_reset=False)
     assert env.N == 5 and env.step_kernel == "group"
     assert (env.lidar is not None and env.lidar.rays == 16) == (family == "lidar") and (env.teams is not None) == (family == "team")
     env.reset()
-    acts = teams._actions(env, 1, seed=6)
+    acts = random_actions(env, 1, seed=6)
     stepped = env.step(acts[0])[0].clone()
     again = env.get_obs(torch.full_like(stepped, float("nan")))
     torch.cuda.synchronize()

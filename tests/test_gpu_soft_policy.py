@@ -15,7 +15,7 @@ import pytest
 import torch
 
 import soft_twin
-from test_gpu_actor import _random_actor
+from gpu_helpers import random_actor, runners_agree as _assert_same_state
 
 pytestmark = pytest.mark.gpu
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -50,7 +50,7 @@ def _fixture_sd(name):
 ])
 def test_sampled_launch_matches_the_twin(shared, H, E, N, D, A, use_rnn, pack, restart_flags):
     from marbler_amd.evaluate import BatchedActor, soft_select
-    sd = _random_actor(1 if shared else N, D + N, H, A, use_rnn, seed=H + E + A)
+    sd = random_actor(1 if shared else N, D + N, H, A, use_rnn, seed=H + E + A)
     for k in sd:   # logits a few units apart (the random heads alone give near-uniform rows), one column that can never be chosen
         if k.endswith("fc2.weight"):
             sd[k] = sd[k] * 12.0
@@ -92,7 +92,7 @@ def test_sampled_launch_matches_the_twin(shared, H, E, N, D, A, use_rnn, pack, r
 
 def test_python_argument_checks_on_the_device():
     from marbler_amd.evaluate import BatchedActor
-    actor = BatchedActor(_random_actor(1, 13, 64, 5, True, seed=1), 4, device=DEV)
+    actor = BatchedActor(random_actor(1, 13, 64, 5, True, seed=1), 4, device=DEV)
     obs, hidden = torch.zeros(3, 4, 9, device=DEV), torch.zeros(3, 4, 64, device=DEV)
     u = torch.zeros(3, 4, device=DEV)
     with pytest.raises(ValueError, match="do not combine"):
@@ -127,7 +127,7 @@ def _actor_for(weights, v):
         sd = _fixture_sd(weights)
     else:
         _, shared, H = weights
-        sd = _random_actor(1 if shared else N, v.obs_size + N, H, v.n_actions, True, seed=4)
+        sd = random_actor(1 if shared else N, v.obs_size + N, H, v.n_actions, True, seed=4)
         for k in sd:
             if k.endswith("fc2.weight"):
                 sd[k] = sd[k] * 8.0
@@ -147,17 +147,6 @@ def _assert_same_dict(x, y):
             assert np.array_equal(_bits(x[k]), _bits(y[k])), k
         else:
             assert torch.equal(x[k], y[k]), k
-
-
-def _assert_same_state(r1, r2):
-    (v1, a), (v2, b) = r1, r2
-    torch.cuda.synchronize()
-    assert torch.equal(a.hidden, b.hidden) and torch.equal(a._restart, b._restart)
-    assert torch.equal(v1.get_obs(), v2.get_obs()) and torch.equal(v1._ended, v2._ended)
-    assert v1.get_stats() == v2.get_stats()
-    s1, s2 = v1.env.state_dict(), v2.env.state_dict()
-    for k in s1:
-        assert torch.equal(s1[k], s2[k]), k
 
 
 @pytest.mark.parametrize("name,key,ov,weights", CASES, ids=[c[0] for c in CASES])
@@ -239,16 +228,16 @@ def test_policy_rollout_sample_refusals_with_a_handle():
         torch.cuda.synchronize()
         return rc, lib.rg_last_error().decode()
 
-    good = BatchedActor(_random_actor(1, v.obs_size + N, 64, 5, True, seed=2), N, device=DEV)
+    good = BatchedActor(random_actor(1, v.obs_size + N, 64, 5, True, seed=2), N, device=DEV)
     assert call(good)[0] == 0
     assert call(good, sample=False)[0] == -55
     rc, msg = call(good, explore=u.data_ptr())
     assert rc == -56 and "explore_u" in msg
     assert call(good, T_=0)[0] == -27
-    rc, msg = call(BatchedActor(_random_actor(1, v.obs_size + N, 64, 5, True, seed=2), N, device=DEV, pack_gru="bf16x3"))
+    rc, msg = call(BatchedActor(random_actor(1, v.obs_size + N, 64, 5, True, seed=2), N, device=DEV, pack_gru="bf16x3"))
     assert rc == -41 and "gru_packed == 3" in msg
-    assert call(BatchedActor(_random_actor(1, v.obs_size + N, 64, 5, False, seed=2), N, use_rnn=False, device=DEV))[0] == -41
-    assert call(BatchedActor(_random_actor(1, v.obs_size + N + 1, 64, 5, True, seed=2), N, device=DEV))[0] == -44
+    assert call(BatchedActor(random_actor(1, v.obs_size + N, 64, 5, False, seed=2), N, use_rnn=False, device=DEV))[0] == -41
+    assert call(BatchedActor(random_actor(1, v.obs_size + N + 1, 64, 5, True, seed=2), N, device=DEV))[0] == -44
     rc, msg = call(good, io=_lib.RgStepIO.from_buffer_copy(VecRobotariumEnvIO(env)))
     assert rc == -29 and "gymma block" in msg
     ipm = GymmaVecEnv("robotarium_gym:PredatorCapturePrey-v0", 8, time_limit=10, seed=1, overrides={"barrier_solver": "cvxopt"})

@@ -16,9 +16,6 @@ SHAPES = [("PredatorCapturePrey", {"predator": 3, "capture": 2, "n_agents": 5}, 
           ("MaterialTransport", {"n_agents": 6, "n_fast_agents": 3, "n_slow_agents": 3, "start_dist": 0.25}, 20, 200, 2048),
           ("Simple", {"n_agents": 7}, 5, 200, 300)]
 
-STATE = ("poses", "carry_dist", "episode_steps", "reset_count", "prey_loc", "prey_sensed", "prey_captured", "loaded", "load",
-         "zone_load", "messages", "ep_return", "done_return_sum", "done_count", "done_steps_sum")
-
 
 def _make(scenario, ov, E, span, monkeypatch):
     from marbler_amd import VecRobotariumEnv
@@ -37,6 +34,7 @@ def _make(scenario, ov, E, span, monkeypatch):
 @pytest.mark.parametrize("scenario,ov,n_act,steps,E", SHAPES)
 def test_span16_rows_match_eight_lane_groups_word_for_word(scenario, ov, n_act, steps, E, monkeypatch):
     import torch
+    from gpu_helpers import ROW_STATE as STATE, differing
     new = _make(scenario, ov, E, True, monkeypatch)
     old = _make(scenario, ov, E, False, monkeypatch)
     assert new.step_kernel == old.step_kernel == "group"
@@ -44,23 +42,15 @@ def test_span16_rows_match_eight_lane_groups_word_for_word(scenario, ov, n_act, 
     n_done = n_viol = n_sweeps = 0
     for t in range(steps):
         a = torch.as_tensor(rng.randint(0, n_act, size=(E, new.N)).astype(np.int32), device=new.device)
-        outs = []
-        for env in (new, old):
-            obs, rew, done, info = env.step(a)
-            torch.cuda.synchronize()
-            outs.append([obs.cpu().numpy().view(np.uint32), rew.cpu().numpy().view(np.uint32), done.cpu().numpy(),
-                         info["dist_travelled"].cpu().numpy().view(np.uint32), info["violation"].cpu().numpy(),
-                         info["remaining"].cpu().numpy(), env.qp_sweeps.cpu().numpy()])
-        for name, x, y in zip(("obs", "reward", "done", "dist_travelled", "violation", "remaining", "qp_sweeps"), *outs):
-            assert np.array_equal(x, y), f"{scenario} step {t}: {name} differs in {int(np.sum(x != y))} words"
-        n_done += int(outs[0][2].astype(bool).sum())
-        n_viol += int((outs[0][4] != 0).sum())
-        n_sweeps = max(n_sweeps, int(outs[0][6].max()))
-    for name in STATE:
-        x, y = getattr(new, name, None), getattr(old, name, None)
-        if x is None:
-            continue
-        assert np.array_equal(x.cpu().numpy().view(np.uint8), y.cpu().numpy().view(np.uint8)), f"{scenario}: state {name} differs"
+        new.step(a)
+        old.step(a)
+        bad = differing(new, old, ("obs", "reward", "done_u8", "dist_travelled", "violation", "remaining", "qp_sweeps"))
+        assert not bad, f"{scenario} step {t}: {bad} differ"
+        n_done += int(new.done_u8.sum())
+        n_viol += int((new.violation != 0).sum())
+        n_sweeps = max(n_sweeps, int(new.qp_sweeps.max()))
+    bad = differing(new, old, STATE)
+    assert not bad, f"{scenario}: state {bad} differs"
     # the rollouts went through resets, collisions (the pre-test fall-backs and the exact replay) and multi-sweep QPs
     assert n_done > 0 and n_viol > 0 and n_sweeps > 2, (n_done, n_viol, n_sweeps)
 

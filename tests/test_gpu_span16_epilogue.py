@@ -8,19 +8,12 @@ whenever the lane-group dispatch picks at most four env slots per wave (`expecte
 import numpy as np
 import pytest
 
-from test_gpu_baseline_shapes import expected_slots, shape_rollout_vs_oracle
+from gpu_helpers import ROW_STATE as STATE, STEP_OUTS as OUTS, expected_slots, guarded_class, lane_group_kernel  # noqa: F401  (the fixture)
+from rollout_harness import shape_rollout_vs_oracle
 
 pytestmark = pytest.mark.gpu
 
-STATE = ("poses", "carry_dist", "episode_steps", "reset_count", "prey_loc", "prey_sensed", "prey_captured", "loaded", "load",
-         "zone_load", "messages", "ep_return", "done_return_sum", "done_count", "done_steps_sum")
-OUTS = ("obs", "reward", "done", "dist_travelled", "violation", "remaining", "qp_sweeps")
 SLOTS = {7: 1, 1025: 2, 2049: 4}
-
-
-@pytest.fixture(autouse=True)
-def _lane_group_kernel(monkeypatch):
-    monkeypatch.setenv("RG_STEP_KERNEL", "group")
 
 
 def _pair(scenario, ov, E, monkeypatch, auto_reset=True):
@@ -252,12 +245,11 @@ def test_replica_stores_leave_the_red_zones_intact(name, scenario, ov, n_act, mo
     env's, which has ordinary allocations."""
     import torch
     from marbler_amd import VecRobotariumEnv
-    from test_gpu_redzone import _guarded_class
     E = 2049
     monkeypatch.setenv("RG_STEP_SPAN", "0")
     old = VecRobotariumEnv(scenario, E, overrides=ov, seed=7, collect_qp_stats=True)
     monkeypatch.delenv("RG_STEP_SPAN", raising=False)
-    new = _guarded_class()(scenario, E, overrides=ov, seed=7, collect_qp_stats=True, slab_bytes=E * 8192 + (8 << 20))
+    new = guarded_class()(scenario, E, overrides=ov, seed=7, collect_qp_stats=True, slab_bytes=E * 8192 + (8 << 20))
     assert new.step_kernel == old.step_kernel == "group" and expected_slots(new.N, E) == 4
     new.reset()
     old.reset()

@@ -1,66 +1,20 @@
 """The team pool on the GPU (DESIGN.md "Team pool"): non-interference with a one-set pool of the config's own values, mixed teams
-bit for bit against the float32 oracle loaded with each env's set, the index draw against its NumPy twin (tests/team_twin.py) on
+against the float32 oracle loaded with each env's set (tests/team_harness.py; what is compared: tests/oracle_check.py), the index draw against its NumPy twin (tests/team_twin.py) on
 every reset path, its frequencies, the fixed mode and sharding, bit identity across the paths that step a pooled env, snapshots,
 BatchedRunner, and guard slabs around the pool's arrays."""
 import numpy as np
 import pytest
 import torch
 
-from helpers import STATE_KEYS, GPU_NAME
+from gpu_helpers import (guarded_class, random_actions as _actions, random_actor, rollout_equals_single_steps, runner_batch_replays,
+                         same_bits as _same)
+from team_harness import SCN_OV, make_env as _env, mixed_teams_vs_oracle, pool4 as _pool4
 from team_twin import expected_after_reset
-from test_gpu_actor import _random_actor
-from test_gpu_redzone import _guarded_class
 
 pytestmark = pytest.mark.gpu
 
-SCN_OV = {"PredatorCapturePrey": {"predator": 3, "capture": 2, "n_agents": 5},
-          "Warehouse": {"n_agents": 8},
-          "MaterialTransport": {"n_agents": 6, "n_fast_agents": 3, "n_slow_agents": 3, "start_dist": 0.25},
-          "Simple": {}}
-N_ACT = {"MaterialTransport": 20}
 SOLVERS = ("exact", "cvxopt")
 OUT_KEYS = ("obs", "reward", "done_u8", "dist_travelled", "violation", "remaining")
-
-
-def _env(scenario, E, ov=None, teams=None, sampling="episode", **kw):
-    from marbler_amd.vec_env import VecRobotariumEnv
-    o = dict(SCN_OV.get(scenario, {}), **(ov or {}))
-    if teams is not None:
-        o.update(teams=teams, team_sampling=sampling)
-    return VecRobotariumEnv(scenario, E, overrides=o, device="cuda:0", **kw)
-
-
-def _actions(env, T, seed):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return torch.randint(0, N_ACT.get(env.scenario, 5), (T, env.E, env.N), generator=g, dtype=torch.int32).to(env.device)
-
-
-def _bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
-
-
-def _same(a, b):
-    return torch.equal(_bits(a), _bits(b))
-
-
-def _pool4(scenario, N):
-    """Four sets that differ in every capability of the scenario; set 3 gives agent 0 both radii 0."""
-    r = np.random.RandomState(N)
-    if scenario == "PredatorCapturePrey":
-        sets = []
-        for t, npred in enumerate((3 * N // 4, N // 2, N // 4, N // 2)):
-            sr = [float(np.float32(0.3 + 0.1 * t)) if a < npred else 0.0 for a in range(N)]
-            cr = [0.0 if a < npred else float(np.float32(0.15 + 0.05 * t)) for a in range(N)]
-            sd = [float(np.float32(x)) for x in r.choice([0.12, 0.2, 0.3], N)]
-            if t == 3:
-                sr[0] = cr[0] = 0.0
-            sets.append({"sensing_radius": sr, "capture_radius": cr, "step_dist": sd})
-        return sets
-    if scenario == "MaterialTransport":
-        return [{"speed": [float(np.float32(x)) for x in r.choice([0.1, 0.2, 0.3], N)], "torque": [int(x) for x in r.randint(0, 12, N)]}
-                for _ in range(4)]
-    return [{"step_dist": [float(np.float32(x)) for x in r.choice([0.1, 0.2, 0.3, 0.4], N)]} for _ in range(4)]
 
 
 # ---------------------------------------------------------------- 1. non-interference
@@ -109,75 +63,9 @@ ORACLE_CASES = [("PredatorCapturePrey", {"predator": 2, "capture": 2, "n_agents"
                 ("Simple", {}, "exact")]
 
 
-def _gpu_state(env):
-    return {k: getattr(env, GPU_NAME.get(k, k)).cpu().numpy() for k in STATE_KEYS}
-
-
-def _load_oracle(orc, env, state, t):
-    for k in STATE_KEYS:
-        arr = getattr(orc, k)
-        arr[...] = state[k].astype(arr.dtype).reshape(arr.shape)
-    pool = env.teams
-    for a in range(env.N):
-        orc.p.agent_step[a] = float(pool.agent_step[t, a])
-        orc.p.sensing_radius[a] = float(pool.sensing_radius[t, a])
-        orc.p.capture_radius[a] = float(pool.capture_radius[t, a])
-        orc.p.torque[a] = int(pool.torque[t, a])
-
-
 @pytest.mark.parametrize("scenario,ov,solver", ORACLE_CASES)
 def test_mixed_teams_are_bit_exact_against_the_float32_oracle(scenario, ov, solver, oracle_lib):
     mixed_teams_vs_oracle(scenario, ov, solver, oracle_lib, 256, 80, 15)
-
-
-def mixed_teams_vs_oracle(scenario, ov, solver, oracle_lib, E, T, episode_steps, before_first_step=None, threads=1):
-    """Four oracles, one per set of `_pool4`, each loaded with the GPU's state before every step; env e is held to the oracle of
-    its own set.  before_first_step(env): called after the reset, for what a caller asserts about the draw.  threads: the oracles'."""
-    ov = dict(ov, barrier_solver=solver, max_episode_steps=episode_steps)
-    N = int(dict(SCN_OV[scenario], **ov).get("n_agents", 4))
-    env = _env(scenario, E, ov, teams=_pool4(scenario, N), seed=11, auto_reset=False, collect_qp_stats=True)
-    cfg = dict(env.cfg)
-    cfg.pop("teams")
-    cfg.pop("team_sampling")
-    orcs = [oracle_lib.OracleVecEnv(scenario, cfg, E, dtype=np.float32) for _ in range(4)]
-    env.reset()
-    if before_first_step is not None:
-        before_first_step(env)
-    acts = _actions(env, T, seed=3).cpu().numpy()
-    changes, seen = 0, set()
-    for step in range(T):
-        team = env.team_index.cpu().numpy()
-        seen |= set(team.tolist())
-        pre = _gpu_state(env)
-        for t in range(4):
-            _load_oracle(orcs[t], env, pre, t)
-        env.step(torch.as_tensor(acts[step], device=env.device))
-        g = {"obs": env.obs, "reward": env.reward, "done": env.done_u8, "dist": env.dist_travelled, "viol": env.violation,
-             "remaining": env.remaining}
-        g = {k: v.cpu().numpy() for k, v in g.items()}
-        post = _gpu_state(env)
-        for t in range(4):
-            rows = np.nonzero(team == t)[0]
-            if rows.size == 0:
-                continue
-            o_obs, o_rew, o_done, o_info = orcs[t].step(acts[step], threads=threads)
-            msg = (step, t)
-            assert np.array_equal(g["obs"][rows].view(np.uint32), o_obs[rows].view(np.uint32)), msg
-            assert np.array_equal(g["reward"][rows].view(np.uint32), o_rew[rows].view(np.uint32)), msg
-            assert np.array_equal(g["done"][rows], o_done[rows]), msg
-            assert np.array_equal(g["dist"][rows].view(np.uint32), o_info["dist_travelled"][rows].view(np.uint32)), msg
-            assert np.array_equal(g["viol"][rows], o_info["violation"][rows]), msg
-            assert np.array_equal(g["remaining"][rows], o_info["remaining"][rows]), msg
-            for k in STATE_KEYS:
-                a, b = post[k][rows], getattr(orcs[t], k)[rows].astype(post[k].dtype)
-                assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), (msg, k)
-        done = env.done_u8.clone()
-        if bool(done.any()):
-            before = env.team_index.clone()
-            env.reset(mask=done)
-            changes += int((env.team_index != before).sum())
-    assert seen == {0, 1, 2, 3} and changes > 0
-    env.close()
 
 
 # ---------------------------------------------------------------- 3. the draw
@@ -274,15 +162,7 @@ def test_rollout_equals_single_steps(scenario, solver):
     r = _env(scenario, E, ov, teams=teams, seed=21)
     s.reset()
     r.reset()
-    acts = _actions(s, K, seed=6)
-    out = r.rollout(acts)
-    for t in range(K):
-        s.step(acts[t])
-        for k, ko in (("obs", "obs"), ("reward", "reward"), ("done_u8", "done"), ("dist_travelled", "dist_travelled"),
-                      ("violation", "violation"), ("remaining", "remaining")):
-            assert _same(getattr(s, k), out[ko][t]), (t, k)
-    for k in s.STATE_KEYS + ("team_index",):
-        assert _same(getattr(s, k), getattr(r, k)), k
+    rollout_equals_single_steps(s, r, _actions(s, K, seed=6), more_state=("team_index",))
 
 
 def test_gymma_step_and_get_obs_equal_the_plain_step():
@@ -343,18 +223,12 @@ def test_batched_runner_two_launch_path_and_one_launch_refusals():
     v = GymmaVecEnv("robotarium_gym:PredatorCapturePrey-v0", E, time_limit=5, seed=3, overrides=ov)
     assert v.env.teams is not None and v.env.teams.n_sets == 4
     N = v.n_agents
-    actor = BatchedActor(_random_actor(1, v.obs_size + N, 64, v.n_actions, True, seed=4), N, device=v.env.device)
+    actor = BatchedActor(random_actor(1, v.obs_size + N, 64, v.n_actions, True, seed=4), N, device=v.env.device)
     runner = BatchedRunner(v, actor, epsilon=0.1, seed=1)
     out = runner.run(T)
     torch.cuda.synchronize()
     assert out["obs"].shape == (T + 1, E, N, v.obs_size)
-    w = GymmaVecEnv("robotarium_gym:PredatorCapturePrey-v0", E, time_limit=5, seed=3, overrides=ov)
-    w.reset()
-    for t in range(T):
-        _, ended, _ = w.step(out["actions"][t])
-        torch.cuda.synchronize()
-        assert torch.equal(ended, out["terminated"][t])
-        assert torch.equal(w.get_obs(), out["obs"][t + 1])
+    runner_batch_replays(out, "robotarium_gym:PredatorCapturePrey-v0", E, T, ov)
     with pytest.raises(ValueError, match="team"):
         runner.run(T, one_launch=True)
     with pytest.raises(ValueError, match="team"):
@@ -363,7 +237,7 @@ def test_batched_runner_two_launch_path_and_one_launch_refusals():
 
 # ---------------------------------------------------------------- 5. guards
 def test_guard_slabs_around_the_pool_stay_untouched():
-    Guarded = _guarded_class()
+    Guarded = guarded_class()
     for scenario in ("PredatorCapturePrey", "MaterialTransport"):
         E = 65
         o = dict(SCN_OV[scenario], teams=_pool4(scenario, SCN_OV[scenario]["n_agents"]), max_episode_steps=5)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import yaml
 
+from gpu_helpers import fused_time_limit_vs_composed, random_actor
 from helpers import GPU_NAME, GOLDEN_DIR, load_golden, pre_state
 
 pytestmark = pytest.mark.gpu
@@ -115,10 +116,9 @@ def test_batched_runner_collects_transitions():
     import torch
     from marbler_amd.evaluate import BatchedActor
     from marbler_amd.gymma import BatchedRunner, GymmaVecEnv
-    from test_gpu_actor import _random_actor
     E, T = 128, 120
     v = GymmaVecEnv("robotarium_gym:PredatorCapturePrey-v0", E, time_limit=1000, seed=3)
-    actor = BatchedActor(_random_actor(1, v.obs_size + v.n_agents, 64, v.n_actions, True, seed=2), v.n_agents,
+    actor = BatchedActor(random_actor(1, v.obs_size + v.n_agents, 64, v.n_actions, True, seed=2), v.n_agents,
                          device=v.env.device)
     runner = BatchedRunner(v, actor, epsilon=0.3, seed=1)
     b = runner.run(T)
@@ -160,13 +160,12 @@ def test_batched_runner_in_place_path_equals_the_composed_one(key, ov, limit, ep
     import torch
     from marbler_amd.evaluate import BatchedActor
     from marbler_amd.gymma import BatchedRunner, GymmaVecEnv
-    from test_gpu_actor import _random_actor
     monkeypatch.setenv("RG_STEP_KERNEL", kernel)
     E, T = 96, 70
     batches = []
     for fused in (True, False):
         v = GymmaVecEnv(key, E, time_limit=limit, seed=5, fused=fused, overrides=ov or None)
-        actor = BatchedActor(_random_actor(1, v.obs_size + v.n_agents, 64, v.n_actions, True, seed=4), v.n_agents, device=v.env.device)
+        actor = BatchedActor(random_actor(1, v.obs_size + v.n_agents, 64, v.n_actions, True, seed=4), v.n_agents, device=v.env.device)
         runner = BatchedRunner(v, actor, epsilon=epsilon, seed=9)
         b = runner.run(T)
         b2 = runner.run(7)       # a second call continues the same episodes
@@ -225,40 +224,6 @@ def test_fused_time_limit_equals_the_composed_gymma_step(kernel, key, ov, n_act,
     consumer sees next, the episode statistics and the env state, step after step through truncations and resets."""
     monkeypatch.setenv("RG_STEP_KERNEL", kernel)
     fused_time_limit_vs_composed(key, ov, n_act, limit, 256, 90)
-
-
-def fused_time_limit_vs_composed(key, ov, n_act, limit, E, steps):
-    """(RG_STEP_KERNEL is the caller's business.)"""
-    import torch
-    from marbler_amd.gymma import GymmaVecEnv
-    a = GymmaVecEnv(key, E, time_limit=limit, overrides=ov, seed=5, fused=True)
-    b = GymmaVecEnv(key, E, time_limit=limit, overrides=ov, seed=5, fused=False)
-    assert a.env.time_limit == limit and b.env.time_limit == 0
-    a.reset()
-    b.reset()
-    g = torch.Generator(device=a.env.device)
-    g.manual_seed(3)
-    n_trunc = n_done = 0
-    for t in range(steps):
-        act = torch.randint(0, n_act, (E, a.n_agents), generator=g, device=a.env.device, dtype=torch.int32)
-        ra, ta, ia = a.step(act)
-        rb, tb, ib = b.step(act)
-        assert torch.equal(ta, tb) and torch.equal(ia["TimeLimit.truncated"], ib["TimeLimit.truncated"]), t
-        assert torch.allclose(ra, rb, rtol=0, atol=1e-5), t
-        assert torch.equal(a.get_obs().view(torch.int32), b.get_obs().view(torch.int32)), t
-        assert torch.equal(a.get_state(), a.get_obs().reshape(E, -1))
-        for k in ("violation", "remaining", "dist_travelled"):
-            assert torch.equal(ia[k], ib[k]), (t, k)
-        assert torch.equal(a.env.poses.view(torch.int32), b.env.poses.view(torch.int32)), t
-        assert torch.equal(a.env.episode_steps, b.env.episode_steps) and torch.equal(a.env.reset_count, b.env.reset_count)
-        n_trunc += int(ia["TimeLimit.truncated"].sum())
-        n_done += int(ta.sum())
-    sa, sb = a.get_stats(), b.get_stats()
-    assert sa["episodes"] == sb["episodes"] == n_done and sa["steps"] == sb["steps"]
-    assert abs(sa["return_sum"] - sb["return_sum"]) < 1e-3 * max(1.0, abs(sb["return_sum"]))
-    assert n_done > E // 2 and (n_trunc > E if limit < 50 else n_trunc == 0)
-    a.close()
-    b.close()
 
 
 def test_gymma_step_outputs_survive_the_next_step():

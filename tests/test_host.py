@@ -428,7 +428,7 @@ def test_fuzzed_configurations_are_accepted_or_rejected_with_a_reason():
     block the kernels would index out of range with."""
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    from test_gpu_config_fuzz import draw_config_extended
+    from fuzz_cases import draw_config_extended
     from marbler_amd.params import load_config, make_params
     from marbler_amd._lib import MAX_AGENTS, MAX_PREY
     accepted = 0

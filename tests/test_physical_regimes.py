@@ -15,9 +15,9 @@ constant shows up here first.  They were read off the oracle, never off the code
 import numpy as np
 import pytest
 
-from helpers import oracle_reset, oracle_reset_params
-from physical_cases import (ACTION_SEED, DISPATCHES, N_ACT, REGIME_DISPATCH, REGIMES, RPS_DEFAULTS, SEED, STEPS, case_overrides,
-                            check_constants)
+from oracle_check import FreeRunningOracle
+from physical_cases import (ACTION_SEED, CASES, DISPATCHES, IPM_CASES, N_ACT, REGIME_DISPATCH, REGIMES, RPS_DEFAULTS, SEED, STEPS,
+                            case_overrides, check_constants)
 
 from marbler_amd.params import load_config, make_params
 
@@ -49,13 +49,11 @@ def oracle_alone(oracle_lib, regime, dispatch=DISPATCH, steps=STEPS):
     ov, consts = case_overrides(regime, dispatch)
     cfg = load_config(scenario, overrides=ov)
     params = make_params(scenario, cfg)
-    orc = oracle_lib.OracleVecEnv(scenario, cfg, E, dtype=np.float32)
+    side = FreeRunningOracle(oracle_lib, scenario, cfg, E, params, SEED)
+    orc = side.orc
     check_constants(orc.p, consts)
     check_constants(params, consts)
-    rp = oracle_reset_params(oracle_lib, params)
-    for e in range(E):
-        oracle_reset(oracle_lib, orc, rp, SEED, e, 0)
-    episodes = np.zeros(E, np.int64)
+    side.reset()
     rng = np.random.RandomState(ACTION_SEED)
     U = int(cfg["update_frequency"])
     one_period = U <= 15 and not cfg.get("robotarium", False)
@@ -86,9 +84,7 @@ def oracle_alone(oracle_lib, regime, dispatch=DISPATCH, steps=STEPS):
         bnd += int(((viol & 2) != 0).sum())
         sweeps = max(sweeps, int(orc.qp_sweeps.max()))
         assert all(np.isfinite(x).all() for x in (orc.obs, orc.reward, orc.poses)), t
-        for e in np.nonzero(done)[0]:
-            episodes[e] += 1
-            oracle_reset(oracle_lib, orc, rp, SEED, e, int(episodes[e]))
+        side.reset_ended()
     return (ended, coll, bnd, sweeps, wide, narrow, far, fast, slow, fresh)
 
 
@@ -179,10 +175,7 @@ def _stray_oracle(oracle_lib, n_agents, pose_id):
     from physical_cases import STRAY_E, STRAY_TEAMS, stray_poses
     scenario = "PredatorCapturePrey"
     cfg = load_config(scenario, overrides=dict(STRAY_TEAMS[n_agents], penalize_violations=True))
-    orc = oracle_lib.OracleVecEnv(scenario, cfg, STRAY_E, dtype=np.float32)
-    rp = oracle_reset_params(oracle_lib, make_params(scenario, cfg))
-    for e in range(STRAY_E):
-        oracle_reset(oracle_lib, orc, rp, SEED, e, 0)
+    orc = FreeRunningOracle.at_reset(oracle_lib, scenario, cfg, STRAY_E, make_params(scenario, cfg), SEED)
     orc.poses[...] = stray_poses(orc.poses, pose_id)
     return cfg, orc
 
@@ -214,10 +207,7 @@ def test_the_oracle_judges_the_loaded_pairs_as_the_gpu_test_expects(n_agents, or
     if n_agents == 5:
         ov, _ = case_overrides(LARGE_ARENA, DISPATCH)
         cfg = load_config("PredatorCapturePrey", overrides=dict(ov, penalize_violations=True))
-        orc = oracle_lib.OracleVecEnv("PredatorCapturePrey", cfg, STRAY_E, dtype=np.float32)
-        rp = oracle_reset_params(oracle_lib, make_params("PredatorCapturePrey", cfg))
-        for e in range(STRAY_E):
-            oracle_reset(oracle_lib, orc, rp, SEED, e, 0)
+        orc = FreeRunningOracle.at_reset(oracle_lib, "PredatorCapturePrey", cfg, STRAY_E, make_params("PredatorCapturePrey", cfg), SEED)
         orc.poses[...] = large_arena_poses(orc.poses)
         # a bound sized for the default arena would miss some of these pairs; the large arena's own holds for all of them
         from physical_cases import RPS_DEFAULTS as D, collision_points
@@ -232,12 +222,11 @@ def test_every_fuzz_draw_lies_inside_the_admitted_domain():
     """rg_create refuses a block outside the domain before it looks for a device: no draw of the GPU fuzz may be refused for
     its constants (without a GPU the call then fails for want of a device; with one it succeeds)."""
     import ctypes
-    import test_gpu_physical_constants as gpu
     from marbler_amd import _lib
     lib = _lib.load()
     lib.rg_create.restype = ctypes.c_void_p
     seen = {k: set() for k in RPS_DEFAULTS}
-    for scenario, ov, _, E, _ in gpu.CASES + gpu.IPM_CASES:
+    for scenario, ov, _, E, _ in CASES + IPM_CASES:
         p = make_params(scenario, load_config(scenario, overrides=ov))
         for k in seen:
             seen[k].add(ov[k])

@@ -6,7 +6,8 @@ import os
 import numpy as np
 import pytest
 
-from helpers import GOLDEN_DIR, oracle_reset, oracle_reset_params
+from helpers import GOLDEN_DIR
+from oracle_check import FreeRunningOracle
 
 REC = os.path.join(GOLDEN_DIR, "ZOO_EVAL.json")
 REPLAY = os.path.join(GOLDEN_DIR, "zoo_eval_replay.npz")
@@ -47,10 +48,7 @@ def test_replay_through_the_float32_oracle_reproduces_the_recorded_statistics(or
         T, E, N = acts.shape
         cfg = load_config(scenario, overrides=ov or None)
         p = make_params(scenario, cfg)
-        orc = oracle_lib.OracleVecEnv(scenario, cfg, E, dtype=np.float32)
-        rp = oracle_reset_params(oracle_lib, p)
-        for e in range(E):
-            oracle_reset(oracle_lib, orc, rp, int(z["seed"]), e, 0)
+        orc = FreeRunningOracle.at_reset(oracle_lib, scenario, cfg, E, p, int(z["seed"]))
         ret, dist = np.zeros(E, np.float64), np.zeros((E, N), np.float64)
         steps, active = np.zeros(E, np.int64), np.ones(E, bool)
         for j in range(T):

@@ -35,7 +35,7 @@ import numpy as np
 import torch
 from marbler_amd import _lib
 from marbler_amd.evaluate import BatchedActor
-from test_gpu_actor import _random_actor
+from gpu_helpers import random_actor
 
 
 def bind(path):
@@ -60,7 +60,7 @@ def case(lib, E, N, D, H, A, shared=True, use_rnn=True, reps=100, check=True, pa
     I = D + N
     if pack is True and not hasattr(lib, "rg_actor_pack_gru_bf16x3"):
         pack = "f32"
-    actor = BatchedActor(_random_actor(1 if shared else N, I, H, A, use_rnn, 3), N, use_rnn=use_rnn, device=dev, pack_gru=pack)
+    actor = BatchedActor(random_actor(1 if shared else N, I, H, A, use_rnn, 3), N, use_rnn=use_rnn, device=dev, pack_gru=pack)
     _lib._lib = lib            # BatchedActor.forward_fused / _weights_struct go through marbler_amd._lib.load()
     actor._ws = None
     g = torch.Generator(device=dev).manual_seed(1)

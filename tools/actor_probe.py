@@ -8,7 +8,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 from marbler_amd.evaluate import BatchedActor, DEFAULT_PACK_GRU
-from test_gpu_actor import _random_actor
+from gpu_helpers import random_actor
 E, N, D = 4096, 4, 16
 forms = [a for a in sys.argv[1:] if a in ("f16x2", "bf16x3", "f32")] or [DEFAULT_PACK_GRU]
 
@@ -28,7 +28,7 @@ def f64_reference(sd, obs, hidden, N):
 
 for form in forms:
     for H in (128, 64):
-        sd = _random_actor(1, D + N, H, 5, True, 3)
+        sd = random_actor(1, D + N, H, 5, True, 3)
         actor = BatchedActor(sd, N, device="cuda:0", pack_gru=form)
         g = torch.Generator(device="cuda:0").manual_seed(5)
         obs = torch.rand(E, N, D, device="cuda:0", generator=g) * 3 - 1.5

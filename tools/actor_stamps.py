@@ -12,7 +12,7 @@ if "--lib" in sys.argv:
 import numpy as np
 import torch
 from marbler_amd.evaluate import BatchedActor
-from test_gpu_actor import _random_actor
+from gpu_helpers import random_actor
 import ctypes
 from marbler_amd import _lib
 lib = ctypes.CDLL(LIB)
@@ -29,7 +29,7 @@ _lib._lib = lib     # the actor-only diagnostic build stands in for the library
 print(LIB)
 N, D = 4, 16
 for E, H in ((4096, 128), (4096, 64), (1024, 128)):
-    actor = BatchedActor(_random_actor(1, D + N, H, 5, True, 3), N, device="cuda:0", pack_gru=PACK)
+    actor = BatchedActor(random_actor(1, D + N, H, 5, True, 3), N, device="cuda:0", pack_gru=PACK)
     obs = torch.rand(E, N, D, device="cuda:0")
     hidden = torch.zeros(E, N, H, device="cuda:0")
     waves = (E * N // 32) * (H // 32)

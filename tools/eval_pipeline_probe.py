@@ -15,7 +15,7 @@ import torch  # noqa: E402
 
 from marbler_amd import VecRobotariumEnv  # noqa: E402
 from marbler_amd.evaluate import BatchedActor  # noqa: E402
-from test_gpu_actor import _random_actor  # noqa: E402
+from gpu_helpers import random_actor  # noqa: E402
 
 OV = {"predator": 2, "capture": 2, "n_agents": 4}
 
@@ -30,7 +30,7 @@ def run(E, parts, H, steps, warm=50):
             env = VecRobotariumEnv("PredatorCapturePrey", Ep, overrides=OV, seed=0, env_offset=p * Ep)
             env.set_stream(st)
             env.reset()
-            actor = BatchedActor(_random_actor(1, env.D + env.N, H, 5, True, 3), env.N, device=dev)
+            actor = BatchedActor(random_actor(1, env.D + env.N, H, 5, True, 3), env.N, device=dev)
             halves.append({"env": env, "actor": actor, "st": st, "hidden": actor.init_hidden(Ep),
                            "q": torch.empty(Ep, env.N, 5, device=dev), "act": torch.zeros(Ep, env.N, dtype=torch.int32, device=dev)})
     for h in halves:

@@ -7,12 +7,12 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 from marbler_amd import VecRobotariumEnv
 from marbler_amd.evaluate import BatchedActor, run_eval
-from test_gpu_actor import _random_actor
+from gpu_helpers import random_actor
 for H in (128, 64):
     for pack in ("bf16x3", "f16x2"):
         for use_graph in (False, True):
             env = VecRobotariumEnv("PredatorCapturePrey", 4096, seed=5)
-            actor = BatchedActor(_random_actor(1, 20, H, 5, True, 3), env.N, device=env.device, pack_gru=pack)
+            actor = BatchedActor(random_actor(1, 20, H, 5, True, 3), env.N, device=env.device, pack_gru=pack)
             run_eval(env, actor, steps=20, use_graph=use_graph, fused=True)
             torch.cuda.synchronize()
             t0 = time.perf_counter()

@@ -25,11 +25,11 @@ def main():
     args = ap.parse_args()
     from marbler_amd.evaluate import BatchedActor
     from marbler_amd.gymma import BatchedRunner, GymmaVecEnv
-    from test_gpu_actor import _random_actor
+    from gpu_helpers import random_actor
     for H in (128, 64):
         v = GymmaVecEnv("robotarium_gym:PredatorCapturePrey-v0", args.envs, time_limit=100, seed=1,
                         overrides={"n_agents": 4, "predator": 2, "capture": 2})
-        actor = BatchedActor(_random_actor(1, v.obs_size + v.n_agents, H, v.n_actions, True, seed=2), v.n_agents, device=v.env.device)
+        actor = BatchedActor(random_actor(1, v.obs_size + v.n_agents, H, v.n_actions, True, seed=2), v.n_agents, device=v.env.device)
         runner = BatchedRunner(v, actor, epsilon=args.epsilon, seed=3)
         times = {False: [], True: []}
         for one in (False, True, False, True):   # warm-up

@@ -9,7 +9,7 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 from marbler_amd.evaluate import BatchedActor
 from marbler_amd.gymma import GymmaVecEnv
-from test_gpu_actor import _random_actor
+from gpu_helpers import random_actor
 E = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 300
 H = int(sys.argv[3]) if len(sys.argv) > 3 else 128
@@ -20,7 +20,7 @@ class Half:
     def __init__(self, n, seed, stream):
         self.v = GymmaVecEnv("robotarium_gym:PredatorCapturePrey-v0", n, time_limit=1000, seed=seed)
         v = self.v
-        self.actor = BatchedActor(_random_actor(1, v.obs_size + v.n_agents, H, v.n_actions, True, seed=2), v.n_agents, device=dev)
+        self.actor = BatchedActor(random_actor(1, v.obs_size + v.n_agents, H, v.n_actions, True, seed=2), v.n_agents, device=dev)
         self.stream = stream
         self.hidden = self.actor.init_hidden(n).to(dev)
         self.q = torch.empty(n, v.n_agents, v.n_actions, device=dev)

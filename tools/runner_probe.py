@@ -7,13 +7,13 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import torch
 from marbler_amd.evaluate import BatchedActor
 from marbler_amd.gymma import BatchedRunner, GymmaVecEnv
-from test_gpu_actor import _random_actor
+from gpu_helpers import random_actor
 E = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 200
 for eps in (0.0, 0.1):
     for H in (64, 128):
         v = GymmaVecEnv("robotarium_gym:PredatorCapturePrey-v0", E, time_limit=1000, seed=3)
-        actor = BatchedActor(_random_actor(1, v.obs_size + v.n_agents, H, v.n_actions, True, seed=2), v.n_agents, device=v.env.device)
+        actor = BatchedActor(random_actor(1, v.obs_size + v.n_agents, H, v.n_actions, True, seed=2), v.n_agents, device=v.env.device)
         runner = BatchedRunner(v, actor, epsilon=eps, seed=1)
         runner.run(20)
         torch.cuda.synchronize()
