@@ -31,7 +31,8 @@ extern "C" {
  * additive (no existing layout or entry point changed): + rg_set_lidar(), rg_lidar_params, rg_sizeof_lidar_params(); + rg_set_teams(),
  * rg_team_params, rg_sizeof_team_params(); + rg_actor_forward_sample(), rg_policy_rollout_sample(), rg_policy_sample,
  * rg_sizeof_policy_sample() (soft-policies action sampling); + rg_set_disturbance(), rg_disturbance_params,
- * rg_sizeof_disturbance_params() (per-step pose disturbance).
+ * rg_sizeof_disturbance_params() (per-step pose disturbance); + rg_render(), rg_render_params, rg_sizeof_render_params(),
+ * rg_render_last_error() (batched RGB frames of the envs' state).
  * 6 (round 5): rg_scenario_params ends in the barrier-QP solver selection (qp_mode + cvxopt's options): RG_QP_CVXOPT computes the
  * interior-point iterate the reference's stack computes (utilities/controller.py:13-16,23) instead of the exact projection;
  * rg_step_io.zero_obs_on_end; + rg_actor_forward_explore(), rg_actor_pack_gru_f16x2() and rg_actor_weights.gru_packed == 3.
@@ -375,6 +376,40 @@ int rg_sizeof_disturbance_params(void);
  * on, -73 a handle with a team pool, -100 a build without the disturbance kernels.  rg_set_lidar (-57) and rg_set_teams (-65)
  * refuse a disturbed handle. */
 int rg_set_disturbance(rg_handle *h, const rg_disturbance_params *dp);
+
+/* ---- rendering: RGB frames of the envs' state (opt-in; replaces scenarios/<S>/visualize.py as utilities/roboEnv.py:67-76 shows it) ----
+ * K frames of K envs in ONE launch: frame k is the picture of env env_index[k] (NULL: env k), height x width pixels of three
+ * bytes (R, G, B), row 0 at the top.  The picture -- what is drawn, in which order and colour, and the binary32 arithmetic that
+ * decides whether a shape covers a pixel's centre -- is stated once in csrc/render.h (DESIGN.md section 4 "Render"): the arena,
+ * the scenario's zones or terrain, prey / goal markers, PredatorCapturePrey's capability rings, the robots in their class colour and
+ * their headings.  The call is handle-free: it reads the state arrays of `state` that the scenario's picture needs (poses; prey_loc,
+ * prey_sensed, prey_captured for PredatorCapturePrey and Simple; grid for ArcticTransport), writes `rgb` and nothing else, never
+ * allocates or synchronises, and launches on `hip_stream` of the caller's CURRENT device.  A non-finite pose draws nothing; what
+ * lies outside the view is clipped; an env_index entry outside [0, E) gives a frame with the arena and the fixed zones only.
+ * Layout: 4 ints, one pointer, 4 floats = 40 bytes, no padding; checked against the binding with rg_sizeof_render_params(). */
+#define RG_RENDER_ARENA 1
+#define RG_RENDER_ZONES 2
+#define RG_RENDER_MARKERS 4
+#define RG_RENDER_RINGS 8
+#define RG_RENDER_ROBOTS 16
+#define RG_RENDER_HEADING 32
+typedef struct rg_render_params {
+    int32_t width, height;        /* pixels; width a multiple of 4 in 8..1024, height in 8..1024 */
+    int32_t n_frames;             /* K >= 1 */
+    int32_t layers;               /* bit mask RG_RENDER_ARENA | _ZONES | _MARKERS | _RINGS | _ROBOTS | _HEADING; 0 = all */
+    const int32_t *env_index;     /* [K] device pointer, each in [0, E); NULL = envs 0 .. K-1 (then K <= E) */
+    float view_x0, view_y0, view_w, view_h;  /* world rectangle the image shows (corner within 1000 m of the origin, sizes at most 1000 m); view_w == 0: the arena (bound_x0, bound_y0, bound_w, bound_h) */
+} rg_render_params;
+int rg_sizeof_render_params(void);
+/* Every argument is checked before the first HIP call.  Errors (text via rg_render_last_error(), which names the field): -1 params,
+ * -2 state, -3 rp, -4 rgb NULL; -5 rgb not 4-byte aligned; -80 scenario, -81 n_agents, -82 num_prey, -83 the arena, -84 robot_diameter
+ * of params outside their domain; -85 num_envs < 1; -86 width outside 8..1024, -87 width not a multiple of 4, -88 height outside
+ * 8..1024, -89 n_frames < 1, -90 more work-groups than a launch takes, -91 unknown layer bits, -92 env_index NULL with
+ * n_frames > num_envs, -93 view_x0 / view_y0 not finite or beyond 1000 m, -94 view_w, -95 view_h not finite, negative or above 1000 m, -96 view_w > 0 with
+ * view_h == 0; -97 state.poses, -98 a prey array, -99 state.grid NULL where the scenario's picture needs it; -30 the launch failed. */
+int rg_render(const rg_scenario_params *params, const rg_state *state, int32_t num_envs, const rg_render_params *rp,
+              uint8_t *rgb /* [K][height][width][3] */, void *hip_stream);
+const char *rg_render_last_error(void);
 
 /* ---- policy inference for evaluation rollouts ------------------------
  * The EPyMARL recurrent actor the reference evaluates with (utilities/rnn_agent.py:5-29 `RNNAgent`:

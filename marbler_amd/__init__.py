@@ -5,10 +5,11 @@ kernels behind the reference's reset()/step() surface.  See DESIGN.md and INTEGR
 There is no CPU fallback: the HIP library must be built (python -m marbler_amd.build) and a
 GPU must be visible, or construction raises.
 """
+from . import render  # noqa: F401
 from ._lib import RobogymError  # noqa: F401
 from .params import load_config, make_params  # noqa: F401
 from .vec_env import VecRobotariumEnv  # noqa: F401
 from .wrapper import Wrapper, env_dict, register_gym_ids  # noqa: F401
 
 __all__ = ["VecRobotariumEnv", "Wrapper", "env_dict", "register_gym_ids", "load_config", "make_params",
-           "RobogymError"]
+           "RobogymError", "render"]

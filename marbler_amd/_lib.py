@@ -114,6 +114,16 @@ class RgDisturbanceParams(C.Structure):
     _fields_ = [("sigma_xy", C.c_float), ("sigma_theta", C.c_float), ("reserved", C.c_float * 2)]
 
 
+# rg_render: the layer bits of rg_render_params.layers (include/robogym.h RG_RENDER_*), in draw order
+RENDER_ARENA, RENDER_ZONES, RENDER_MARKERS, RENDER_RINGS, RENDER_ROBOTS, RENDER_HEADING = 1, 2, 4, 8, 16, 32
+
+
+class RgRenderParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_frames", C.c_int32), ("layers", C.c_int32),
+                ("env_index", C.c_void_p), ("view_x0", C.c_float), ("view_y0", C.c_float), ("view_w", C.c_float),
+                ("view_h", C.c_float)]
+
+
 # rg_step_form: which form the last rg_step launch took (include/robogym.h RG_FORM_*)
 FORM_NONE, FORM_BY_VALUE, FORM_RESIDENT, FORM_SHAPE = 0, 1, 2, 16
 
@@ -136,10 +146,11 @@ EXPORTS = ("rg_abi_version", "rg_last_error", "rg_sizeof_params", "rg_sizeof_sta
            "rg_sizeof_policy_io", "rg_policy_rollout", "rg_sizeof_lidar_params", "rg_set_lidar",
            "rg_sizeof_team_params", "rg_set_teams",
            "rg_actor_forward_sample", "rg_sizeof_policy_sample", "rg_policy_rollout_sample",
-           "rg_sizeof_disturbance_params", "rg_set_disturbance", "rg_step_form", "rg_shape_match", "rg_shape_info")
+           "rg_sizeof_disturbance_params", "rg_set_disturbance", "rg_step_form", "rg_shape_match", "rg_shape_info",
+           "rg_sizeof_render_params", "rg_render", "rg_render_last_error")
 # the queries a library of an earlier build lacks: tolerated in one loaded through ROBOGYM_LIB (an A/B run against it), never in
 # the package's own
-LATE_QUERIES = ("rg_step_form", "rg_shape_match", "rg_shape_info")
+LATE_QUERIES = ("rg_step_form", "rg_shape_match", "rg_shape_info", "rg_sizeof_render_params", "rg_render", "rg_render_last_error")
 
 _lib = None
 
@@ -218,6 +229,12 @@ def load():
     lib.rg_set_disturbance.argtypes = [C.c_void_p, C.POINTER(RgDisturbanceParams)]
     lib.rg_set_disturbance.restype = C.c_int
     lib.rg_sizeof_disturbance_params.restype = C.c_int
+    if hasattr(lib, "rg_render"):   # (LATE_QUERIES)
+        lib.rg_render.argtypes = [C.POINTER(RgScenarioParams), C.POINTER(RgState), C.c_int32, C.POINTER(RgRenderParams), C.c_void_p,
+                                  C.c_void_p]
+        lib.rg_render.restype = C.c_int
+        lib.rg_render_last_error.restype = C.c_char_p
+        lib.rg_sizeof_render_params.restype = C.c_int
     for f in (lib.rg_destroy, lib.rg_bind_state, lib.rg_set_stream, lib.rg_reset, lib.rg_step, lib.rg_rollout, lib.rg_get_obs,
               lib.rg_sizeof_params, lib.rg_sizeof_state, lib.rg_sizeof_step_io):
         f.restype = C.c_int
@@ -227,7 +244,8 @@ def load():
             or lib.rg_sizeof_step_io() != C.sizeof(RgStepIO) or lib.rg_sizeof_policy_io() != C.sizeof(RgPolicyIO)
             or lib.rg_sizeof_policy_sample() != C.sizeof(RgPolicySample)
             or lib.rg_sizeof_lidar_params() != C.sizeof(RgLidarParams) or lib.rg_sizeof_team_params() != C.sizeof(RgTeamParams)
-            or lib.rg_sizeof_disturbance_params() != C.sizeof(RgDisturbanceParams)):
+            or lib.rg_sizeof_disturbance_params() != C.sizeof(RgDisturbanceParams)
+            or (hasattr(lib, "rg_render") and lib.rg_sizeof_render_params() != C.sizeof(RgRenderParams))):
         raise RobogymError("struct layout of the binding differs from the compiled library; rebuild")
     _lib = lib
     return lib

@@ -139,8 +139,11 @@ class GymmaVecEnv(object):
         s, n, t = self.env.episode_stats()
         return {"return_sum": float(s), "episodes": int(n), "steps": int(t)}
 
-    def render(self):
-        pass
+    def render(self, mode=None, **kw):
+        """mode 'rgb_array': VecRobotariumEnv.render(**kw), a uint8 tensor [K, H, W, 3]; None (the default): None."""
+        if mode != "rgb_array":
+            return None
+        return self.env.render(**kw)
 
     def close(self):
         self.env.close()
@@ -213,8 +216,11 @@ class GymmaEnv(object):
     def get_env_info(self):
         return self._v.get_env_info()
 
-    def render(self):
-        pass
+    def render(self, mode=None, **kw):
+        """mode 'rgb_array': the env's frame, NumPy uint8 [H, W, 3]; None (the default): None."""
+        if mode != "rgb_array":
+            return None
+        return self._v.env.render(envs=0, **kw)[0].cpu().numpy()
 
     def close(self):
         self._v.close()

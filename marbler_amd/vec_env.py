@@ -151,6 +151,7 @@ class VecRobotariumEnv(object):
             self.next_init.data_ptr() if self.next_init is not None else None,
             self.next_episode.data_ptr() if self.next_episode is not None else None)
         _lib.check(self.lib.rg_bind_state(self._h, C.byref(st)), "rg_bind_state")
+        self._state = st   # (render() reads the same arrays through the handle-free rg_render)
         if self.lidar is not None:
             rc = self.lib.rg_set_lidar(self._h, C.byref(self.lidar))
             if rc != 0:
@@ -449,6 +450,22 @@ class VecRobotariumEnv(object):
         out = self.obs if out is None else out
         _lib.check(self.lib.rg_get_obs(self._h, out.data_ptr()), "rg_get_obs")
         return out
+
+    def render(self, envs=None, size=84, out=None, layers=None, view=None):
+        """RGB frames of the envs' current state, rasterised on the device in one launch (rg_render; the picture is stated in
+        csrc/render.h and DESIGN.md section 4 "Render"): uint8 [K, H, W, 3] on the env's device, row 0 at the top.  Runs on
+        torch's current stream of that device.  Reads state only: works with the lidar, a team pool or the pose disturbance
+        on, and never changes what a later step computes.
+        envs: None (all E envs), an int, a sequence or an int tensor of env indices, in the order of the frames; host data
+            outside [0, E) raises IndexError.
+        size: an int (square) or (H, W), each in 8..1024, W a multiple of 4.
+        out: a contiguous uint8 tensor [K, H, W, 3] on the env's device to render into (a slice of a caller's batch); returned.
+        layers: names from marbler_amd.render.LAYERS ('arena', 'zones', 'markers', 'rings', 'robots', 'heading'); None = all.
+            With a team pool 'rings' is dropped unless named: the rings show the config's sensing / capture radii, NOT those
+            of the capability set an env drew for its episode.
+        view: (x0, y0, w, h), the world rectangle the image shows; None = the arena."""
+        from .render import render_frames
+        return render_frames(self, envs=envs, size=size, out=out, layers=layers, view=view)
 
     # ------------------------------------------------------------------ state access (parity / checkpoints)
     # everything a later step depends on: the scenario state, the RNG stream position (reset_count) and the

@@ -101,8 +101,12 @@ class _ScenarioFacade(object):
         return [obs[i] for i in range(self.num_robots)], [float(r) for r in h_rew], \
             [terminated] * self.num_robots, out
 
-    def render(self, mode='human'):
-        pass
+    def render(self, mode='human', **kw):
+        """mode 'rgb_array': the env's frame, NumPy uint8 [H, W, 3] (VecRobotariumEnv.render's size / layers / view as keywords);
+        'human' (the default): nothing is shown, None."""
+        if mode != "rgb_array":
+            return None
+        return self.vec.render(envs=0, **kw)[0].cpu().numpy()
 
 
 env_dict = {name: name for name in SCENARIOS}  # wrapper.py:12-16
@@ -136,8 +140,8 @@ class Wrapper(_EnvBase):
     def get_observation_space(self):
         return self.env.get_observation_space()
 
-    def render(self, mode='human'):
-        pass
+    def render(self, mode='human', **kw):
+        return self.env.render(mode, **kw)
 
     def close(self):
         self.env.vec.close()
