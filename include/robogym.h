@@ -32,7 +32,8 @@ extern "C" {
  * rg_team_params, rg_sizeof_team_params(); + rg_actor_forward_sample(), rg_policy_rollout_sample(), rg_policy_sample,
  * rg_sizeof_policy_sample() (soft-policies action sampling); + rg_set_disturbance(), rg_disturbance_params,
  * rg_sizeof_disturbance_params() (per-step pose disturbance); + rg_render(), rg_render_params, rg_sizeof_render_params(),
- * rg_render_last_error() (batched RGB frames of the envs' state).
+ * rg_render_last_error() (batched RGB frames of the envs' state); + rg_episodes_append(), rg_episode_buffer, rg_episode_stream,
+ * rg_sizeof_episode_buffer(), rg_sizeof_episode_stream(), rg_episodes_last_error() (a collector's stream as padded episodes).
  * 6 (round 5): rg_scenario_params ends in the barrier-QP solver selection (qp_mode + cvxopt's options): RG_QP_CVXOPT computes the
  * interior-point iterate the reference's stack computes (utilities/controller.py:13-16,23) instead of the exact projection;
  * rg_step_io.zero_obs_on_end; + rg_actor_forward_explore(), rg_actor_pack_gru_f16x2() and rg_actor_weights.gru_packed == 3.
@@ -410,6 +411,62 @@ int rg_sizeof_render_params(void);
 int rg_render(const rg_scenario_params *params, const rg_state *state, int32_t num_envs, const rg_render_params *rp,
               uint8_t *rgb /* [K][height][width][3] */, void *hip_stream);
 const char *rg_render_last_error(void);
+
+/* ---- episode buffer: a collector's time-major stream as episode-major slots padded to episode_limit + 1 (opt-in) ----
+ * The layout EPyMARL's learners read (components/episode_buffer.py EpisodeBatch / ReplayBuffer, external to the reference), filled
+ * on the device in ONE launch per collection.  The rule is stated once in csrc/episodes.h (DESIGN.md section 4 "Episode buffer"):
+ *   buffer  E envs x R slots (slot s = e R + r), episode limit L, N agents, row width D:
+ *           obs [E R][L+1][N][D] f32, actions [E R][L+1][N] i32, reward [E R][L+1] f32, terminated / filled [E R][L+1] u8,
+ *           optional prob [E R][L+1][N] f32; per slot length i32, episode_return f32, complete u8, fresh u8, episode_index i32;
+ *           per env cursor [E][4] i32 = the open slot or -1, the position in it, episodes opened, overflow counter.
+ *   stream  obs [T+1][E][N][D], actions [T][E][N], reward [T][E], terminated [T][E] u8, episode_start [T][E] u8, optional
+ *           prob [T][E][N]: what BatchedRunner.run(T) returns.
+ *   per env, for t = 0 .. T-1 in order: (1) episode_start[t,e] abandons an episode that is still open (not complete; the new
+ *   one takes its slot and index) and opens a new one in slot e R + (opened mod R) at position 0, zeroing the slot's filled,
+ *   terminated and reward rows and its length, episode_return, complete and fresh; (2) without an open episode the transition
+ *   is dropped; (3) otherwise row p takes obs, actions, reward, terminated and prob of (t, e), filled[p] = 1 and
+ *   episode_return += reward[t,e] (binary32, step order); (4) terminated[t,e]: row p+1 takes obs[t+1,e], filled[p+1] = 1,
+ *   length = p+1, complete = fresh = 1, the episode closes; (5) p+1 == L without termination: force-closed as in (4) and the
+ *   overflow counter goes up.  Nothing is written outside a slot.  An env that opens more than R episodes in one call
+ *   overwrites its own older slots exactly as the sequential rule does.
+ * Handle-free; reads the stream, writes the buffer and nothing else; never allocates, copies or synchronises (safe under stream
+ * capture); launches on `hip_stream` of the caller's CURRENT device.  Rows are copied with 16-byte accesses where N D and the
+ * obs bases allow it, with 8- or 4-byte ones where not: no width is refused.
+ * Layouts: 12 pointers + 6 ints = 120 bytes; 6 pointers + 2 ints = 56 bytes; checked with rg_sizeof_episode_buffer / _stream(). */
+typedef struct rg_episode_buffer {
+    float *obs;
+    int32_t *actions;
+    float *reward;
+    uint8_t *terminated, *filled;
+    float *prob;                  /* NULL: the buffer keeps no prob (then the stream's must be NULL too) */
+    int32_t *length;
+    float *episode_return;
+    uint8_t *complete, *fresh;
+    int32_t *episode_index;
+    int32_t *cursor;              /* [E][4] */
+    int32_t num_envs, slots_per_env, episode_limit, n_agents, obs_dim;   /* E, R, L, N, D: each >= 1 */
+    int32_t reserved;             /* 0 */
+} rg_episode_buffer;
+typedef struct rg_episode_stream {
+    const float *obs;
+    const int32_t *actions;
+    const float *reward;
+    const uint8_t *terminated, *episode_start;
+    const float *prob;            /* NULL exactly when the buffer's is */
+    int32_t T;                    /* >= 1 */
+    int32_t reserved;             /* 0 */
+} rg_episode_stream;
+int rg_sizeof_episode_buffer(void);
+int rg_sizeof_episode_stream(void);
+/* Every argument is checked before the first HIP call.  Errors (text via rg_episodes_last_error(), which names the field):
+ * -1 buffer, -2 stream NULL; -110 num_envs, -111 slots_per_env, -112 episode_limit, -113 n_agents, -114 obs_dim, -115 T below 1;
+ * -116 the buffer's, -117 the stream's largest array has more than 2^31 - 1 elements; -120 - i: pointer field i is NULL, and
+ * -150 - i: it is not aligned to its element (4 bytes for f32 / i32), with i counting buffer.obs, actions, reward, terminated,
+ * filled, length, episode_return, complete, fresh, episode_index, cursor (0..10), stream.obs, actions, reward, terminated,
+ * episode_start (11..15), buffer.prob (16), stream.prob (17); -136 prob in the buffer but not in the stream, -137 in the stream
+ * but not in the buffer; -30 the launch failed. */
+int rg_episodes_append(const rg_episode_buffer *buffer, const rg_episode_stream *stream, void *hip_stream);
+const char *rg_episodes_last_error(void);
 
 /* ---- policy inference for evaluation rollouts ------------------------
  * The EPyMARL recurrent actor the reference evaluates with (utilities/rnn_agent.py:5-29 `RNNAgent`:

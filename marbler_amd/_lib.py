@@ -124,6 +124,20 @@ class RgRenderParams(C.Structure):
                 ("view_h", C.c_float)]
 
 
+# rg_episodes_append: the buffer's arrays and the collector's stream (include/robogym.h; the rule: csrc/episodes.h)
+class RgEpisodeBuffer(C.Structure):
+    _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("reward", C.c_void_p), ("terminated", C.c_void_p),
+                ("filled", C.c_void_p), ("prob", C.c_void_p), ("length", C.c_void_p), ("episode_return", C.c_void_p),
+                ("complete", C.c_void_p), ("fresh", C.c_void_p), ("episode_index", C.c_void_p), ("cursor", C.c_void_p),
+                ("num_envs", C.c_int32), ("slots_per_env", C.c_int32), ("episode_limit", C.c_int32), ("n_agents", C.c_int32),
+                ("obs_dim", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RgEpisodeStream(C.Structure):
+    _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("reward", C.c_void_p), ("terminated", C.c_void_p),
+                ("episode_start", C.c_void_p), ("prob", C.c_void_p), ("T", C.c_int32), ("reserved", C.c_int32)]
+
+
 # rg_step_form: which form the last rg_step launch took (include/robogym.h RG_FORM_*)
 FORM_NONE, FORM_BY_VALUE, FORM_RESIDENT, FORM_SHAPE = 0, 1, 2, 16
 
@@ -147,10 +161,12 @@ EXPORTS = ("rg_abi_version", "rg_last_error", "rg_sizeof_params", "rg_sizeof_sta
            "rg_sizeof_team_params", "rg_set_teams",
            "rg_actor_forward_sample", "rg_sizeof_policy_sample", "rg_policy_rollout_sample",
            "rg_sizeof_disturbance_params", "rg_set_disturbance", "rg_step_form", "rg_shape_match", "rg_shape_info",
-           "rg_sizeof_render_params", "rg_render", "rg_render_last_error")
+           "rg_sizeof_render_params", "rg_render", "rg_render_last_error",
+           "rg_sizeof_episode_buffer", "rg_sizeof_episode_stream", "rg_episodes_append", "rg_episodes_last_error")
 # the queries a library of an earlier build lacks: tolerated in one loaded through ROBOGYM_LIB (an A/B run against it), never in
 # the package's own
-LATE_QUERIES = ("rg_step_form", "rg_shape_match", "rg_shape_info", "rg_sizeof_render_params", "rg_render", "rg_render_last_error")
+LATE_QUERIES = ("rg_step_form", "rg_shape_match", "rg_shape_info", "rg_sizeof_render_params", "rg_render", "rg_render_last_error",
+                "rg_sizeof_episode_buffer", "rg_sizeof_episode_stream", "rg_episodes_append", "rg_episodes_last_error")
 
 _lib = None
 
@@ -235,6 +251,12 @@ def load():
         lib.rg_render.restype = C.c_int
         lib.rg_render_last_error.restype = C.c_char_p
         lib.rg_sizeof_render_params.restype = C.c_int
+    if hasattr(lib, "rg_episodes_append"):   # (LATE_QUERIES)
+        lib.rg_episodes_append.argtypes = [C.POINTER(RgEpisodeBuffer), C.POINTER(RgEpisodeStream), C.c_void_p]
+        lib.rg_episodes_append.restype = C.c_int
+        lib.rg_episodes_last_error.restype = C.c_char_p
+        lib.rg_sizeof_episode_buffer.restype = C.c_int
+        lib.rg_sizeof_episode_stream.restype = C.c_int
     for f in (lib.rg_destroy, lib.rg_bind_state, lib.rg_set_stream, lib.rg_reset, lib.rg_step, lib.rg_rollout, lib.rg_get_obs,
               lib.rg_sizeof_params, lib.rg_sizeof_state, lib.rg_sizeof_step_io):
         f.restype = C.c_int
@@ -245,7 +267,9 @@ def load():
             or lib.rg_sizeof_policy_sample() != C.sizeof(RgPolicySample)
             or lib.rg_sizeof_lidar_params() != C.sizeof(RgLidarParams) or lib.rg_sizeof_team_params() != C.sizeof(RgTeamParams)
             or lib.rg_sizeof_disturbance_params() != C.sizeof(RgDisturbanceParams)
-            or (hasattr(lib, "rg_render") and lib.rg_sizeof_render_params() != C.sizeof(RgRenderParams))):
+            or (hasattr(lib, "rg_render") and lib.rg_sizeof_render_params() != C.sizeof(RgRenderParams))
+            or (hasattr(lib, "rg_episodes_append") and (lib.rg_sizeof_episode_buffer() != C.sizeof(RgEpisodeBuffer)
+                                                        or lib.rg_sizeof_episode_stream() != C.sizeof(RgEpisodeStream)))):
         raise RobogymError("struct layout of the binding differs from the compiled library; rebuild")
     _lib = lib
     return lib

@@ -20,7 +20,7 @@ SOURCES = ["robogym_kernels.hip", "robogym_resident.hip", "robogym_resident_shap
            "robogym_policy_h128.hip", "robogym_policy_sample_h64.hip", "robogym_policy_sample_h128.hip", "robogym_lidar.hip", "robogym_lidar_rollout.hip", "robogym_lidar_ipm.hip",
            "robogym_lidar_rollout_ipm.hip", "robogym_team.hip", "robogym_team_rollout.hip", "robogym_team_ipm.hip",
            "robogym_team_rollout_ipm.hip", "robogym_disturb.hip", "robogym_disturb_rollout.hip", "robogym_disturb_ipm.hip",
-           "robogym_disturb_rollout_ipm.hip", "robogym_render.hip"]
+           "robogym_disturb_rollout_ipm.hip", "robogym_render.hip", "robogym_episodes.hip"]
 # every header of csrc/ (a forgotten one would mean a stale library), and the C ABI's
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(CSRC, "probes", "*.h"))) + \
           [os.path.join(HERE, "..", "include", "robogym.h")]
@@ -156,7 +156,8 @@ def build(force=False, verbose=False, defines=(), out=None):
 def build_host_sanitized(out=None):
     """CPU sanitizer tier: the C ABI's host half (csrc/robogym_capi.hip) compiled for the HOST ONLY with
     ASan + UBSan, linked against tests/sanitize/launch_stubs.cpp in place of the device translation units; with it the host half
-    of csrc/robogym_render.hip (rg_render's argument checks: handle-free, it needs no stub).
+    of csrc/robogym_render.hip (rg_render's argument checks: handle-free, it needs no stub) and of csrc/robogym_episodes.hip
+    (rg_episodes_append's, likewise).
     Used by tests/test_sanitizers.py for the no-GPU cases of tests/test_host.py; never shipped.  (GPU ASan is
     not available on this pool: sanitizers run on the CPU build only.)"""
     out = out or os.path.join(HERE, "build", "librobogym_capi_asan.so")
@@ -165,7 +166,8 @@ def build_host_sanitized(out=None):
     stubs_sample = os.path.join(HERE, "..", "tests", "sanitize", "launch_stubs_sample.cpp")   # rg_actor_forward_sample
     cmd = [hipcc_path(), "-x", "hip", "--offload-host-only", "-O1", "-g", "-fno-omit-frame-pointer",
            "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fPIC", "-shared", "-std=c++17", "-DRG_RENDER_HOST_ONLY",
-           "-I", CSRC, os.path.join(CSRC, "robogym_capi.hip"), os.path.join(CSRC, "robogym_render.hip"), stubs, stubs_sample,
+           "-DRG_EPISODES_HOST_ONLY", "-I", CSRC, os.path.join(CSRC, "robogym_capi.hip"), os.path.join(CSRC, "robogym_render.hip"),
+           os.path.join(CSRC, "robogym_episodes.hip"), stubs, stubs_sample,
            "-o", out]
     subprocess.check_call(cmd)
     return out

@@ -1,0 +1,254 @@
+"""Episode buffer: BatchedRunner.run(T)'s time-major stream as episode-major batches padded to episode_limit + 1, the layout of
+EPyMARL's EpisodeBatch / ReplayBuffer, kept on the device and filled by one HIP launch per collection (rg_episodes_append,
+include/robogym.h).
+
+    buf = EpisodeBuffer.for_runner(runner)          # E x 2 slots of episode_limit + 1 rows, allocated once
+    runner.run(64, one_launch=True, into=buf)       # collect, then ONE launch cuts the stream into the slots
+    new = buf.take_new()                            # the slots completed since the last call
+    batch = buf.batch(new)                          # obs [B, L + 1, N, D], actions, reward, terminated, filled, ...
+
+The rule -- where an episode opens, which row takes what, what happens to an episode that is cut off or does not fit -- is
+stated once in csrc/episodes.h and DESIGN.md section 4 "Episode buffer".  There is no host path: append() needs the library and a
+HIP device.
+"""
+import ctypes as C
+
+from . import _lib
+
+# name -> (dtype name, shape as a function of (E, R, L, N, D)); `prob` only with with_prob
+ARRAYS = {"obs": ("float32", lambda E, R, L, N, D: (E * R, L + 1, N, D)),
+          "actions": ("int32", lambda E, R, L, N, D: (E * R, L + 1, N)),
+          "reward": ("float32", lambda E, R, L, N, D: (E * R, L + 1)),
+          "terminated": ("uint8", lambda E, R, L, N, D: (E * R, L + 1)),
+          "filled": ("uint8", lambda E, R, L, N, D: (E * R, L + 1)),
+          "prob": ("float32", lambda E, R, L, N, D: (E * R, L + 1, N)),
+          "length": ("int32", lambda E, R, L, N, D: (E * R,)),
+          "episode_return": ("float32", lambda E, R, L, N, D: (E * R,)),
+          "complete": ("uint8", lambda E, R, L, N, D: (E * R,)),
+          "fresh": ("uint8", lambda E, R, L, N, D: (E * R,)),
+          "episode_index": ("int32", lambda E, R, L, N, D: (E * R,)),
+          "cursor": ("int32", lambda E, R, L, N, D: (E, 4))}
+INT32_MAX = 2 ** 31 - 1
+
+
+def _check_tensor(name, t, dtypes, shape, device=None):
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch tensor, got {type(t).__name__}")
+    if t.dtype not in dtypes:
+        raise ValueError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have the shape {tuple(shape)}, got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if device is not None and t.device != device:
+        raise ValueError(f"{name} is on {t.device}, the buffer on {device}")
+    return t
+
+
+class EpisodeBuffer(object):
+    """E x slots_per_env episode slots of episode_limit + 1 rows on `device`; all storage is allocated here, zero-filled, and
+    nothing is allocated afterwards by append().  Slot e * slots_per_env + r is env e's r-th ring entry: an env's episodes go
+    round its own ring, so with slots_per_env = 2 the episode an env has just completed stays readable while its next one fills.
+    storage: the arrays themselves (name -> tensor, ARRAYS' dtypes and shapes, contiguous), for a caller that owns the memory."""
+
+    def __init__(self, num_envs, n_agents, obs_dim, n_actions, episode_limit, slots_per_env=2, with_prob=False, device="cuda:0",
+                 storage=None):
+        import torch
+        dims = {"num_envs": num_envs, "n_agents": n_agents, "obs_dim": obs_dim, "n_actions": n_actions,
+                "episode_limit": episode_limit, "slots_per_env": slots_per_env}
+        for k, v in dims.items():
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise TypeError(f"{k} must be an int, got {v!r}")
+            if v < 1:
+                raise ValueError(f"{k} must be >= 1, got {v}")
+        self.E, self.N, self.D, self.A = num_envs, n_agents, obs_dim, n_actions
+        self.L, self.R = episode_limit, slots_per_env
+        self.with_prob = bool(with_prob)
+        self.device = torch.device(device)
+        if self.E * self.R * (self.L + 1) * self.N * self.D > INT32_MAX:
+            raise ValueError("num_envs * slots_per_env * (episode_limit + 1) * n_agents * obs_dim exceeds 2^31 - 1 elements")
+        shape_args = (self.E, self.R, self.L, self.N, self.D)
+        self.names = tuple(k for k in ARRAYS if k != "prob" or self.with_prob)
+        if storage is None:
+            storage = {k: torch.zeros(ARRAYS[k][1](*shape_args), dtype=getattr(torch, ARRAYS[k][0]), device=self.device)
+                       for k in self.names}
+            storage["cursor"][:, 0] = -1           # no env has an open episode
+        elif set(storage) != set(self.names):
+            raise ValueError(f"storage must hold exactly {self.names}, got {tuple(storage)}")
+        for k in self.names:
+            _check_tensor(f"storage[{k!r}]", storage[k], (getattr(torch, ARRAYS[k][0]),), ARRAYS[k][1](*shape_args), self.device)
+            setattr(self, k, storage[k])
+        if not self.with_prob:
+            self.prob = None
+        self._c_buffer = _lib.RgEpisodeBuffer(
+            self.obs.data_ptr(), self.actions.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(), self.filled.data_ptr(),
+            self.prob.data_ptr() if self.with_prob else None, self.length.data_ptr(), self.episode_return.data_ptr(),
+            self.complete.data_ptr(), self.fresh.data_ptr(), self.episode_index.data_ptr(), self.cursor.data_ptr(),
+            self.E, self.R, self.L, self.N, self.D, 0)
+
+    @classmethod
+    def for_runner(cls, runner, slots_per_env=2):
+        """A buffer that fits `runner` (a BatchedRunner): its venv's shapes and episode limit, `prob` if it samples soft policies."""
+        v = runner.venv
+        soft = runner.action_selector == "soft_policies" and not runner.test_mode
+        return cls(v.E, v.n_agents, v.obs_size, v.n_actions, v.episode_limit, slots_per_env=slots_per_env, with_prob=soft,
+                   device=v.env.device)
+
+    @property
+    def num_slots(self):
+        return self.E * self.R
+
+    # -- filling
+    def check_fits(self, num_envs, n_agents, obs_dim, episode_limit, with_prob):
+        """ValueError unless a collector of these shapes can append to this buffer (BatchedRunner.run(into=) asks before it
+        collects): the same E, N, D, an episode limit the slots can hold, the same `prob` setting."""
+        for name, have, want in (("num_envs", self.E, num_envs), ("n_agents", self.N, n_agents), ("obs_dim", self.D, obs_dim)):
+            if have != want:
+                raise ValueError(f"the buffer was built for {name} = {have}, the collector has {want}")
+        if self.L < episode_limit:
+            raise ValueError(f"the buffer's episode_limit {self.L} is below the collector's {episode_limit}: its episodes would overflow")
+        if self.with_prob != bool(with_prob):
+            raise ValueError("the buffer was built with_prob=%s, the collector %s `prob`" %
+                             (self.with_prob, "returns" if with_prob else "does not return"))
+
+    def check_stream(self, batch):
+        """batch: run()'s dict.  Checks names, dtypes, shapes, contiguity and devices; returns T.  Touches no device."""
+        import torch
+        if not isinstance(batch, dict):
+            raise TypeError("batch must be the dict BatchedRunner.run returns")
+        need = ("obs", "actions", "reward", "terminated", "episode_start")
+        missing = [k for k in need if k not in batch]
+        if missing:
+            raise ValueError(f"batch lacks {missing}")
+        if self.with_prob and batch.get("prob") is None:
+            raise ValueError("the buffer was built with_prob=True, the batch has no 'prob'")
+        if not self.with_prob and batch.get("prob") is not None:
+            raise ValueError("the batch has 'prob', the buffer was built with_prob=False")
+        if not isinstance(batch["actions"], torch.Tensor) or batch["actions"].dim() != 3 or batch["actions"].shape[0] < 1:
+            raise ValueError("batch['actions'] must be a tensor [T, E, N] with T >= 1")
+        T = int(batch["actions"].shape[0])
+        if (T + 1) * self.E * self.N * self.D > INT32_MAX:
+            raise ValueError("(T + 1) * num_envs * n_agents * obs_dim exceeds 2^31 - 1 elements")
+        flags = (torch.bool, torch.uint8)
+        _check_tensor("batch['obs']", batch["obs"], (torch.float32,), (T + 1, self.E, self.N, self.D), self.device)
+        _check_tensor("batch['actions']", batch["actions"], (torch.int32,), (T, self.E, self.N), self.device)
+        _check_tensor("batch['reward']", batch["reward"], (torch.float32,), (T, self.E), self.device)
+        _check_tensor("batch['terminated']", batch["terminated"], flags, (T, self.E), self.device)
+        _check_tensor("batch['episode_start']", batch["episode_start"], flags, (T, self.E), self.device)
+        if self.with_prob:
+            _check_tensor("batch['prob']", batch["prob"], (torch.float32,), (T, self.E, self.N), self.device)
+        return T
+
+    def append(self, batch, stream=None):
+        """Cut run()'s dict into the slots: one launch on `stream` (a torch stream; None: the current one), no host
+        synchronisation, nothing allocated -- safe inside a torch.cuda.graph capture.  Returns nothing."""
+        import torch
+        T = self.check_stream(batch)
+        if self.device.type != "cuda":
+            raise ValueError(f"the buffer lives on {self.device}: append() runs on a HIP device and has no host path")
+        lib = _lib.load()
+        s = _lib.RgEpisodeStream(batch["obs"].data_ptr(), batch["actions"].data_ptr(), batch["reward"].data_ptr(),
+                                 batch["terminated"].data_ptr(), batch["episode_start"].data_ptr(),
+                                 batch["prob"].data_ptr() if self.with_prob else None, T, 0)
+        with torch.cuda.device(self.device):
+            hip_stream = (torch.cuda.current_stream(self.device) if stream is None else stream).cuda_stream
+            rc = lib.rg_episodes_append(C.byref(self._c_buffer), C.byref(s), C.c_void_p(hip_stream))
+        if rc != 0:
+            raise _lib.RobogymError(f"rg_episodes_append failed ({rc}): {lib.rg_episodes_last_error().decode()}")
+
+    # -- reading
+    def take_new(self):
+        """The slots completed since the last call: int64, ascending.  Clears `fresh`."""
+        import torch
+        new = torch.nonzero(self.fresh).flatten()
+        self.fresh.zero_()
+        return new
+
+    def _slots(self, slots):
+        import torch
+        if slots is None:
+            return torch.nonzero(self.complete).flatten()
+        if isinstance(slots, torch.Tensor):
+            if slots.dtype not in (torch.int64, torch.int32):
+                raise ValueError(f"slots must be an int64 or int32 tensor, got {slots.dtype}")
+            if slots.dim() != 1:
+                raise ValueError(f"slots must be one-dimensional, got {tuple(slots.shape)}")
+            if slots.device.type == "cpu":
+                host = slots.tolist()
+            else:
+                return slots.to(device=self.device, dtype=torch.int64)    # device data: taken as it is (torch checks the index)
+        else:
+            try:
+                host = [int(v) for v in slots]
+            except TypeError:
+                raise ValueError(f"slots must be None, an int tensor or a sequence of ints, got {slots!r}") from None
+        bad = [v for v in host if not 0 <= v < self.num_slots]
+        if bad:
+            raise ValueError(f"slots {bad[:4]} outside [0, {self.num_slots})")
+        return torch.tensor(host, dtype=torch.int64).to(self.device)
+
+    def batch(self, slots=None, trim=False):
+        """EPyMARL's episode batch of `slots` (None: every complete slot, ascending), B episodes: obs [B, L + 1, N, D], state
+        [B, L + 1, N D] (gymma's state is the concatenated observations), actions [B, L + 1, N, 1] int64, avail_actions
+        [B, L + 1, N, A] int32 ones, reward [B, L + 1, 1], terminated [B, L + 1, 1] uint8, filled [B, L + 1, 1] int64, probs
+        [B, L + 1, N] (a buffer with_prob), length [B] int32, episode_return [B].  trim: the time axis is cut to the longest
+        episode selected, max(length) + 1 rows (one host read)."""
+        import torch
+        idx = self._slots(slots)
+        B = int(idx.numel())
+        rows = self.L + 1
+        length = self.length[idx]
+        if trim and B > 0:
+            rows = int(length.max()) + 1
+        obs = self.obs[idx, :rows]
+        out = {"obs": obs, "state": obs.reshape(B, rows, self.N * self.D),
+               "actions": self.actions[idx, :rows].to(torch.int64).unsqueeze(-1),
+               "avail_actions": torch.ones(B, rows, self.N, self.A, dtype=torch.int32, device=self.device),
+               "reward": self.reward[idx, :rows].unsqueeze(-1),
+               "terminated": self.terminated[idx, :rows].unsqueeze(-1),
+               "filled": self.filled[idx, :rows].to(torch.int64).unsqueeze(-1),
+               "length": length, "episode_return": self.episode_return[idx]}
+        if self.with_prob:
+            out["probs"] = self.prob[idx, :rows]
+        return out
+
+    def sample(self, n, generator=None):
+        """n slots drawn uniformly, without replacement, among the complete ones (int64); ValueError if fewer are complete."""
+        import torch
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"sample(n) draws n >= 1 slots, got {n!r}")
+        if n > self.num_slots:
+            raise ValueError(f"sample({n}): the buffer has {self.num_slots} slots")
+        done = torch.nonzero(self.complete).flatten()
+        if int(done.numel()) < n:
+            raise ValueError(f"sample({n}): only {int(done.numel())} slots hold a complete episode")
+        pick = torch.randperm(int(done.numel()), generator=generator, device=generator.device if generator is not None else "cpu")
+        return done[pick[:n].to(done.device)]
+
+    def overflowed(self):
+        """How many episodes were cut at the buffer's episode_limit (rule 5), over all envs: a device scalar (int64)."""
+        return self.cursor[:, 3].sum()
+
+    # -- checkpoints
+    def state_dict(self):
+        """Every array, cursors included (an open episode goes on after load_state_dict), as a plain dict of tensor copies."""
+        import torch
+        out = {k: getattr(self, k).clone() for k in self.names}
+        out["dims"] = torch.tensor([self.E, self.R, self.L, self.N, self.D, self.A], dtype=torch.int64)
+        return out
+
+    def load_state_dict(self, state):
+        import torch
+        want = torch.tensor([self.E, self.R, self.L, self.N, self.D, self.A], dtype=torch.int64)
+        if "dims" not in state or not torch.equal(state["dims"].cpu().to(torch.int64), want):
+            raise ValueError(f"the checkpoint's dims {state.get('dims')} differ from this buffer's {want.tolist()} (E, R, L, N, D, A)")
+        missing = [k for k in self.names if k not in state]
+        if missing or ("prob" in state) != self.with_prob:
+            raise ValueError(f"the checkpoint lacks {missing}" if missing else "the checkpoint and the buffer differ in with_prob")
+        for k in self.names:
+            mine = getattr(self, k)
+            if state[k].dtype != mine.dtype or tuple(state[k].shape) != tuple(mine.shape):
+                raise ValueError(f"checkpoint[{k!r}] is {state[k].dtype} {tuple(state[k].shape)}, the buffer's {mine.dtype} {tuple(mine.shape)}")
+        for k in self.names:
+            getattr(self, k).copy_(state[k])

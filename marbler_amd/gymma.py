@@ -272,7 +272,7 @@ class BatchedRunner(object):
         venv.reset()
 
     @torch.no_grad()
-    def run(self, T, one_launch=False):
+    def run(self, T, one_launch=False, into=None):
         """With the fused env step and the fused actor a time step is TWO launches, with exploration too: the actor reads the
         previous step's episode-end flags and observation straight from the batch and writes its (epsilon-)greedy actions into it; the env step reads
         those actions and writes the next observation (zeros for an env that ended: the reset observation), the summed reward
@@ -280,11 +280,16 @@ class BatchedRunner(object):
         same memory: gymma's state IS the concatenated observations); `episode_start` is filled once per call.
         one_launch: the whole collection in ONE launch (rg_policy_rollout: the actor and the env step alternate inside it, the
         hidden state resident on the CU) -- the same dict, hidden state and env state bit for bit.  Needs the fused env and an
-        actor packed as two binary16 planes; anything else raises ValueError instead of falling back."""
+        actor packed as two binary16 planes; anything else raises ValueError instead of falling back.
+        into: an episodes.EpisodeBuffer; the collected dict is appended to it (one more launch, on either path) before it is
+        returned.  A buffer that does not fit the venv (E, N, D, an episode limit below the venv's, the `prob` setting) raises
+        ValueError before anything is collected."""
         v, env, dev = self.venv, self.venv.env, self.venv.env.device
         E, N, D, A = v.E, v.n_agents, v.obs_size, v.n_actions
         if int(T) < 1:
             raise ValueError("run(T) collects T >= 1 time steps")
+        if into is not None:
+            into.check_fits(E, N, D, v.episode_limit, self.action_selector == "soft_policies" and not self.test_mode)
         if one_launch and getattr(env, "disturbance", None) is not None:
             raise ValueError("one_launch: an env with the pose disturbance (pose_noise_xy / pose_noise_theta) is not supported; "
                              "run(T) collects it on the two-launch path")
@@ -338,6 +343,8 @@ class BatchedRunner(object):
             # the wrapper's own view of "the current observation" and of which envs just restarted, for whoever steps next
             self._restart = term_u8[T - 1].clone()
             v._obs, v._ended = out["obs"][T].clone(), out["terminated"][T - 1].clone()
+            if into is not None:
+                into.append(out)
             return out
         out["state"] = torch.empty(T + 1, E, N * D, device=dev)
         for t in range(T):
@@ -368,4 +375,6 @@ class BatchedRunner(object):
             self._restart.copy_(ended)
         out["obs"][T] = v.get_obs()
         out["state"][T] = v.get_state()
+        if into is not None:
+            into.append(out)
         return out
