@@ -33,7 +33,9 @@ extern "C" {
  * rg_sizeof_policy_sample() (soft-policies action sampling); + rg_set_disturbance(), rg_disturbance_params,
  * rg_sizeof_disturbance_params() (per-step pose disturbance); + rg_render(), rg_render_params, rg_sizeof_render_params(),
  * rg_render_last_error() (batched RGB frames of the envs' state); + rg_episodes_append(), rg_episode_buffer, rg_episode_stream,
- * rg_sizeof_episode_buffer(), rg_sizeof_episode_stream(), rg_episodes_last_error() (a collector's stream as padded episodes).
+ * rg_sizeof_episode_buffer(), rg_sizeof_episode_stream(), rg_episodes_last_error() (a collector's stream as padded episodes);
+ * + rg_actor_unroll(), rg_actor_unroll_io, rg_sizeof_actor_unroll_io(), rg_actor_unroll_last_error() (the actor over every time
+ * step of an episode batch in one launch).
  * 6 (round 5): rg_scenario_params ends in the barrier-QP solver selection (qp_mode + cvxopt's options): RG_QP_CVXOPT computes the
  * interior-point iterate the reference's stack computes (utilities/controller.py:13-16,23) instead of the exact projection;
  * rg_step_io.zero_obs_on_end; + rg_actor_forward_explore(), rg_actor_pack_gru_f16x2() and rg_actor_weights.gru_packed == 3.
@@ -534,6 +536,38 @@ int rg_actor_pack_gru_bf16x3(const float *src, int32_t n_sets, int32_t hidden_di
  * the matrix cores take as it is. */
 int rg_actor_pack_gru_f16x2(const float *src, int32_t n_sets, int32_t hidden_dim, void *dst, void *hip_stream);
 const char *rg_actor_last_error(void);
+
+/* ---- actor unroll: the recurrent actor over every time step of an episode batch in ONE launch ----
+ * What a learner does first with an episode-major batch (EPyMARL: mac.init_hidden(B), then mac.forward(batch, t) for every t; the
+ * target network's pass and MAPPO's old-policy logits are the same computation).  The rule is stated once in csrc/actor_unroll.h
+ * (DESIGN.md section 4 "Actor unroll").  For every episode b < B and agent n < N independently:
+ *   h_{-1} = hidden_in[b][n], or zero when hidden_in is NULL; for t = 0 .. rows-1 in order,
+ *   (q[b][t][n][:], h_t) = actor(obs[b][t][n][:] (+ one-hot n), h_{t-1}); actions[b][t][n] is the greedy action (the first
+ *   maximum, a NaN counting as the largest value); hidden_out[b][n] = h_{rows-1}.
+ * The observation at t = 0 is read as stored (this is not rg_actor_forward's restart flag, which also zeroes the observation), and
+ * there are no `filled` masks: every one of the `rows` time steps is computed.  Bit-identical to `rows` calls of rg_actor_forward
+ * (gru_packed == 3, restart = NULL) on the time slices with the hidden state carried through memory.
+ * obs_pitch / out_pitch: the rows an episode takes in obs / in q and actions (>= rows): a slice [:, :rows] of a longer batch is read
+ * and written in place.  Rows t >= rows of q and actions are not touched.
+ * Handle-free; never allocates, copies or synchronises (safe under stream capture); launches on `hip_stream` of the caller's CURRENT
+ * device.  Layout: 5 pointers + 8 ints = 72 bytes, checked with rg_sizeof_actor_unroll_io(). */
+typedef struct rg_actor_unroll_io {
+    const float *obs;        /* [B][obs_pitch][N][D] */
+    float *q;                /* [B][out_pitch][N][A] or NULL */
+    int32_t *actions;        /* [B][out_pitch][N]    or NULL */
+    const float *hidden_in;  /* [B][N][H] or NULL: zeros */
+    float *hidden_out;       /* [B][N][H] or NULL; may equal hidden_in */
+    int32_t num_episodes, n_agents, obs_dim, rows, obs_pitch, out_pitch, append_agent_id, reserved;
+} rg_actor_unroll_io;
+int rg_sizeof_actor_unroll_io(void);
+/* Every argument is checked before the first HIP call.  Errors (text via rg_actor_unroll_last_error(), which names the argument):
+ * -1 w, -2 io, -3 io.obs NULL; -4 a weight array NULL; -5 use_rnn == 0 or gru_packed != 3 (the two-binary16-plane GRU only);
+ * -6 hidden_dim not 64 / 128; -7 n_actions outside 1..32; -8 n_sets not 1 or n_agents; -9 num_episodes, -10 n_agents (also above
+ * 65536), -11 obs_dim, -12 rows below 1; -13 obs_dim (+ n_agents) != input_dim; -14 padded input width above 64; -15 obs_pitch,
+ * -16 out_pitch below rows; -17 reserved != 0; -18 q, actions and hidden_out all NULL; -19 hidden_in, hidden_out, w1, wih, whh or
+ * w2 not 16-byte aligned; -20 num_episodes * max(pitch) * n_agents * max(obs_dim, n_actions) above 2^31 - 1; -30 the launch failed. */
+int rg_actor_unroll(const rg_actor_weights *w, const rg_actor_unroll_io *io, void *hip_stream);
+const char *rg_actor_unroll_last_error(void);
 
 /* ---- policy-in-the-loop rollouts ---------------------------------------------------------------
  * The evaluation / data-collection loop of misc.py:155-185 (`actor(obs, hs)`, arg-max, env.step; the actor of

@@ -138,6 +138,14 @@ class RgEpisodeStream(C.Structure):
                 ("episode_start", C.c_void_p), ("prob", C.c_void_p), ("T", C.c_int32), ("reserved", C.c_int32)]
 
 
+# rg_actor_unroll: the actor over every time step of an episode batch (include/robogym.h; the rule: csrc/actor_unroll.h)
+class RgActorUnrollIO(C.Structure):
+    _fields_ = [("obs", C.c_void_p), ("q", C.c_void_p), ("actions", C.c_void_p), ("hidden_in", C.c_void_p),
+                ("hidden_out", C.c_void_p), ("num_episodes", C.c_int32), ("n_agents", C.c_int32), ("obs_dim", C.c_int32),
+                ("rows", C.c_int32), ("obs_pitch", C.c_int32), ("out_pitch", C.c_int32), ("append_agent_id", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 # rg_step_form: which form the last rg_step launch took (include/robogym.h RG_FORM_*)
 FORM_NONE, FORM_BY_VALUE, FORM_RESIDENT, FORM_SHAPE = 0, 1, 2, 16
 
@@ -162,11 +170,13 @@ EXPORTS = ("rg_abi_version", "rg_last_error", "rg_sizeof_params", "rg_sizeof_sta
            "rg_actor_forward_sample", "rg_sizeof_policy_sample", "rg_policy_rollout_sample",
            "rg_sizeof_disturbance_params", "rg_set_disturbance", "rg_step_form", "rg_shape_match", "rg_shape_info",
            "rg_sizeof_render_params", "rg_render", "rg_render_last_error",
-           "rg_sizeof_episode_buffer", "rg_sizeof_episode_stream", "rg_episodes_append", "rg_episodes_last_error")
+           "rg_sizeof_episode_buffer", "rg_sizeof_episode_stream", "rg_episodes_append", "rg_episodes_last_error",
+           "rg_sizeof_actor_unroll_io", "rg_actor_unroll", "rg_actor_unroll_last_error")
 # the queries a library of an earlier build lacks: tolerated in one loaded through ROBOGYM_LIB (an A/B run against it), never in
 # the package's own
 LATE_QUERIES = ("rg_step_form", "rg_shape_match", "rg_shape_info", "rg_sizeof_render_params", "rg_render", "rg_render_last_error",
-                "rg_sizeof_episode_buffer", "rg_sizeof_episode_stream", "rg_episodes_append", "rg_episodes_last_error")
+                "rg_sizeof_episode_buffer", "rg_sizeof_episode_stream", "rg_episodes_append", "rg_episodes_last_error",
+                "rg_sizeof_actor_unroll_io", "rg_actor_unroll", "rg_actor_unroll_last_error")
 
 _lib = None
 
@@ -257,6 +267,11 @@ def load():
         lib.rg_episodes_last_error.restype = C.c_char_p
         lib.rg_sizeof_episode_buffer.restype = C.c_int
         lib.rg_sizeof_episode_stream.restype = C.c_int
+    if hasattr(lib, "rg_actor_unroll"):   # (LATE_QUERIES)
+        lib.rg_actor_unroll.argtypes = [C.POINTER(RgActorWeights), C.POINTER(RgActorUnrollIO), C.c_void_p]
+        lib.rg_actor_unroll.restype = C.c_int
+        lib.rg_actor_unroll_last_error.restype = C.c_char_p
+        lib.rg_sizeof_actor_unroll_io.restype = C.c_int
     for f in (lib.rg_destroy, lib.rg_bind_state, lib.rg_set_stream, lib.rg_reset, lib.rg_step, lib.rg_rollout, lib.rg_get_obs,
               lib.rg_sizeof_params, lib.rg_sizeof_state, lib.rg_sizeof_step_io):
         f.restype = C.c_int
@@ -269,7 +284,8 @@ def load():
             or lib.rg_sizeof_disturbance_params() != C.sizeof(RgDisturbanceParams)
             or (hasattr(lib, "rg_render") and lib.rg_sizeof_render_params() != C.sizeof(RgRenderParams))
             or (hasattr(lib, "rg_episodes_append") and (lib.rg_sizeof_episode_buffer() != C.sizeof(RgEpisodeBuffer)
-                                                        or lib.rg_sizeof_episode_stream() != C.sizeof(RgEpisodeStream)))):
+                                                        or lib.rg_sizeof_episode_stream() != C.sizeof(RgEpisodeStream)))
+            or (hasattr(lib, "rg_actor_unroll") and lib.rg_sizeof_actor_unroll_io() != C.sizeof(RgActorUnrollIO))):
         raise RobogymError("struct layout of the binding differs from the compiled library; rebuild")
     _lib = lib
     return lib

@@ -20,7 +20,7 @@ SOURCES = ["robogym_kernels.hip", "robogym_resident.hip", "robogym_resident_shap
            "robogym_policy_h128.hip", "robogym_policy_sample_h64.hip", "robogym_policy_sample_h128.hip", "robogym_lidar.hip", "robogym_lidar_rollout.hip", "robogym_lidar_ipm.hip",
            "robogym_lidar_rollout_ipm.hip", "robogym_team.hip", "robogym_team_rollout.hip", "robogym_team_ipm.hip",
            "robogym_team_rollout_ipm.hip", "robogym_disturb.hip", "robogym_disturb_rollout.hip", "robogym_disturb_ipm.hip",
-           "robogym_disturb_rollout_ipm.hip", "robogym_render.hip", "robogym_episodes.hip"]
+           "robogym_disturb_rollout_ipm.hip", "robogym_render.hip", "robogym_episodes.hip", "robogym_actor_unroll.hip"]
 # every header of csrc/ (a forgotten one would mean a stale library), and the C ABI's
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(CSRC, "probes", "*.h"))) + \
           [os.path.join(HERE, "..", "include", "robogym.h")]
@@ -61,6 +61,13 @@ IPM_SCHED = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 # first by-value struct; it changes every kernel of a translation unit it is given to, hence a file of its own.
 # tools/ubench/resident_args.py priced it (profiles/resident_args_ubench.txt).
 RESIDENT_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
+# The unroll kernels (actor_unroll.h) run actor_body.inc inside a time loop, and inside a loop the block placement duplicates the
+# join block of the arg-max pass's `if (c < A)`: the taken path falls into its own copy of `s_or_b64 exec`, the skipped path
+# branches to another.  Correct code -- the compare in front of that copy belongs to the `then` lanes -- but it is the shape
+# tools/isa_scan.py exec_prologue reports (vector instructions between a label, here the inner `if (ok && a.q)`'s join, and an
+# exec restore), and tests/test_kernel_resources.py scans every shipped kernel.  Without the duplication the kernels have the
+# layout actor_kernel has, the same registers and LDS, and the scan is clean.
+UNROLL_LAYOUT = ["-mllvm", "-tail-dup-placement=false"]
 FILE_FLAGS = {"robogym_tpe.hip": ["-fno-slp-vectorize"], "robogym_rollout_tpe.hip": ["-fno-slp-vectorize"],
               "robogym_kernels.hip": GROUP_SLP, "robogym_rollout_group.hip": GROUP_SLP,
               "robogym_resident.hip": GROUP_SLP + RESIDENT_PRELOAD,
@@ -77,7 +84,8 @@ FILE_FLAGS = {"robogym_tpe.hip": ["-fno-slp-vectorize"], "robogym_rollout_tpe.hi
               "robogym_team_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_team_rollout_ipm.hip": GROUP_SLP + IPM_SCHED,
               # the pose-disturbance kernels (step_group.h disturb_step_kernel): lane-group kernels, with the flags of their mode
               "robogym_disturb.hip": GROUP_SLP, "robogym_disturb_rollout.hip": GROUP_SLP,
-              "robogym_disturb_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_disturb_rollout_ipm.hip": GROUP_SLP + IPM_SCHED}
+              "robogym_disturb_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_disturb_rollout_ipm.hip": GROUP_SLP + IPM_SCHED,
+              "robogym_actor_unroll.hip": UNROLL_LAYOUT}
 BASE_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 STAMP = LIB + ".flags"
 
@@ -157,7 +165,7 @@ def build_host_sanitized(out=None):
     """CPU sanitizer tier: the C ABI's host half (csrc/robogym_capi.hip) compiled for the HOST ONLY with
     ASan + UBSan, linked against tests/sanitize/launch_stubs.cpp in place of the device translation units; with it the host half
     of csrc/robogym_render.hip (rg_render's argument checks: handle-free, it needs no stub) and of csrc/robogym_episodes.hip
-    (rg_episodes_append's, likewise).
+    (rg_episodes_append's, likewise) and of csrc/robogym_actor_unroll.hip (rg_actor_unroll's, likewise).
     Used by tests/test_sanitizers.py for the no-GPU cases of tests/test_host.py; never shipped.  (GPU ASan is
     not available on this pool: sanitizers run on the CPU build only.)"""
     out = out or os.path.join(HERE, "build", "librobogym_capi_asan.so")
@@ -166,8 +174,9 @@ def build_host_sanitized(out=None):
     stubs_sample = os.path.join(HERE, "..", "tests", "sanitize", "launch_stubs_sample.cpp")   # rg_actor_forward_sample
     cmd = [hipcc_path(), "-x", "hip", "--offload-host-only", "-O1", "-g", "-fno-omit-frame-pointer",
            "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fPIC", "-shared", "-std=c++17", "-DRG_RENDER_HOST_ONLY",
-           "-DRG_EPISODES_HOST_ONLY", "-I", CSRC, os.path.join(CSRC, "robogym_capi.hip"), os.path.join(CSRC, "robogym_render.hip"),
-           os.path.join(CSRC, "robogym_episodes.hip"), stubs, stubs_sample,
+           "-DRG_EPISODES_HOST_ONLY", "-DRG_UNROLL_HOST_ONLY", "-I", CSRC, os.path.join(CSRC, "robogym_capi.hip"),
+           os.path.join(CSRC, "robogym_render.hip"), os.path.join(CSRC, "robogym_episodes.hip"),
+           os.path.join(CSRC, "robogym_actor_unroll.hip"), stubs, stubs_sample,
            "-o", out]
     subprocess.check_call(cmd)
     return out

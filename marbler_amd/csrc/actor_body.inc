@@ -1,7 +1,8 @@
 // actor_body.inc -- the body of the actor's tile computation (csrc/actor_mfma.hip describes the network and its layout on the
-// matrix cores), included INSIDE a function by its two users:
+// matrix cores), included INSIDE a function by its three users:
 //   * actor_kernel (actor_mfma.hip): one tile of the whole batch per workgroup, hidden state in memory;
-//   * policy_tile (policy_rollout.h): a tile of the workgroup's envs at one time step of rg_policy_rollout, hidden state in LDS.
+//   * policy_tile (policy_rollout.h): a tile of the workgroup's envs at one time step of rg_policy_rollout, hidden state in LDS;
+//   * unroll_tile (actor_unroll.h): a tile of an episode batch at one time step of rg_actor_unroll, hidden state in LDS.
 // The including function provides `a` (ActorArgs), the template parameters H and SPLIT, and three hooks:
 //   RG_ACTOR_LOCATE(shared, E, set, base)  -- assigns the tile's weight set and first row (shared: flat row of [E*N]; otherwise env)
 //   RG_ACTOR_HIDDEN_LOAD(r, k4)            -- float4 k4 of the old hidden state of flat row r (r = 0 for rows outside the tile)
@@ -10,12 +11,32 @@
 //                                             greedy / epsilon-greedy kernels pass `false` and keep their code; the sampling
 //                                             kernels (actor_sample_kernel, policy_rollout_sample_kernel) `true`.  Optional:
 //                                             an includer that does not define it gets `false`
+//   RG_ACTOR_IN_ROW(r)                     -- where flat row r's observation lies, in rows of a.D floats from a.obs.  Optional:
+//                                             an includer that does not define it gets `r` (obs is [E][N][D])
+//   RG_ACTOR_OUT_ROW(r)                    -- where flat row r's q row (A floats from a.q) and greedy action (from a.actions) go.
+//                                             Optional, default `r`.  (The sampling and exploring epilogues index their arrays by
+//                                             the flat row: an includer that moves the rows offers neither.)
+//   RG_ACTOR_THREAD                        -- the thread's index in the workgroup.  Optional, default `threadIdx.x`; an includer
+//                                             that runs the body in a loop passes a copy the compiler cannot see through, so that
+//                                             what the body derives from it is not held across the loop (actor_unroll.h)
 // Rows are valid while (shared ? base + i < E * N : base + i < E): a caller that owns part of the batch passes the end of its part
 // as a.E.  Textual inclusion keeps actor_kernel's instruction stream exactly what it was before the tile computation had a
 // second user (a device-function boundary changes how the kernel-argument loads are scheduled).
 #ifndef RG_ACTOR_SAMPLING   // an includer that knows the three hooks above only: greedy / epsilon-greedy
 #define RG_ACTOR_SAMPLING(a) false
 #define RG_ACTOR_SAMPLING_DEFAULTED
+#endif
+#ifndef RG_ACTOR_THREAD
+#define RG_ACTOR_THREAD threadIdx.x
+#define RG_ACTOR_THREAD_DEFAULTED
+#endif
+#ifndef RG_ACTOR_IN_ROW
+#define RG_ACTOR_IN_ROW(r) r
+#define RG_ACTOR_IN_ROW_DEFAULTED
+#endif
+#ifndef RG_ACTOR_OUT_ROW
+#define RG_ACTOR_OUT_ROW(r) r
+#define RG_ACTOR_OUT_ROW_DEFAULTED
 #endif
     RG_ASTAMP_BEGIN();
     constexpr int NW = H / 32;  // wavefronts per tile
@@ -27,7 +48,7 @@
     float *const Hs = lds + TM * H;  // the old hidden state (A operand), then the new one
     _Float16 *const Yp = reinterpret_cast<_Float16 *>(lds);                // planes: hi at 0, lo' at TM * H halves
     _Float16 *const Hp = reinterpret_cast<_Float16 *>(lds + (SPLIT == 2 ? 2 : 0) * TM * H);
-    const int tid = threadIdx.x, lane = tid & 63, cb = tid >> 6, half = lane >> 5, col = lane & 31;
+    const int tid = RG_ACTOR_THREAD, lane = tid & 63, cb = tid >> 6, half = lane >> 5, col = lane & 31;
     const int E = a.E, N = a.N, A = a.w.n_actions, I = a.w.input_dim, IP = a.ip;
     const bool shared = a.w.n_sets == 1;
     // tile -> weight set and rows
@@ -102,7 +123,7 @@
         const int r = ok ? row_of(srow) : 0;
         const int env = shared ? r / N : base + srow, agent = shared ? r - env * N : set;
         int restarted = a.restart ? a.restart[ok ? env : 0] : 0;
-        const float *xrow = a.obs + static_cast<size_t>(r) * a.D;
+        const float *xrow = a.obs + static_cast<size_t>(RG_ACTOR_IN_ROW(r)) * a.D;
         const int id_k = (ok && a.append_agent_id) ? a.D + agent : -1;   // where this row's one-hot agent id sits
         float xv[32 / TPRX];
         u32x4 wv[4];
@@ -166,7 +187,7 @@
         const bool ok = row_ok(col);
         const int r = ok ? row_of(col) : 0;
         const int env = r / N, agent = r - env * N;
-        const float *xrow = a.obs + static_cast<size_t>(r) * a.D;
+        const float *xrow = a.obs + static_cast<size_t>(RG_ACTOR_IN_ROW(r)) * a.D;
         const float *wrow = W1 + static_cast<size_t>(n) * I;
         const bool live = live_s[col] != 0;
         const int id_k = (ok && a.append_agent_id) ? a.D + agent : -1;
@@ -527,7 +548,7 @@
 #pragma unroll
                 for (int wv = 0; wv < NW; ++wv) v = v + Y[wv * (TM * 32) + i * 32 + c];
                 v = v + b2v[c_];
-                if (ok && a.q) a.q[static_cast<size_t>(r) * A + c] = v;
+                if (ok && a.q) a.q[static_cast<size_t>(RG_ACTOR_OUT_ROW(r)) * A + c] = v;
                 vq[c_] = v;
                 if (v > best || (v != v && best == best)) {  // first maximum, like torch.argmax
                     best = v;
@@ -558,11 +579,23 @@
                 const int k = static_cast<int>(a.explore_u[r] * a.explore_scale);
                 if (static_cast<unsigned>(k) < static_cast<unsigned>(A)) arg = k;
             }
-            a.actions[r] = arg;
+            a.actions[RG_ACTOR_OUT_ROW(r)] = arg;
         }
     }
     RG_ASTAMP_END(a, E, N, A, H, cb, lane);
 #ifdef RG_ACTOR_SAMPLING_DEFAULTED
 #undef RG_ACTOR_SAMPLING
 #undef RG_ACTOR_SAMPLING_DEFAULTED
+#endif
+#ifdef RG_ACTOR_THREAD_DEFAULTED
+#undef RG_ACTOR_THREAD
+#undef RG_ACTOR_THREAD_DEFAULTED
+#endif
+#ifdef RG_ACTOR_IN_ROW_DEFAULTED
+#undef RG_ACTOR_IN_ROW
+#undef RG_ACTOR_IN_ROW_DEFAULTED
+#endif
+#ifdef RG_ACTOR_OUT_ROW_DEFAULTED
+#undef RG_ACTOR_OUT_ROW
+#undef RG_ACTOR_OUT_ROW_DEFAULTED
 #endif

@@ -213,6 +213,30 @@ class EpisodeBuffer(object):
             out["probs"] = self.prob[idx, :rows]
         return out
 
+    def unroll(self, actor, slots=None, trim=False, obs_agent_id=True):
+        """A learner's first pass over batch(slots, trim): `actor` (a BatchedActor) from a zero hidden state over every row of
+        every selected episode, in ONE launch (BatchedActor.unroll; the rule: csrc/actor_unroll.h).  Returns q [B, rows, N, A]
+        and greedy [B, rows, N] int32 over the same rows as batch(slots, trim).  Every row is computed, the padding behind an
+        episode's end included (there are no masks: `filled` says which rows are data); q of the taken action and max q stay
+        torch.gather / max on q.  ValueError for an actor that does not fit the buffer or that the launch refuses."""
+        import torch
+        for name, have, want in (("n_agents", getattr(actor, "n_agents", None), self.N), ("n_actions", getattr(actor, "n_actions", None), self.A),
+                                 ("input_dim", getattr(actor, "input_dim", None), self.D + (self.N if obs_agent_id else 0))):
+            if have != want:
+                raise ValueError(f"the actor's {name} is {have}, the buffer's episodes need {want}")
+        if actor.w1.device != self.device:
+            raise ValueError(f"the actor is on {actor.w1.device}, the buffer on {self.device}")
+        idx = self._slots(slots)
+        B = int(idx.numel())
+        rows = self.L + 1
+        if trim and B > 0:
+            rows = int(self.length[idx].max()) + 1
+        if B == 0:
+            return {"q": torch.empty(0, rows, self.N, self.A, device=self.device),
+                    "greedy": torch.empty(0, rows, self.N, dtype=torch.int32, device=self.device)}
+        q, greedy = actor.unroll(self.obs[idx][:, :rows], append_agent_id=obs_agent_id)   # (the gathered copy is read in place)
+        return {"q": q, "greedy": greedy}
+
     def sample(self, n, generator=None):
         """n slots drawn uniformly, without replacement, among the complete ones (int64); ValueError if fewer are complete."""
         import torch

@@ -170,6 +170,105 @@ class BatchedActor(object):
             raise _lib.RobogymError("rg_actor_forward: " + lib.rg_actor_last_error().decode())
         return q_out, actions_out
 
+    # ------------------------------------------------------------------ whole episode batches (csrc/actor_unroll.h)
+    @staticmethod
+    def _episode_pitch(name, t, inner):
+        """The rows an episode takes in `t` ([B, rows, *inner] with the last dimensions contiguous), from its batch stride."""
+        want, row = [], 1
+        for d in reversed(inner):
+            want.insert(0, row)
+            row *= d
+        want.insert(0, row)
+        # (a dimension of size 1 has no stride to speak of)
+        if any(t.shape[1 + k] > 1 and t.stride(1 + k) != want[k] for k in range(len(want))):
+            raise ValueError(f"{name}: the last {len(want)} dimensions must be contiguous (shape {tuple(t.shape)}, strides {t.stride()})")
+        B, rows = t.shape[0], t.shape[1]
+        if B == 1:
+            return rows
+        if t.stride(0) % row != 0 or t.stride(0) < rows * row:
+            raise ValueError(f"{name}: the batch stride {t.stride(0)} must be a multiple of {row} and at least {rows * row}")
+        return t.stride(0) // row
+
+    def unroll(self, obs, append_agent_id=True, hidden=None, q_out=None, actions_out=None, hidden_out=None, stream=None):
+        """The actor over every time step of an episode batch in ONE launch (rg_actor_unroll; the rule: csrc/actor_unroll.h):
+        what `init_hidden(B)` and `rows` calls of forward_fused on the time slices compute, bit for bit, with the hidden state kept
+        on the chip.  obs [B, rows, N, D] f32 on the actor's device, its last three dimensions contiguous and its batch stride a
+        multiple of N D (EpisodeBuffer.obs[:, :rows] is read in place); the observation at t = 0 is read as stored.  hidden
+        [B, N, H] f32 or None (zeros); hidden_out [B, N, H] or None receives the state after the last step (it may be `hidden`).
+        q_out [B, rows, N, A] f32 / actions_out [B, rows, N] int32: outputs to reuse, laid out like obs (the same number of rows
+        per episode in both); nothing is allocated when both are given, so the call can be captured.  Every one of the `rows`
+        steps is computed: there are no masks.  Returns (q, greedy actions).  ValueError for a wrong dtype, shape, stride or
+        device and for an actor the launch refuses."""
+        import ctypes as C
+        if not (self.use_rnn and self.pack_gru == "f16x2"):
+            raise ValueError("unroll: the actor must be a GRU packed as two binary16 planes (pack_gru=True / 'f16x2')")
+        if self.hidden_dim not in (64, 128):
+            raise ValueError(f"unroll: hidden size must be 64 or 128, the actor's is {self.hidden_dim}")
+        if not 1 <= self.n_actions <= 32:
+            raise ValueError(f"unroll: n_actions must be in 1..32, the actor's is {self.n_actions}")
+        if (self.input_dim + 7) // 8 * 8 > 64:
+            raise ValueError(f"unroll: an input width above 64 is not supported, the actor's is {self.input_dim}")
+        dev, N, H, A = self.w1.device, self.n_agents, self.hidden_dim, self.n_actions
+        if not isinstance(obs, torch.Tensor) or obs.dtype != torch.float32:
+            raise ValueError("unroll: obs must be a float32 tensor")
+        if obs.dim() != 4 or obs.shape[0] < 1 or obs.shape[1] < 1 or obs.shape[2] != N:
+            raise ValueError(f"unroll: obs must be [B, rows, {N}, D] with B, rows >= 1, got {tuple(obs.shape)}")
+        B, rows, _, D = obs.shape
+        if D + (N if append_agent_id else 0) != self.input_dim:
+            raise ValueError(f"unroll: the actor expects {self.input_dim} inputs per agent, obs provides "
+                             f"{D + (N if append_agent_id else 0)}")
+        if obs.device != dev:
+            raise ValueError(f"unroll: obs is on {obs.device}, the actor on {dev}")
+        obs_pitch = self._episode_pitch("unroll: obs", obs, (N, D))
+        out_pitch = None
+        for name, t, dtype, inner in (("q_out", q_out, torch.float32, (N, A)), ("actions_out", actions_out, torch.int32, (N,))):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (B, rows) + inner:
+                raise ValueError(f"unroll: {name} must be a {dtype} tensor {(B, rows) + inner}")
+            if t.device != dev:
+                raise ValueError(f"unroll: {name} is on {t.device}, the actor on {dev}")
+            pitch = self._episode_pitch(f"unroll: {name}", t, inner)
+            if out_pitch not in (None, pitch):
+                raise ValueError(f"unroll: q_out and actions_out must take the same number of rows per episode ({out_pitch}, {pitch})")
+            out_pitch = pitch
+        for name, t in (("hidden", hidden), ("hidden_out", hidden_out)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (B, N, H) or not t.is_contiguous():
+                raise ValueError(f"unroll: {name} must be a contiguous float32 tensor {(B, N, H)}")
+            if t.device != dev:
+                raise ValueError(f"unroll: {name} is on {t.device}, the actor on {dev}")
+        if dev.type != "cuda":
+            raise ValueError(f"unroll: the actor lives on {dev}; the launch runs on a HIP device and has no host path")
+        from . import _lib
+        lib = _lib.load()
+        if out_pitch is None:
+            out_pitch = rows
+        if q_out is None:
+            q_out = torch.empty(B, out_pitch, N, A, device=dev)[:, :rows]
+        if actions_out is None:
+            actions_out = torch.empty(B, out_pitch, N, dtype=torch.int32, device=dev)[:, :rows]
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        ws = self._weights_struct()
+        ev = getattr(self, "_pack_done", None)
+        if ev is not None:   # the weights were packed (once) on the then-current stream: order this stream behind them
+            if ev.query():
+                self._pack_done = None
+            else:
+                stream.wait_event(ev)
+        io = _lib.RgActorUnrollIO(obs.data_ptr(), q_out.data_ptr(), actions_out.data_ptr(),
+                                  hidden.data_ptr() if hidden is not None else None,
+                                  hidden_out.data_ptr() if hidden_out is not None else None,
+                                  B, N, D, rows, obs_pitch, out_pitch, 1 if append_agent_id else 0, 0)
+        with torch.cuda.device(dev):
+            rc = lib.rg_actor_unroll(C.byref(ws), C.byref(io), C.c_void_p(stream.cuda_stream))
+        if rc != 0:
+            msg = f"({rc}) {lib.rg_actor_unroll_last_error().decode()}"
+            raise (_lib.RobogymError if rc == -30 else ValueError)(msg)
+        return q_out, actions_out
+
 
 def policy_rollout(env, actor, T, io, hidden, actions, restart=None, append_agent_id=True, restart_on_done=False, explore_u=None,
                    epsilon=0.0, obs=None, reward_sum=None, ended=None, dist_sum=None, sample_u=None, prob=None):
