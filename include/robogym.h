@@ -35,7 +35,9 @@ extern "C" {
  * rg_render_last_error() (batched RGB frames of the envs' state); + rg_episodes_append(), rg_episode_buffer, rg_episode_stream,
  * rg_sizeof_episode_buffer(), rg_sizeof_episode_stream(), rg_episodes_last_error() (a collector's stream as padded episodes);
  * + rg_actor_unroll(), rg_actor_unroll_io, rg_sizeof_actor_unroll_io(), rg_actor_unroll_last_error() (the actor over every time
- * step of an episode batch in one launch).
+ * step of an episode batch in one launch); + rg_td_targets(), rg_mixer_weights, rg_td_targets_io, rg_sizeof_mixer_weights(),
+ * rg_sizeof_td_targets_io(), rg_td_targets_last_error() (the target mixer and the double-Q TD targets of an episode batch in one
+ * launch).
  * 6 (round 5): rg_scenario_params ends in the barrier-QP solver selection (qp_mode + cvxopt's options): RG_QP_CVXOPT computes the
  * interior-point iterate the reference's stack computes (utilities/controller.py:13-16,23) instead of the exact projection;
  * rg_step_io.zero_obs_on_end; + rg_actor_forward_explore(), rg_actor_pack_gru_f16x2() and rg_actor_weights.gru_packed == 3.
@@ -568,6 +570,93 @@ int rg_sizeof_actor_unroll_io(void);
  * w2 not 16-byte aligned; -20 num_episodes * max(pitch) * n_agents * max(obs_dim, n_actions) above 2^31 - 1; -30 the launch failed. */
 int rg_actor_unroll(const rg_actor_weights *w, const rg_actor_unroll_io *io, void *hip_stream);
 const char *rg_actor_unroll_last_error(void);
+
+/* ---- TD targets: target mixer and double-Q targets of an episode batch in ONE launch ----
+ * The gradient-free half of a Q-learner's training step (EPyMARL: what q_learner.train computes under detach() from the target
+ * network's unroll; QMixer with mixing_embed_dim 32, hypernet_layers 2, hypernet_embed 64; `state` is the concatenated
+ * observations).  The rule is stated once in csrc/td_targets.h (DESIGN.md section 4 "TD targets"):
+ *
+ * Inputs.
+ *   - qt [B][q_pitch][N][A] f32: the target actor's unroll.
+ *   - sel [B][q_pitch][N] i32 or NULL: the online actor's greedy actions, which is double-Q.
+ *   - obs [B][obs_pitch][N][D] f32: the state of row (b, t) is the S = N D contiguous floats of obs[b][t], read in place.
+ *   - reward f32, terminated u8 and filled u8, each [B][flag_pitch].
+ *   - rows >= 2, with T = rows - 1.
+ *   - gamma.
+ *   - kind in {none, vdn, qmix} and the mixer's weights.
+ * Outputs.
+ *   - targets [B][out_pitch] f32.  For `none` it is [B][out_pitch][N].
+ *   - Optional mask [B][out_pitch] f32.
+ *   - Optional agent_q [B][out_pitch][N] f32: the per-agent value before mixing.
+ * For every b < B and t < T independently:
+ *   - Mask.  mask[b][t] = filled[b][t] && (t == 0 || !terminated[b][t-1]), as 0.0 / 1.0.  This is EPyMARL's
+ *     mask[:, 1:] *= 1 - terminated[:, :-1].
+ *   - Masked rows.  A row with mask == 0 gets targets = 0.0 and agent_q = 0.0.  None of its qt, sel or obs rows is read.
+ *   - Terminal rows.  A row with mask == 1 and terminated[b][t] gets targets = reward[b][t] and agent_q = 0.0.  Row t+1 is not read.
+ *   - Agent values.  Otherwise a_n = sel[b][t+1][n] and agent_q[n] = qt[b][t+1][n][a_n].
+ *       - An a_n outside [0, A) makes agent_q[n] NaN, and with it that row's target (with `none`: that agent's), and reads nothing
+ *         out of bounds.
+ *       - With sel == NULL, agent_q[n] is the maximum of qt[b][t+1][n][:] by the actor epilogue's existing rule: the first maximum,
+ *         with a NaN counting as the largest value.
+ *       - avail_actions is all ones in this project and plays no part.
+ *   - Mixing.
+ *       - none: y_n = agent_q[n].
+ *       - vdn: y is the binary32 sum over n = 0 .. N-1 in that order: ((agent_q[0] + agent_q[1]) + agent_q[2]) + ...
+ *       - qmix: EPyMARL's QMixer.forward on (agent_q, state[b][t+1]):
+ *           w1 = |W1b relu(W1a s + b1a) + b1b|, viewed [N][32].
+ *           b1 = Wb s + bb.
+ *           hidden = elu(agent_q w1 + b1).
+ *           wf = |Wfb relu(Wfa s + bfa) + bfb|, [32].
+ *           v = Vb relu(Va s + ba) + bv.
+ *           y = hidden wf + v.
+ *   - Target.  targets = fl(reward[b][t] + fl(gamma y)).  The product is rounded before the sum, with no contraction.
+ * Rows t >= T of the outputs are not touched.
+ * With none and vdn this fixes every bit.  The qmix arithmetic is float32 with a summation order of the kernel's choosing.
+ *
+ * The mixer's weights, packed once on the host into the K-major layout the kernel streams (marbler_amd/targets.py TargetMixer; torch's
+ * Linear.weight is [out][in], every matrix here is its transpose [in][out]); qmix only, NULL otherwise; each 16-byte aligned:
+ *   w_in [SP][192]: the four first layers side by side -- columns 0..63 hyper_w_1.0, 64..127 hyper_w_final.0, 128..159 V.0,
+ *        160..191 hyper_b_1 -- with SP = state_dim rounded up to a multiple of 4 and the rows behind state_dim zero; b_in [192];
+ *   w_w1 [64][N 32] hyper_w_1.2, b_w1 [N 32]; w_wf [64][32] hyper_w_final.2, b_wf [32]; w_v [32] V.2, b_v [1].
+ * Layout: 8 pointers + 6 ints = 88 bytes, checked with rg_sizeof_mixer_weights(). */
+enum { RG_MIXER_NONE = 0, RG_MIXER_VDN = 1, RG_MIXER_QMIX = 2 };
+typedef struct rg_mixer_weights {
+    const float *w_in, *b_in, *w_w1, *b_w1, *w_wf, *b_wf, *w_v, *b_v;
+    int32_t kind;             /* RG_MIXER_* */
+    int32_t n_agents;         /* must equal io.n_agents */
+    int32_t state_dim;        /* qmix: must equal io.n_agents * io.obs_dim */
+    int32_t embed_dim;        /* qmix: mixing_embed_dim, must be 32 */
+    int32_t hypernet_embed;   /* qmix: must be 64 (with hypernet_layers 2) */
+    int32_t reserved;
+} rg_mixer_weights;
+int rg_sizeof_mixer_weights(void);
+/* Layout: 9 pointers + 9 ints + 1 float + 1 int = 116 bytes, 120 with the tail padding, checked with rg_sizeof_td_targets_io(). */
+typedef struct rg_td_targets_io {
+    const float *qt;            /* [B][q_pitch][N][A] */
+    const int32_t *sel;         /* [B][q_pitch][N] or NULL: the maximum over the actions */
+    const float *obs;           /* [B][obs_pitch][N][D]; read with qmix only (may be NULL otherwise) */
+    const float *reward;        /* [B][flag_pitch] */
+    const uint8_t *terminated;  /* [B][flag_pitch] */
+    const uint8_t *filled;      /* [B][flag_pitch] */
+    float *targets;             /* [B][out_pitch], with RG_MIXER_NONE [B][out_pitch][N] */
+    float *mask;                /* [B][out_pitch] or NULL */
+    float *agent_q;             /* [B][out_pitch][N] or NULL */
+    int32_t num_episodes, n_agents, obs_dim, n_actions, rows;
+    int32_t q_pitch, obs_pitch, flag_pitch, out_pitch;   /* rows an episode takes in qt and sel; obs; the flags; the outputs */
+    float gamma;
+    int32_t reserved;
+} rg_td_targets_io;
+int rg_sizeof_td_targets_io(void);
+/* Handle-free; never allocates, copies or synchronises (safe under stream capture); launches on `hip_stream` of the caller's CURRENT
+ * device.  Every argument is checked before the first HIP call.  Errors (text via rg_td_targets_last_error(), which names the
+ * argument): -1 m, -2 io NULL; -3 qt, reward, terminated, filled or targets NULL (obs with qmix); -4 an unknown kind; -5 qmix with
+ * a weight array NULL; -6 or not 16-byte aligned; -7 embed_dim not 32 / hypernet_embed not 64; -8 m.n_agents != io.n_agents;
+ * -9 qmix: m.state_dim != io.n_agents * io.obs_dim; -10 num_episodes below 1; -11 rows below 2; -12 n_agents outside
+ * 1..RG_MAX_AGENTS; -13 n_actions outside 1..32; -14 obs_dim below 1, or with qmix the padded state wider than 256; -15 obs_pitch,
+ * -16 q_pitch, -17 flag_pitch below rows; -18 out_pitch below rows - 1; -19 gamma not finite or outside [0, 1]; -20 m.reserved or
+ * io.reserved != 0; -21 an array of more than 2^31 - 1 elements; -30 the launch failed. */
+int rg_td_targets(const rg_mixer_weights *m, const rg_td_targets_io *io, void *hip_stream);
+const char *rg_td_targets_last_error(void);
 
 /* ---- policy-in-the-loop rollouts ---------------------------------------------------------------
  * The evaluation / data-collection loop of misc.py:155-185 (`actor(obs, hs)`, arg-max, env.step; the actor of

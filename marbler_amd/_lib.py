@@ -146,6 +146,24 @@ class RgActorUnrollIO(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+# rg_td_targets: the target mixer and the TD targets of an episode batch (include/robogym.h; the rule: csrc/td_targets.h)
+MIXER_NONE, MIXER_VDN, MIXER_QMIX = 0, 1, 2
+
+
+class RgMixerWeights(C.Structure):
+    _fields_ = [("w_in", C.c_void_p), ("b_in", C.c_void_p), ("w_w1", C.c_void_p), ("b_w1", C.c_void_p), ("w_wf", C.c_void_p),
+                ("b_wf", C.c_void_p), ("w_v", C.c_void_p), ("b_v", C.c_void_p), ("kind", C.c_int32), ("n_agents", C.c_int32),
+                ("state_dim", C.c_int32), ("embed_dim", C.c_int32), ("hypernet_embed", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RgTdTargetsIO(C.Structure):
+    _fields_ = [("qt", C.c_void_p), ("sel", C.c_void_p), ("obs", C.c_void_p), ("reward", C.c_void_p), ("terminated", C.c_void_p),
+                ("filled", C.c_void_p), ("targets", C.c_void_p), ("mask", C.c_void_p), ("agent_q", C.c_void_p),
+                ("num_episodes", C.c_int32), ("n_agents", C.c_int32), ("obs_dim", C.c_int32), ("n_actions", C.c_int32),
+                ("rows", C.c_int32), ("q_pitch", C.c_int32), ("obs_pitch", C.c_int32), ("flag_pitch", C.c_int32),
+                ("out_pitch", C.c_int32), ("gamma", C.c_float), ("reserved", C.c_int32)]
+
+
 # rg_step_form: which form the last rg_step launch took (include/robogym.h RG_FORM_*)
 FORM_NONE, FORM_BY_VALUE, FORM_RESIDENT, FORM_SHAPE = 0, 1, 2, 16
 
@@ -171,12 +189,14 @@ EXPORTS = ("rg_abi_version", "rg_last_error", "rg_sizeof_params", "rg_sizeof_sta
            "rg_sizeof_disturbance_params", "rg_set_disturbance", "rg_step_form", "rg_shape_match", "rg_shape_info",
            "rg_sizeof_render_params", "rg_render", "rg_render_last_error",
            "rg_sizeof_episode_buffer", "rg_sizeof_episode_stream", "rg_episodes_append", "rg_episodes_last_error",
-           "rg_sizeof_actor_unroll_io", "rg_actor_unroll", "rg_actor_unroll_last_error")
+           "rg_sizeof_actor_unroll_io", "rg_actor_unroll", "rg_actor_unroll_last_error",
+           "rg_sizeof_mixer_weights", "rg_sizeof_td_targets_io", "rg_td_targets", "rg_td_targets_last_error")
 # the queries a library of an earlier build lacks: tolerated in one loaded through ROBOGYM_LIB (an A/B run against it), never in
 # the package's own
 LATE_QUERIES = ("rg_step_form", "rg_shape_match", "rg_shape_info", "rg_sizeof_render_params", "rg_render", "rg_render_last_error",
                 "rg_sizeof_episode_buffer", "rg_sizeof_episode_stream", "rg_episodes_append", "rg_episodes_last_error",
-                "rg_sizeof_actor_unroll_io", "rg_actor_unroll", "rg_actor_unroll_last_error")
+                "rg_sizeof_actor_unroll_io", "rg_actor_unroll", "rg_actor_unroll_last_error",
+                "rg_sizeof_mixer_weights", "rg_sizeof_td_targets_io", "rg_td_targets", "rg_td_targets_last_error")
 
 _lib = None
 
@@ -272,6 +292,12 @@ def load():
         lib.rg_actor_unroll.restype = C.c_int
         lib.rg_actor_unroll_last_error.restype = C.c_char_p
         lib.rg_sizeof_actor_unroll_io.restype = C.c_int
+    if hasattr(lib, "rg_td_targets"):   # (LATE_QUERIES)
+        lib.rg_td_targets.argtypes = [C.POINTER(RgMixerWeights), C.POINTER(RgTdTargetsIO), C.c_void_p]
+        lib.rg_td_targets.restype = C.c_int
+        lib.rg_td_targets_last_error.restype = C.c_char_p
+        lib.rg_sizeof_mixer_weights.restype = C.c_int
+        lib.rg_sizeof_td_targets_io.restype = C.c_int
     for f in (lib.rg_destroy, lib.rg_bind_state, lib.rg_set_stream, lib.rg_reset, lib.rg_step, lib.rg_rollout, lib.rg_get_obs,
               lib.rg_sizeof_params, lib.rg_sizeof_state, lib.rg_sizeof_step_io):
         f.restype = C.c_int
@@ -285,7 +311,9 @@ def load():
             or (hasattr(lib, "rg_render") and lib.rg_sizeof_render_params() != C.sizeof(RgRenderParams))
             or (hasattr(lib, "rg_episodes_append") and (lib.rg_sizeof_episode_buffer() != C.sizeof(RgEpisodeBuffer)
                                                         or lib.rg_sizeof_episode_stream() != C.sizeof(RgEpisodeStream)))
-            or (hasattr(lib, "rg_actor_unroll") and lib.rg_sizeof_actor_unroll_io() != C.sizeof(RgActorUnrollIO))):
+            or (hasattr(lib, "rg_actor_unroll") and lib.rg_sizeof_actor_unroll_io() != C.sizeof(RgActorUnrollIO))
+            or (hasattr(lib, "rg_td_targets") and (lib.rg_sizeof_mixer_weights() != C.sizeof(RgMixerWeights)
+                                                   or lib.rg_sizeof_td_targets_io() != C.sizeof(RgTdTargetsIO)))):
         raise RobogymError("struct layout of the binding differs from the compiled library; rebuild")
     _lib = lib
     return lib

@@ -20,7 +20,8 @@ SOURCES = ["robogym_kernels.hip", "robogym_resident.hip", "robogym_resident_shap
            "robogym_policy_h128.hip", "robogym_policy_sample_h64.hip", "robogym_policy_sample_h128.hip", "robogym_lidar.hip", "robogym_lidar_rollout.hip", "robogym_lidar_ipm.hip",
            "robogym_lidar_rollout_ipm.hip", "robogym_team.hip", "robogym_team_rollout.hip", "robogym_team_ipm.hip",
            "robogym_team_rollout_ipm.hip", "robogym_disturb.hip", "robogym_disturb_rollout.hip", "robogym_disturb_ipm.hip",
-           "robogym_disturb_rollout_ipm.hip", "robogym_render.hip", "robogym_episodes.hip", "robogym_actor_unroll.hip"]
+           "robogym_disturb_rollout_ipm.hip", "robogym_render.hip", "robogym_episodes.hip", "robogym_actor_unroll.hip",
+           "robogym_td_targets.hip"]
 # every header of csrc/ (a forgotten one would mean a stale library), and the C ABI's
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(CSRC, "probes", "*.h"))) + \
           [os.path.join(HERE, "..", "include", "robogym.h")]
@@ -165,7 +166,9 @@ def build_host_sanitized(out=None):
     """CPU sanitizer tier: the C ABI's host half (csrc/robogym_capi.hip) compiled for the HOST ONLY with
     ASan + UBSan, linked against tests/sanitize/launch_stubs.cpp in place of the device translation units; with it the host half
     of csrc/robogym_render.hip (rg_render's argument checks: handle-free, it needs no stub) and of csrc/robogym_episodes.hip
-    (rg_episodes_append's, likewise) and of csrc/robogym_actor_unroll.hip (rg_actor_unroll's, likewise).
+    (rg_episodes_append's, likewise) and of csrc/robogym_actor_unroll.hip (rg_actor_unroll's, likewise).  csrc/robogym_td_targets.hip
+    is NOT part of it -- its host half runs under the sanitizers in a stand-alone program (tests/test_td_targets_host_sanitized.py);
+    tests/sanitize/td_targets_absent.cpp only exports its entry points, so that the library declares what the header declares.
     Used by tests/test_sanitizers.py for the no-GPU cases of tests/test_host.py; never shipped.  (GPU ASan is
     not available on this pool: sanitizers run on the CPU build only.)"""
     out = out or os.path.join(HERE, "build", "librobogym_capi_asan.so")
@@ -177,7 +180,7 @@ def build_host_sanitized(out=None):
            "-DRG_EPISODES_HOST_ONLY", "-DRG_UNROLL_HOST_ONLY", "-I", CSRC, os.path.join(CSRC, "robogym_capi.hip"),
            os.path.join(CSRC, "robogym_render.hip"), os.path.join(CSRC, "robogym_episodes.hip"),
            os.path.join(CSRC, "robogym_actor_unroll.hip"), stubs, stubs_sample,
-           "-o", out]
+           os.path.join(HERE, "..", "tests", "sanitize", "td_targets_absent.cpp"), "-o", out]
     subprocess.check_call(cmd)
     return out
 

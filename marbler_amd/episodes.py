@@ -237,6 +237,49 @@ class EpisodeBuffer(object):
         q, greedy = actor.unroll(self.obs[idx][:, :rows], append_agent_id=obs_agent_id)   # (the gathered copy is read in place)
         return {"q": q, "greedy": greedy}
 
+    def td_targets(self, target_actor, mixer, greedy=None, slots=None, trim=False, gamma=0.99, obs_agent_id=True):
+        """Everything a Q-learner computes under detach() for batch(slots, trim), in two launches: `target_actor` (a BatchedActor)
+        unrolled over the selected episodes (BatchedActor.unroll), then the episode mask, the double-Q gather, `mixer` (a
+        targets.TargetMixer) and reward + gamma (1 - terminated) mixed (targets.td_targets; the rule: csrc/td_targets.h), both on
+        ONE gathered copy of the slots' observations.  greedy: unroll(online_actor)["greedy"] over the same slots and trim, which
+        is double-Q; None: the target network's own maximum.  Returns targets [B, rows - 1, 1] (a `none` mixer:
+        [B, rows - 1, N]), mask [B, rows - 1, 1] and agent_q [B, rows - 1, N] over the rows of batch(slots, trim)[:, :-1].
+        ValueError for an actor, a mixer or a `greedy` that does not fit the buffer or that a launch refuses."""
+        import torch
+        from . import targets
+        if not isinstance(mixer, targets.TargetMixer):
+            raise ValueError(f"mixer must be a TargetMixer, got {type(mixer).__name__}")
+        for name, have, want in (("actor's n_agents", getattr(target_actor, "n_agents", None), self.N),
+                                 ("actor's n_actions", getattr(target_actor, "n_actions", None), self.A),
+                                 ("actor's input_dim", getattr(target_actor, "input_dim", None), self.D + (self.N if obs_agent_id else 0)),
+                                 ("mixer's n_agents", mixer.n_agents, self.N)):
+            if have != want:
+                raise ValueError(f"the {name} is {have}, the buffer's episodes need {want}")
+        if mixer.kind == "qmix" and mixer.state_dim != self.N * self.D:
+            raise ValueError(f"the mixer's state_dim is {mixer.state_dim}, the buffer's episodes need {self.N * self.D}")
+        if target_actor.w1.device != self.device:
+            raise ValueError(f"the actor is on {target_actor.w1.device}, the buffer on {self.device}")
+        if mixer.device != self.device:
+            raise ValueError(f"the mixer is on {mixer.device}, the buffer on {self.device}")
+        idx = self._slots(slots)
+        B = int(idx.numel())
+        rows = self.L + 1
+        if trim and B > 0:
+            rows = max(int(self.length[idx].max()) + 1, 2)
+        if greedy is not None and (not isinstance(greedy, torch.Tensor) or greedy.dtype != torch.int32
+                                   or tuple(greedy.shape) != (B, rows, self.N)):
+            raise ValueError(f"greedy must be an int32 tensor {(B, rows, self.N)}: unroll(online_actor)['greedy'] of the same slots and trim")
+        if B == 0:
+            t_shape = (0, rows - 1, self.N if mixer.kind == "none" else 1)
+            return {"targets": torch.empty(t_shape, device=self.device), "mask": torch.empty(0, rows - 1, 1, device=self.device),
+                    "agent_q": torch.empty(0, rows - 1, self.N, device=self.device)}
+        obs = self.obs[idx][:, :rows]                             # the one gathered copy both launches read in place
+        qt, _ = target_actor.unroll(obs, append_agent_id=obs_agent_id)
+        out = targets.td_targets(qt, obs, self.reward[idx][:, :rows], self.terminated[idx][:, :rows], self.filled[idx][:, :rows],
+                                 mixer, gamma, sel=greedy)
+        return {"targets": out["targets"] if mixer.kind == "none" else out["targets"].unsqueeze(-1),
+                "mask": out["mask"].unsqueeze(-1), "agent_q": out["agent_q"]}
+
     def sample(self, n, generator=None):
         """n slots drawn uniformly, without replacement, among the complete ones (int64); ValueError if fewer are complete."""
         import torch
