@@ -180,23 +180,52 @@ def reference_shapes():
     return out
 
 
-EXPORTS = ("rg_abi_version", "rg_last_error", "rg_sizeof_params", "rg_sizeof_state", "rg_sizeof_step_io", "rg_next_init_stride",
-           "rg_create", "rg_destroy", "rg_bind_state", "rg_set_stream", "rg_reset", "rg_step", "rg_rollout", "rg_get_obs", "rg_step_kernel",
-           "rg_actor_forward", "rg_actor_forward_explore", "rg_actor_pack_gru", "rg_actor_pack_gru_bf16x3", "rg_actor_pack_gru_f16x2", "rg_actor_last_error",
-           "rg_sizeof_policy_io", "rg_policy_rollout", "rg_sizeof_lidar_params", "rg_set_lidar",
-           "rg_sizeof_team_params", "rg_set_teams",
-           "rg_actor_forward_sample", "rg_sizeof_policy_sample", "rg_policy_rollout_sample",
-           "rg_sizeof_disturbance_params", "rg_set_disturbance", "rg_step_form", "rg_shape_match", "rg_shape_info",
-           "rg_sizeof_render_params", "rg_render", "rg_render_last_error",
-           "rg_sizeof_episode_buffer", "rg_sizeof_episode_stream", "rg_episodes_append", "rg_episodes_last_error",
-           "rg_sizeof_actor_unroll_io", "rg_actor_unroll", "rg_actor_unroll_last_error",
-           "rg_sizeof_mixer_weights", "rg_sizeof_td_targets_io", "rg_td_targets", "rg_td_targets_last_error")
-# the queries a library of an earlier build lacks: tolerated in one loaded through ROBOGYM_LIB (an A/B run against it), never in
-# the package's own
-LATE_QUERIES = ("rg_step_form", "rg_shape_match", "rg_shape_info", "rg_sizeof_render_params", "rg_render", "rg_render_last_error",
-                "rg_sizeof_episode_buffer", "rg_sizeof_episode_stream", "rg_episodes_append", "rg_episodes_last_error",
-                "rg_sizeof_actor_unroll_io", "rg_actor_unroll", "rg_actor_unroll_last_error",
-                "rg_sizeof_mixer_weights", "rg_sizeof_td_targets_io", "rg_td_targets", "rg_td_targets_last_error")
+_P, _INT, _STR, _VP, _I32, _U64 = C.POINTER, C.c_int, C.c_char_p, C.c_void_p, C.c_int32, C.c_uint64
+_ACTOR_STEP = [_P(RgActorWeights), _I32, _I32, _VP, _I32, _I32, _VP, _VP, _VP, _VP]      # what the three rg_actor_forward* share
+_PACK = [_VP, _I32, _I32, _VP, _VP]
+LATE = True
+# every entry of include/robogym.h: (name, restype, argtypes or None for "takes nothing", late).  A late entry is one a library
+# of an earlier build lacks: tolerated in one loaded through ROBOGYM_LIB (an A/B run against it), never in the package's own
+ENTRIES = (
+    ("rg_abi_version", _INT, None, False), ("rg_last_error", _STR, None, False),
+    ("rg_sizeof_params", _INT, None, False), ("rg_sizeof_state", _INT, None, False), ("rg_sizeof_step_io", _INT, None, False),
+    ("rg_next_init_stride", _INT, [_P(RgScenarioParams)], False),
+    ("rg_create", _VP, [_P(RgScenarioParams), _I32, C.c_int64, _I32, _VP], False), ("rg_destroy", _INT, [_VP], False),
+    ("rg_bind_state", _INT, [_VP, _P(RgState)], False), ("rg_set_stream", _INT, [_VP, _VP], False),
+    ("rg_reset", _INT, [_VP, _VP, _U64, _I32], False), ("rg_step", _INT, [_VP, _VP, _P(RgStepIO), _I32, _U64], False),
+    ("rg_rollout", _INT, [_VP, _VP, _I32, _P(RgStepIO), _I32, _U64], False), ("rg_get_obs", _INT, [_VP, _VP], False),
+    ("rg_step_kernel", _INT, [_VP], False),
+    ("rg_actor_forward", _INT, _ACTOR_STEP + [_VP], False),
+    ("rg_actor_forward_explore", _INT, _ACTOR_STEP + [_VP, C.c_float, _VP], False),
+    ("rg_actor_pack_gru", _INT, _PACK, False), ("rg_actor_pack_gru_bf16x3", _INT, _PACK, False),
+    ("rg_actor_pack_gru_f16x2", _INT, _PACK, False), ("rg_actor_last_error", _STR, None, False),
+    ("rg_sizeof_policy_io", _INT, None, False),
+    ("rg_policy_rollout", _INT, [_VP, _P(RgActorWeights), _I32, _P(RgPolicyIO), _P(RgStepIO), _I32, _U64], False),
+    ("rg_sizeof_lidar_params", _INT, None, False), ("rg_set_lidar", _INT, [_VP, _P(RgLidarParams)], False),
+    ("rg_sizeof_team_params", _INT, None, False), ("rg_set_teams", _INT, [_VP, _P(RgTeamParams)], False),
+    ("rg_actor_forward_sample", _INT, _ACTOR_STEP + [_VP, _VP, _VP], False), ("rg_sizeof_policy_sample", _INT, None, False),
+    ("rg_policy_rollout_sample", _INT, [_VP, _P(RgActorWeights), _I32, _P(RgPolicyIO), _P(RgPolicySample), _P(RgStepIO), _I32, _U64], False),
+    ("rg_sizeof_disturbance_params", _INT, None, False), ("rg_set_disturbance", _INT, [_VP, _P(RgDisturbanceParams)], False),
+    ("rg_step_form", _INT, [_VP], LATE), ("rg_shape_match", _INT, [_P(RgScenarioParams)], LATE),
+    ("rg_shape_info", _INT, [_I32, _P(_I32 * 10)], LATE),
+    ("rg_sizeof_render_params", _INT, None, LATE),
+    ("rg_render", _INT, [_P(RgScenarioParams), _P(RgState), _I32, _P(RgRenderParams), _VP, _VP], LATE),
+    ("rg_render_last_error", _STR, None, LATE),
+    ("rg_sizeof_episode_buffer", _INT, None, LATE), ("rg_sizeof_episode_stream", _INT, None, LATE),
+    ("rg_episodes_append", _INT, [_P(RgEpisodeBuffer), _P(RgEpisodeStream), _VP], LATE), ("rg_episodes_last_error", _STR, None, LATE),
+    ("rg_sizeof_actor_unroll_io", _INT, None, LATE),
+    ("rg_actor_unroll", _INT, [_P(RgActorWeights), _P(RgActorUnrollIO), _VP], LATE), ("rg_actor_unroll_last_error", _STR, None, LATE),
+    ("rg_sizeof_mixer_weights", _INT, None, LATE), ("rg_sizeof_td_targets_io", _INT, None, LATE),
+    ("rg_td_targets", _INT, [_P(RgMixerWeights), _P(RgTdTargetsIO), _VP], LATE), ("rg_td_targets_last_error", _STR, None, LATE))
+EXPORTS = tuple(e[0] for e in ENTRIES)
+LATE_QUERIES = tuple(e[0] for e in ENTRIES if e[3])
+# the layout check: (sizeof query, the ctypes struct it must agree with)
+LAYOUTS = (("rg_sizeof_params", RgScenarioParams), ("rg_sizeof_state", RgState), ("rg_sizeof_step_io", RgStepIO),
+           ("rg_sizeof_policy_io", RgPolicyIO), ("rg_sizeof_policy_sample", RgPolicySample), ("rg_sizeof_lidar_params", RgLidarParams),
+           ("rg_sizeof_team_params", RgTeamParams), ("rg_sizeof_disturbance_params", RgDisturbanceParams),
+           ("rg_sizeof_render_params", RgRenderParams), ("rg_sizeof_episode_buffer", RgEpisodeBuffer),
+           ("rg_sizeof_episode_stream", RgEpisodeStream), ("rg_sizeof_actor_unroll_io", RgActorUnrollIO),
+           ("rg_sizeof_mixer_weights", RgMixerWeights), ("rg_sizeof_td_targets_io", RgTdTargetsIO))
 
 _lib = None
 
@@ -215,106 +244,21 @@ def load():
             f"{LIB_PATH} not found: build it with `python -m marbler_amd.build` (hipcc, gfx950). "
             "marbler_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name in EXPORTS:
+    for name, restype, argtypes, late in ENTRIES:
         if not hasattr(lib, name):
-            if name in LATE_QUERIES and os.environ.get("ROBOGYM_LIB"):
+            if late and os.environ.get("ROBOGYM_LIB"):
                 continue
             raise RobogymError(f"{LIB_PATH} does not export {name}")
-    lib.rg_abi_version.restype = C.c_int
-    lib.rg_last_error.restype = C.c_char_p
-    lib.rg_create.restype = C.c_void_p
-    lib.rg_create.argtypes = [C.POINTER(RgScenarioParams), C.c_int32, C.c_int64, C.c_int32, C.c_void_p]
-    lib.rg_next_init_stride.argtypes = [C.POINTER(RgScenarioParams)]
-    lib.rg_next_init_stride.restype = C.c_int
-    lib.rg_destroy.argtypes = [C.c_void_p]
-    lib.rg_bind_state.argtypes = [C.c_void_p, C.POINTER(RgState)]
-    lib.rg_set_stream.argtypes = [C.c_void_p, C.c_void_p]
-    lib.rg_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32]
-    lib.rg_step.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(RgStepIO), C.c_int32, C.c_uint64]
-    lib.rg_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(RgStepIO), C.c_int32, C.c_uint64]
-    lib.rg_get_obs.argtypes = [C.c_void_p, C.c_void_p]
-    lib.rg_step_kernel.argtypes = [C.c_void_p]
-    lib.rg_step_kernel.restype = C.c_int
-    if hasattr(lib, "rg_step_form"):   # (LATE_QUERIES)
-        lib.rg_step_form.argtypes = [C.c_void_p]
-        lib.rg_step_form.restype = C.c_int
-        lib.rg_shape_match.argtypes = [C.POINTER(RgScenarioParams)]
-        lib.rg_shape_match.restype = C.c_int
-        lib.rg_shape_info.argtypes = [C.c_int32, C.POINTER(C.c_int32 * 10)]
-        lib.rg_shape_info.restype = C.c_int
-    lib.rg_actor_forward.argtypes = [C.POINTER(RgActorWeights), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rg_actor_forward.restype = C.c_int
-    lib.rg_actor_forward_explore.argtypes = [C.POINTER(RgActorWeights), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
-    lib.rg_actor_forward_explore.restype = C.c_int
-    lib.rg_actor_forward_sample.argtypes = [C.POINTER(RgActorWeights), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rg_actor_forward_sample.restype = C.c_int
-    lib.rg_actor_pack_gru.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.rg_actor_pack_gru.restype = C.c_int
-    lib.rg_actor_pack_gru_bf16x3.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.rg_actor_pack_gru_bf16x3.restype = C.c_int
-    lib.rg_actor_pack_gru_f16x2.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.rg_actor_pack_gru_f16x2.restype = C.c_int
-    lib.rg_actor_last_error.restype = C.c_char_p
-    lib.rg_policy_rollout.argtypes = [C.c_void_p, C.POINTER(RgActorWeights), C.c_int32, C.POINTER(RgPolicyIO), C.POINTER(RgStepIO),
-                                      C.c_int32, C.c_uint64]
-    lib.rg_policy_rollout.restype = C.c_int
-    lib.rg_sizeof_policy_io.restype = C.c_int
-    lib.rg_policy_rollout_sample.argtypes = [C.c_void_p, C.POINTER(RgActorWeights), C.c_int32, C.POINTER(RgPolicyIO),
-                                             C.POINTER(RgPolicySample), C.POINTER(RgStepIO), C.c_int32, C.c_uint64]
-    lib.rg_policy_rollout_sample.restype = C.c_int
-    lib.rg_sizeof_policy_sample.restype = C.c_int
-    lib.rg_set_lidar.argtypes = [C.c_void_p, C.POINTER(RgLidarParams)]
-    lib.rg_set_lidar.restype = C.c_int
-    lib.rg_sizeof_lidar_params.restype = C.c_int
-    lib.rg_set_teams.argtypes = [C.c_void_p, C.POINTER(RgTeamParams)]
-    lib.rg_set_teams.restype = C.c_int
-    lib.rg_sizeof_team_params.restype = C.c_int
-    lib.rg_set_disturbance.argtypes = [C.c_void_p, C.POINTER(RgDisturbanceParams)]
-    lib.rg_set_disturbance.restype = C.c_int
-    lib.rg_sizeof_disturbance_params.restype = C.c_int
-    if hasattr(lib, "rg_render"):   # (LATE_QUERIES)
-        lib.rg_render.argtypes = [C.POINTER(RgScenarioParams), C.POINTER(RgState), C.c_int32, C.POINTER(RgRenderParams), C.c_void_p,
-                                  C.c_void_p]
-        lib.rg_render.restype = C.c_int
-        lib.rg_render_last_error.restype = C.c_char_p
-        lib.rg_sizeof_render_params.restype = C.c_int
-    if hasattr(lib, "rg_episodes_append"):   # (LATE_QUERIES)
-        lib.rg_episodes_append.argtypes = [C.POINTER(RgEpisodeBuffer), C.POINTER(RgEpisodeStream), C.c_void_p]
-        lib.rg_episodes_append.restype = C.c_int
-        lib.rg_episodes_last_error.restype = C.c_char_p
-        lib.rg_sizeof_episode_buffer.restype = C.c_int
-        lib.rg_sizeof_episode_stream.restype = C.c_int
-    if hasattr(lib, "rg_actor_unroll"):   # (LATE_QUERIES)
-        lib.rg_actor_unroll.argtypes = [C.POINTER(RgActorWeights), C.POINTER(RgActorUnrollIO), C.c_void_p]
-        lib.rg_actor_unroll.restype = C.c_int
-        lib.rg_actor_unroll_last_error.restype = C.c_char_p
-        lib.rg_sizeof_actor_unroll_io.restype = C.c_int
-    if hasattr(lib, "rg_td_targets"):   # (LATE_QUERIES)
-        lib.rg_td_targets.argtypes = [C.POINTER(RgMixerWeights), C.POINTER(RgTdTargetsIO), C.c_void_p]
-        lib.rg_td_targets.restype = C.c_int
-        lib.rg_td_targets_last_error.restype = C.c_char_p
-        lib.rg_sizeof_mixer_weights.restype = C.c_int
-        lib.rg_sizeof_td_targets_io.restype = C.c_int
-    for f in (lib.rg_destroy, lib.rg_bind_state, lib.rg_set_stream, lib.rg_reset, lib.rg_step, lib.rg_rollout, lib.rg_get_obs,
-              lib.rg_sizeof_params, lib.rg_sizeof_state, lib.rg_sizeof_step_io):
-        f.restype = C.c_int
+        f = getattr(lib, name)
+        f.restype = restype
+        if argtypes is not None:
+            f.argtypes = argtypes
     if lib.rg_abi_version() != ABI_VERSION:
         raise RobogymError(f"ABI version {lib.rg_abi_version()} != {ABI_VERSION}; rebuild the library")
-    if (lib.rg_sizeof_params() != C.sizeof(RgScenarioParams) or lib.rg_sizeof_state() != C.sizeof(RgState)
-            or lib.rg_sizeof_step_io() != C.sizeof(RgStepIO) or lib.rg_sizeof_policy_io() != C.sizeof(RgPolicyIO)
-            or lib.rg_sizeof_policy_sample() != C.sizeof(RgPolicySample)
-            or lib.rg_sizeof_lidar_params() != C.sizeof(RgLidarParams) or lib.rg_sizeof_team_params() != C.sizeof(RgTeamParams)
-            or lib.rg_sizeof_disturbance_params() != C.sizeof(RgDisturbanceParams)
-            or (hasattr(lib, "rg_render") and lib.rg_sizeof_render_params() != C.sizeof(RgRenderParams))
-            or (hasattr(lib, "rg_episodes_append") and (lib.rg_sizeof_episode_buffer() != C.sizeof(RgEpisodeBuffer)
-                                                        or lib.rg_sizeof_episode_stream() != C.sizeof(RgEpisodeStream)))
-            or (hasattr(lib, "rg_actor_unroll") and lib.rg_sizeof_actor_unroll_io() != C.sizeof(RgActorUnrollIO))
-            or (hasattr(lib, "rg_td_targets") and (lib.rg_sizeof_mixer_weights() != C.sizeof(RgMixerWeights)
-                                                   or lib.rg_sizeof_td_targets_io() != C.sizeof(RgTdTargetsIO)))):
-        raise RobogymError("struct layout of the binding differs from the compiled library; rebuild")
+    for query, struct in LAYOUTS:
+        if hasattr(lib, query) and getattr(lib, query)() != C.sizeof(struct):
+            raise RobogymError(f"struct layout of the binding differs from the compiled library; rebuild ({struct.__name__} is "
+                               f"{C.sizeof(struct)} bytes here, {query}() says {getattr(lib, query)()})")
     _lib = lib
     return lib
 

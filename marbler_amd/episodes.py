@@ -13,7 +13,9 @@ HIP device.
 """
 import ctypes as C
 
-from . import _lib
+import torch
+
+from . import _args, _lib
 
 # name -> (dtype name, shape as a function of (E, R, L, N, D)); `prob` only with with_prob
 ARRAYS = {"obs": ("float32", lambda E, R, L, N, D: (E * R, L + 1, N, D)),
@@ -31,21 +33,6 @@ ARRAYS = {"obs": ("float32", lambda E, R, L, N, D: (E * R, L + 1, N, D)),
 INT32_MAX = 2 ** 31 - 1
 
 
-def _check_tensor(name, t, dtypes, shape, device=None):
-    import torch
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch tensor, got {type(t).__name__}")
-    if t.dtype not in dtypes:
-        raise ValueError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} must have the shape {tuple(shape)}, got {tuple(t.shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
-    if device is not None and t.device != device:
-        raise ValueError(f"{name} is on {t.device}, the buffer on {device}")
-    return t
-
-
 class EpisodeBuffer(object):
     """E x slots_per_env episode slots of episode_limit + 1 rows on `device`; all storage is allocated here, zero-filled, and
     nothing is allocated afterwards by append().  Slot e * slots_per_env + r is env e's r-th ring entry: an env's episodes go
@@ -54,7 +41,6 @@ class EpisodeBuffer(object):
 
     def __init__(self, num_envs, n_agents, obs_dim, n_actions, episode_limit, slots_per_env=2, with_prob=False, device="cuda:0",
                  storage=None):
-        import torch
         dims = {"num_envs": num_envs, "n_agents": n_agents, "obs_dim": obs_dim, "n_actions": n_actions,
                 "episode_limit": episode_limit, "slots_per_env": slots_per_env}
         for k, v in dims.items():
@@ -77,7 +63,7 @@ class EpisodeBuffer(object):
         elif set(storage) != set(self.names):
             raise ValueError(f"storage must hold exactly {self.names}, got {tuple(storage)}")
         for k in self.names:
-            _check_tensor(f"storage[{k!r}]", storage[k], (getattr(torch, ARRAYS[k][0]),), ARRAYS[k][1](*shape_args), self.device)
+            _args.check_tensor(f"storage[{k!r}]", storage[k], (getattr(torch, ARRAYS[k][0]),), ARRAYS[k][1](*shape_args), self.device)
             setattr(self, k, storage[k])
         if not self.with_prob:
             self.prob = None
@@ -114,7 +100,6 @@ class EpisodeBuffer(object):
 
     def check_stream(self, batch):
         """batch: run()'s dict.  Checks names, dtypes, shapes, contiguity and devices; returns T.  Touches no device."""
-        import torch
         if not isinstance(batch, dict):
             raise TypeError("batch must be the dict BatchedRunner.run returns")
         need = ("obs", "actions", "reward", "terminated", "episode_start")
@@ -130,20 +115,17 @@ class EpisodeBuffer(object):
         T = int(batch["actions"].shape[0])
         if (T + 1) * self.E * self.N * self.D > INT32_MAX:
             raise ValueError("(T + 1) * num_envs * n_agents * obs_dim exceeds 2^31 - 1 elements")
-        flags = (torch.bool, torch.uint8)
-        _check_tensor("batch['obs']", batch["obs"], (torch.float32,), (T + 1, self.E, self.N, self.D), self.device)
-        _check_tensor("batch['actions']", batch["actions"], (torch.int32,), (T, self.E, self.N), self.device)
-        _check_tensor("batch['reward']", batch["reward"], (torch.float32,), (T, self.E), self.device)
-        _check_tensor("batch['terminated']", batch["terminated"], flags, (T, self.E), self.device)
-        _check_tensor("batch['episode_start']", batch["episode_start"], flags, (T, self.E), self.device)
-        if self.with_prob:
-            _check_tensor("batch['prob']", batch["prob"], (torch.float32,), (T, self.E, self.N), self.device)
+        f32, flags = (torch.float32,), (torch.bool, torch.uint8)
+        for k, dtypes, shape in (("obs", f32, (T + 1, self.E, self.N, self.D)), ("actions", (torch.int32,), (T, self.E, self.N)),
+                                 ("reward", f32, (T, self.E)), ("terminated", flags, (T, self.E)), ("episode_start", flags, (T, self.E)),
+                                 ("prob", f32, (T, self.E, self.N))):
+            if k != "prob" or self.with_prob:
+                _args.check_tensor(f"batch[{k!r}]", batch[k], dtypes, shape, self.device)
         return T
 
     def append(self, batch, stream=None):
         """Cut run()'s dict into the slots: one launch on `stream` (a torch stream; None: the current one), no host
         synchronisation, nothing allocated -- safe inside a torch.cuda.graph capture.  Returns nothing."""
-        import torch
         T = self.check_stream(batch)
         if self.device.type != "cuda":
             raise ValueError(f"the buffer lives on {self.device}: append() runs on a HIP device and has no host path")
@@ -152,21 +134,18 @@ class EpisodeBuffer(object):
                                  batch["terminated"].data_ptr(), batch["episode_start"].data_ptr(),
                                  batch["prob"].data_ptr() if self.with_prob else None, T, 0)
         with torch.cuda.device(self.device):
-            hip_stream = (torch.cuda.current_stream(self.device) if stream is None else stream).cuda_stream
-            rc = lib.rg_episodes_append(C.byref(self._c_buffer), C.byref(s), C.c_void_p(hip_stream))
+            rc = lib.rg_episodes_append(C.byref(self._c_buffer), C.byref(s), _args.launch_stream(stream, self.device)[1])
         if rc != 0:
-            raise _lib.RobogymError(f"rg_episodes_append failed ({rc}): {lib.rg_episodes_last_error().decode()}")
+            raise _args.launch_error(rc, "rg_episodes_append: " + lib.rg_episodes_last_error().decode(), refuses=False)
 
     # -- reading
     def take_new(self):
         """The slots completed since the last call: int64, ascending.  Clears `fresh`."""
-        import torch
         new = torch.nonzero(self.fresh).flatten()
         self.fresh.zero_()
         return new
 
     def _slots(self, slots):
-        import torch
         if slots is None:
             return torch.nonzero(self.complete).flatten()
         if isinstance(slots, torch.Tensor):
@@ -188,19 +167,40 @@ class EpisodeBuffer(object):
             raise ValueError(f"slots {bad[:4]} outside [0, {self.num_slots})")
         return torch.tensor(host, dtype=torch.int64).to(self.device)
 
+    def _select(self, slots, trim, min_rows):
+        """(idx, B, rows, length) of a read of `slots`: their indices, how many, and the rows of the time axis -- L + 1, or under
+        `trim` those of the longest episode selected (one host read), at least `min_rows`.  length: the slots' lengths where
+        trimming gathered them, else None (only batch() returns them: nothing is gathered twice, or for nobody)."""
+        idx = self._slots(slots)
+        B, rows, length = int(idx.numel()), self.L + 1, None
+        if trim and B > 0:
+            length = self.length[idx]
+            rows = max(int(length.max()) + 1, min_rows)
+        return idx, B, rows, length
+
+    def _check_fits(self, actor, obs_agent_id, mixer=None):
+        """ValueError unless `actor` (a BatchedActor) and `mixer` (a targets.TargetMixer, if given) fit this buffer's episodes."""
+        fits = [("actor's n_agents", getattr(actor, "n_agents", None), self.N), ("actor's n_actions", getattr(actor, "n_actions", None), self.A),
+                ("actor's input_dim", getattr(actor, "input_dim", None), self.D + (self.N if obs_agent_id else 0))]
+        if mixer is not None:
+            fits.append(("mixer's n_agents", mixer.n_agents, self.N))
+            if mixer.kind == "qmix":
+                fits.append(("mixer's state_dim", mixer.state_dim, self.N * self.D))
+        for name, have, want in fits:
+            if have != want:
+                raise ValueError(f"the {name} is {have}, the buffer's episodes need {want}")
+        if actor.w1.device != self.device:
+            raise ValueError(f"the actor is on {actor.w1.device}, the buffer on {self.device}")
+        if mixer is not None and mixer.device != self.device:
+            raise ValueError(f"the mixer is on {mixer.device}, the buffer on {self.device}")
+
     def batch(self, slots=None, trim=False):
         """EPyMARL's episode batch of `slots` (None: every complete slot, ascending), B episodes: obs [B, L + 1, N, D], state
         [B, L + 1, N D] (gymma's state is the concatenated observations), actions [B, L + 1, N, 1] int64, avail_actions
         [B, L + 1, N, A] int32 ones, reward [B, L + 1, 1], terminated [B, L + 1, 1] uint8, filled [B, L + 1, 1] int64, probs
         [B, L + 1, N] (a buffer with_prob), length [B] int32, episode_return [B].  trim: the time axis is cut to the longest
         episode selected, max(length) + 1 rows (one host read)."""
-        import torch
-        idx = self._slots(slots)
-        B = int(idx.numel())
-        rows = self.L + 1
-        length = self.length[idx]
-        if trim and B > 0:
-            rows = int(length.max()) + 1
+        idx, B, rows, length = self._select(slots, trim, 1)
         obs = self.obs[idx, :rows]
         out = {"obs": obs, "state": obs.reshape(B, rows, self.N * self.D),
                "actions": self.actions[idx, :rows].to(torch.int64).unsqueeze(-1),
@@ -208,7 +208,7 @@ class EpisodeBuffer(object):
                "reward": self.reward[idx, :rows].unsqueeze(-1),
                "terminated": self.terminated[idx, :rows].unsqueeze(-1),
                "filled": self.filled[idx, :rows].to(torch.int64).unsqueeze(-1),
-               "length": length, "episode_return": self.episode_return[idx]}
+               "length": self.length[idx] if length is None else length, "episode_return": self.episode_return[idx]}
         if self.with_prob:
             out["probs"] = self.prob[idx, :rows]
         return out
@@ -219,18 +219,8 @@ class EpisodeBuffer(object):
         and greedy [B, rows, N] int32 over the same rows as batch(slots, trim).  Every row is computed, the padding behind an
         episode's end included (there are no masks: `filled` says which rows are data); q of the taken action and max q stay
         torch.gather / max on q.  ValueError for an actor that does not fit the buffer or that the launch refuses."""
-        import torch
-        for name, have, want in (("n_agents", getattr(actor, "n_agents", None), self.N), ("n_actions", getattr(actor, "n_actions", None), self.A),
-                                 ("input_dim", getattr(actor, "input_dim", None), self.D + (self.N if obs_agent_id else 0))):
-            if have != want:
-                raise ValueError(f"the actor's {name} is {have}, the buffer's episodes need {want}")
-        if actor.w1.device != self.device:
-            raise ValueError(f"the actor is on {actor.w1.device}, the buffer on {self.device}")
-        idx = self._slots(slots)
-        B = int(idx.numel())
-        rows = self.L + 1
-        if trim and B > 0:
-            rows = int(self.length[idx].max()) + 1
+        self._check_fits(actor, obs_agent_id)
+        idx, B, rows, _ = self._select(slots, trim, 1)
         if B == 0:
             return {"q": torch.empty(0, rows, self.N, self.A, device=self.device),
                     "greedy": torch.empty(0, rows, self.N, dtype=torch.int32, device=self.device)}
@@ -245,30 +235,13 @@ class EpisodeBuffer(object):
         is double-Q; None: the target network's own maximum.  Returns targets [B, rows - 1, 1] (a `none` mixer:
         [B, rows - 1, N]), mask [B, rows - 1, 1] and agent_q [B, rows - 1, N] over the rows of batch(slots, trim)[:, :-1].
         ValueError for an actor, a mixer or a `greedy` that does not fit the buffer or that a launch refuses."""
-        import torch
         from . import targets
         if not isinstance(mixer, targets.TargetMixer):
             raise ValueError(f"mixer must be a TargetMixer, got {type(mixer).__name__}")
-        for name, have, want in (("actor's n_agents", getattr(target_actor, "n_agents", None), self.N),
-                                 ("actor's n_actions", getattr(target_actor, "n_actions", None), self.A),
-                                 ("actor's input_dim", getattr(target_actor, "input_dim", None), self.D + (self.N if obs_agent_id else 0)),
-                                 ("mixer's n_agents", mixer.n_agents, self.N)):
-            if have != want:
-                raise ValueError(f"the {name} is {have}, the buffer's episodes need {want}")
-        if mixer.kind == "qmix" and mixer.state_dim != self.N * self.D:
-            raise ValueError(f"the mixer's state_dim is {mixer.state_dim}, the buffer's episodes need {self.N * self.D}")
-        if target_actor.w1.device != self.device:
-            raise ValueError(f"the actor is on {target_actor.w1.device}, the buffer on {self.device}")
-        if mixer.device != self.device:
-            raise ValueError(f"the mixer is on {mixer.device}, the buffer on {self.device}")
-        idx = self._slots(slots)
-        B = int(idx.numel())
-        rows = self.L + 1
-        if trim and B > 0:
-            rows = max(int(self.length[idx].max()) + 1, 2)
-        if greedy is not None and (not isinstance(greedy, torch.Tensor) or greedy.dtype != torch.int32
-                                   or tuple(greedy.shape) != (B, rows, self.N)):
-            raise ValueError(f"greedy must be an int32 tensor {(B, rows, self.N)}: unroll(online_actor)['greedy'] of the same slots and trim")
+        self._check_fits(target_actor, obs_agent_id, mixer)
+        idx, B, rows, _ = self._select(slots, trim, 2)
+        if greedy is not None:      # (unroll(online_actor)["greedy"] of the same slots and trim has this shape)
+            _args.check_tensor("greedy", greedy, (torch.int32,), (B, rows, self.N), contiguous=False, errors=_args.VALUE)
         if B == 0:
             t_shape = (0, rows - 1, self.N if mixer.kind == "none" else 1)
             return {"targets": torch.empty(t_shape, device=self.device), "mask": torch.empty(0, rows - 1, 1, device=self.device),
@@ -282,7 +255,6 @@ class EpisodeBuffer(object):
 
     def sample(self, n, generator=None):
         """n slots drawn uniformly, without replacement, among the complete ones (int64); ValueError if fewer are complete."""
-        import torch
         if isinstance(n, bool) or not isinstance(n, int) or n < 1:
             raise ValueError(f"sample(n) draws n >= 1 slots, got {n!r}")
         if n > self.num_slots:
@@ -300,13 +272,11 @@ class EpisodeBuffer(object):
     # -- checkpoints
     def state_dict(self):
         """Every array, cursors included (an open episode goes on after load_state_dict), as a plain dict of tensor copies."""
-        import torch
         out = {k: getattr(self, k).clone() for k in self.names}
         out["dims"] = torch.tensor([self.E, self.R, self.L, self.N, self.D, self.A], dtype=torch.int64)
         return out
 
     def load_state_dict(self, state):
-        import torch
         want = torch.tensor([self.E, self.R, self.L, self.N, self.D, self.A], dtype=torch.int64)
         if "dims" not in state or not torch.equal(state["dims"].cpu().to(torch.int64), want):
             raise ValueError(f"the checkpoint's dims {state.get('dims')} differ from this buffer's {want.tolist()} (E, R, L, N, D, A)")

@@ -10,9 +10,12 @@ actions are the arg-max Q (misc.py:170), and the episode statistics accumulate i
 on-device counters.  `load_actor` reads the reference's model zoo (`scenarios/*/models/*.th`
 state dicts + sacred `.json` configs, misc.py:65-91) unchanged.
 """
+import ctypes as C
 import json
 
 import torch
+
+from . import _args, _lib
 
 
 DEFAULT_PACK_GRU = "f16x2"   # what pack_gru=True means
@@ -80,8 +83,6 @@ class BatchedActor(object):
         return (self.w1.is_cuda and self.hidden_dim in (64, 128) and self.n_actions <= 32 and self.input_dim <= 64)
 
     def _weights_struct(self):
-        import ctypes as C
-        from . import _lib
         if getattr(self, "_ws", None) is None:
             t = {k: getattr(self, k).contiguous() for k in ("w1", "b1", "w2", "b2")}
             packed = 0
@@ -104,7 +105,7 @@ class BatchedActor(object):
                         raise _lib.RobogymError("rg_actor_pack_gru: " + lib.rg_actor_last_error().decode())
                     t[k] = dst
                 packed = {"bf16x3": 2, "f16x2": 3}.get(self.pack_gru, 1)
-                # a first launch on ANOTHER stream must not overtake the two pack kernels (forward_fused waits on this once)
+                # a first launch on ANOTHER stream must not overtake the two pack kernels (weights_for orders every launch behind this)
                 self._pack_done = torch.cuda.Event()
                 self._pack_done.record(torch.cuda.current_stream(self.w1.device))
             if not self.use_rnn:
@@ -116,6 +117,18 @@ class BatchedActor(object):
                                            self.n_actions, 1 if self.use_rnn else 0, packed)
         return self._ws
 
+    def weights_for(self, stream):
+        """The weights struct for a launch on `stream` (a torch stream).  The weights were packed (once) on the then-current
+        stream: until that has finished, a launch on any stream is ordered behind it here."""
+        ws = self._weights_struct()
+        ev = getattr(self, "_pack_done", None)
+        if ev is not None:
+            if ev.query():
+                self._pack_done = None
+            else:
+                stream.wait_event(ev)
+        return ws
+
     def forward_fused(self, obs, hidden, append_agent_id=True, restart=None, q_out=None, actions_out=None, stream=None,
                       explore_u=None, epsilon=0.0, sample_u=None, prob_out=None):
         """One actor step for all E x N agents in one launch (rg_actor_forward: the matrix cores; GRU on bfloat16 planes unless pack_gru says otherwise).
@@ -125,70 +138,34 @@ class BatchedActor(object):
         `explore_select` below).  sample_u [E,N] f32 uniforms in [0, 1): soft-policies actions, SAMPLED from softmax(q)
         (rg_actor_forward_sample; the rule is `soft_select` below), and prob_out [E,N] f32 (or None) receives the probability of the
         sampled action; not together with explore_u.  Returns (q [E,N,A], actions [E,N] int32)."""
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         E, N, D = obs.shape
         if q_out is None:
             q_out = torch.empty(E, N, self.n_actions, device=obs.device)
         if actions_out is None:
             actions_out = torch.empty(E, N, dtype=torch.int32, device=obs.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(obs.device)
-        ws = self._weights_struct()
-        ev = getattr(self, "_pack_done", None)
-        if ev is not None:   # the weights were packed (once) on the then-current stream: order this stream behind them
-            if ev.query():
-                self._pack_done = None
-            else:
-                stream.wait_event(ev)
+        stream, hip_stream = _args.launch_stream(stream, obs.device)
+        args = [C.byref(self.weights_for(stream)), E, N, obs.data_ptr(), D, 1 if append_agent_id else 0,
+                restart.data_ptr() if restart is not None else None, hidden.data_ptr(), q_out.data_ptr(), actions_out.data_ptr()]
         if sample_u is not None and explore_u is not None:
             raise ValueError("sample_u (soft policies) and explore_u (epsilon-greedy) do not combine")
         if prob_out is not None and sample_u is None:
             raise ValueError("prob_out needs sample_u")
         if sample_u is not None:
-            if sample_u.shape != (E, N) or sample_u.dtype != torch.float32 or not sample_u.is_contiguous():
-                raise ValueError("sample_u must be a contiguous float32 [E, N] tensor")
-            if prob_out is not None and (prob_out.shape != (E, N) or prob_out.dtype != torch.float32 or not prob_out.is_contiguous()):
-                raise ValueError("prob_out must be a contiguous float32 [E, N] tensor")
-            rc = lib.rg_actor_forward_sample(C.byref(ws), E, N, obs.data_ptr(), D, 1 if append_agent_id else 0,
-                                             restart.data_ptr() if restart is not None else None, hidden.data_ptr(),
-                                             q_out.data_ptr(), actions_out.data_ptr(), sample_u.data_ptr(),
-                                             prob_out.data_ptr() if prob_out is not None else None, C.c_void_p(stream.cuda_stream))
+            _args.check_tensor("sample_u", sample_u, (torch.float32,), (E, N), errors=_args.VALUE)
+            if prob_out is not None:
+                _args.check_tensor("prob_out", prob_out, (torch.float32,), (E, N), errors=_args.VALUE)
+            rc = lib.rg_actor_forward_sample(*args, sample_u.data_ptr(), prob_out.data_ptr() if prob_out is not None else None, hip_stream)
         elif explore_u is not None:
-            if explore_u.shape != (E, N) or explore_u.dtype != torch.float32 or not explore_u.is_contiguous():
-                raise ValueError("explore_u must be a contiguous float32 [E, N] tensor")
-            rc = lib.rg_actor_forward_explore(C.byref(ws), E, N, obs.data_ptr(), D, 1 if append_agent_id else 0,
-                                              restart.data_ptr() if restart is not None else None, hidden.data_ptr(),
-                                              q_out.data_ptr(), actions_out.data_ptr(), explore_u.data_ptr(), float(epsilon),
-                                              C.c_void_p(stream.cuda_stream))
+            _args.check_tensor("explore_u", explore_u, (torch.float32,), (E, N), errors=_args.VALUE)
+            rc = lib.rg_actor_forward_explore(*args, explore_u.data_ptr(), float(epsilon), hip_stream)
         else:
-            rc = lib.rg_actor_forward(C.byref(ws), E, N, obs.data_ptr(), D, 1 if append_agent_id else 0,
-                                      restart.data_ptr() if restart is not None else None, hidden.data_ptr(),
-                                      q_out.data_ptr(), actions_out.data_ptr(), C.c_void_p(stream.cuda_stream))
+            rc = lib.rg_actor_forward(*args, hip_stream)
         if rc != 0:
             raise _lib.RobogymError("rg_actor_forward: " + lib.rg_actor_last_error().decode())
         return q_out, actions_out
 
     # ------------------------------------------------------------------ whole episode batches (csrc/actor_unroll.h)
-    @staticmethod
-    def _episode_pitch(name, t, inner):
-        """The rows an episode takes in `t` ([B, rows, *inner] with the last dimensions contiguous), from its batch stride."""
-        want, row = [], 1
-        for d in reversed(inner):
-            want.insert(0, row)
-            row *= d
-        want.insert(0, row)
-        # (a dimension of size 1 has no stride to speak of)
-        if any(t.shape[1 + k] > 1 and t.stride(1 + k) != want[k] for k in range(len(want))):
-            raise ValueError(f"{name}: the last {len(want)} dimensions must be contiguous (shape {tuple(t.shape)}, strides {t.stride()})")
-        B, rows = t.shape[0], t.shape[1]
-        if B == 1:
-            return rows
-        if t.stride(0) % row != 0 or t.stride(0) < rows * row:
-            raise ValueError(f"{name}: the batch stride {t.stride(0)} must be a multiple of {row} and at least {rows * row}")
-        return t.stride(0) // row
-
     def unroll(self, obs, append_agent_id=True, hidden=None, q_out=None, actions_out=None, hidden_out=None, stream=None):
         """The actor over every time step of an episode batch in ONE launch (rg_actor_unroll; the rule: csrc/actor_unroll.h):
         what `init_hidden(B)` and `rows` calls of forward_fused on the time slices compute, bit for bit, with the hidden state kept
@@ -199,7 +176,6 @@ class BatchedActor(object):
         per episode in both); nothing is allocated when both are given, so the call can be captured.  Every one of the `rows`
         steps is computed: there are no masks.  Returns (q, greedy actions).  ValueError for a wrong dtype, shape, stride or
         device and for an actor the launch refuses."""
-        import ctypes as C
         if not (self.use_rnn and self.pack_gru == "f16x2"):
             raise ValueError("unroll: the actor must be a GRU packed as two binary16 planes (pack_gru=True / 'f16x2')")
         if self.hidden_dim not in (64, 128):
@@ -209,65 +185,60 @@ class BatchedActor(object):
         if (self.input_dim + 7) // 8 * 8 > 64:
             raise ValueError(f"unroll: an input width above 64 is not supported, the actor's is {self.input_dim}")
         dev, N, H, A = self.w1.device, self.n_agents, self.hidden_dim, self.n_actions
-        if not isinstance(obs, torch.Tensor) or obs.dtype != torch.float32:
-            raise ValueError("unroll: obs must be a float32 tensor")
+        _args.check_tensor("unroll: obs", obs, (torch.float32,), None, dev, contiguous=False, errors=_args.VALUE)
         if obs.dim() != 4 or obs.shape[0] < 1 or obs.shape[1] < 1 or obs.shape[2] != N:
             raise ValueError(f"unroll: obs must be [B, rows, {N}, D] with B, rows >= 1, got {tuple(obs.shape)}")
         B, rows, _, D = obs.shape
         if D + (N if append_agent_id else 0) != self.input_dim:
             raise ValueError(f"unroll: the actor expects {self.input_dim} inputs per agent, obs provides "
                              f"{D + (N if append_agent_id else 0)}")
-        if obs.device != dev:
-            raise ValueError(f"unroll: obs is on {obs.device}, the actor on {dev}")
-        obs_pitch = self._episode_pitch("unroll: obs", obs, (N, D))
-        out_pitch = None
-        for name, t, dtype, inner in (("q_out", q_out, torch.float32, (N, A)), ("actions_out", actions_out, torch.int32, (N,))):
-            if t is None:
-                continue
-            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (B, rows) + inner:
-                raise ValueError(f"unroll: {name} must be a {dtype} tensor {(B, rows) + inner}")
-            if t.device != dev:
-                raise ValueError(f"unroll: {name} is on {t.device}, the actor on {dev}")
-            pitch = self._episode_pitch(f"unroll: {name}", t, inner)
-            if out_pitch not in (None, pitch):
-                raise ValueError(f"unroll: q_out and actions_out must take the same number of rows per episode ({out_pitch}, {pitch})")
-            out_pitch = pitch
+        obs_pitch = _args.episode_pitch("unroll: obs", obs, (N, D))
+        outs = (("q_out", q_out, (N, A)), ("actions_out", actions_out, (N,)))
+        for (name, t, inner), dtype in zip(outs, (torch.float32, torch.int32)):
+            if t is not None:
+                _args.check_tensor("unroll: " + name, t, (dtype,), (B, rows) + inner, dev, contiguous=False, errors=_args.VALUE)
+        out_pitch = _args.shared_pitch("unroll: ", outs, rows)
         for name, t in (("hidden", hidden), ("hidden_out", hidden_out)):
-            if t is None:
-                continue
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (B, N, H) or not t.is_contiguous():
-                raise ValueError(f"unroll: {name} must be a contiguous float32 tensor {(B, N, H)}")
-            if t.device != dev:
-                raise ValueError(f"unroll: {name} is on {t.device}, the actor on {dev}")
+            if t is not None:
+                _args.check_tensor("unroll: " + name, t, (torch.float32,), (B, N, H), dev, errors=_args.VALUE)
         if dev.type != "cuda":
             raise ValueError(f"unroll: the actor lives on {dev}; the launch runs on a HIP device and has no host path")
-        from . import _lib
         lib = _lib.load()
-        if out_pitch is None:
-            out_pitch = rows
         if q_out is None:
             q_out = torch.empty(B, out_pitch, N, A, device=dev)[:, :rows]
         if actions_out is None:
             actions_out = torch.empty(B, out_pitch, N, dtype=torch.int32, device=dev)[:, :rows]
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        ws = self._weights_struct()
-        ev = getattr(self, "_pack_done", None)
-        if ev is not None:   # the weights were packed (once) on the then-current stream: order this stream behind them
-            if ev.query():
-                self._pack_done = None
-            else:
-                stream.wait_event(ev)
+        stream, hip_stream = _args.launch_stream(stream, dev)
+        ws = self.weights_for(stream)
         io = _lib.RgActorUnrollIO(obs.data_ptr(), q_out.data_ptr(), actions_out.data_ptr(),
                                   hidden.data_ptr() if hidden is not None else None,
                                   hidden_out.data_ptr() if hidden_out is not None else None,
                                   B, N, D, rows, obs_pitch, out_pitch, 1 if append_agent_id else 0, 0)
         with torch.cuda.device(dev):
-            rc = lib.rg_actor_unroll(C.byref(ws), C.byref(io), C.c_void_p(stream.cuda_stream))
+            rc = lib.rg_actor_unroll(C.byref(ws), C.byref(io), hip_stream)
         if rc != 0:
-            msg = f"({rc}) {lib.rg_actor_unroll_last_error().decode()}"
-            raise (_lib.RobogymError if rc == -30 else ValueError)(msg)
+            raise _args.launch_error(rc, lib.rg_actor_unroll_last_error().decode())
         return q_out, actions_out
+
+
+def one_launch_refusals(env, actor=None, append_agent_id=True):
+    """ValueError for what rg_policy_rollout refuses, said before anything is launched: first the env's part (read from its
+    attributes alone), then the actor's.  actor=None: the env's part only, for a caller that has not looked at its actor yet."""
+    if int(env.params.qp_mode) != 0:
+        raise ValueError("one launch: the interior-point mode (barrier_solver: cvxopt) is not supported")
+    for attr, what in (("teams", "a team pool (teams)"), ("lidar", "the lidar observation (lidar_rays > 0)"),
+                       ("disturbance", "the pose disturbance (pose_noise_xy / pose_noise_theta)")):
+        if getattr(env, attr, None) is not None:
+            raise ValueError(f"one launch: an env with {what} is not supported; use the two-launch path")
+    if actor is None:
+        return
+    if not (actor.use_rnn and actor.pack_gru == "f16x2"):
+        raise ValueError("one launch: the actor must be a GRU packed as two binary16 planes (pack_gru=True / 'f16x2')")
+    if actor.hidden_dim not in (64, 128):
+        raise ValueError("one launch: hidden size must be 64 or 128")
+    in_dim = env.D + (env.N if append_agent_id else 0)
+    if in_dim != actor.input_dim:
+        raise ValueError(f"one launch: the actor expects {actor.input_dim} inputs per agent, the env provides {in_dim}")
 
 
 def policy_rollout(env, actor, T, io, hidden, actions, restart=None, append_agent_id=True, restart_on_done=False, explore_u=None,
@@ -277,43 +248,20 @@ def policy_rollout(env, actor, T, io, hidden, actions, restart=None, append_agen
     the layouts of include/robogym.h rg_policy_io (None = NULL).  sample_u [T, E, N] f32 uniforms: soft-policies actions
     (rg_policy_rollout_sample), prob [T, E, N] f32 or None the probability each had; not together with explore_u.
     Raises ValueError for a configuration the launch refuses."""
-    import ctypes as C
-    from . import _lib
     lib = _lib.load()
-    if int(env.params.qp_mode) != 0:
-        raise ValueError("one launch: the interior-point mode (barrier_solver: cvxopt) is not supported")
-    if getattr(env, "teams", None) is not None:
-        raise ValueError("one launch: an env with a team pool (teams) is not supported; use the two-launch path")
-    if getattr(env, "lidar", None) is not None:
-        raise ValueError("one launch: an env with the lidar observation (lidar_rays > 0) is not supported; use the two-launch path")
-    if getattr(env, "disturbance", None) is not None:
-        raise ValueError("one launch: an env with the pose disturbance (pose_noise_xy / pose_noise_theta) is not supported; "
-                         "use the two-launch path")
-    if not (actor.use_rnn and actor.pack_gru == "f16x2"):
-        raise ValueError("one launch: the actor must be a GRU packed as two binary16 planes (pack_gru=True / 'f16x2')")
-    if actor.hidden_dim not in (64, 128):
-        raise ValueError("one launch: hidden size must be 64 or 128")
-    in_dim = env.D + (env.N if append_agent_id else 0)
-    if in_dim != actor.input_dim:
-        raise ValueError(f"one launch: the actor expects {actor.input_dim} inputs per agent, the env provides {in_dim}")
+    one_launch_refusals(env, actor, append_agent_id)
     ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    if explore_u is not None and (explore_u.dtype != torch.float32 or not explore_u.is_contiguous()):
-        raise ValueError("explore_u must be a contiguous float32 [T, E, N] tensor")
+    if explore_u is not None:
+        _args.check_tensor("explore_u", explore_u, (torch.float32,), None, errors=_args.VALUE)
     if sample_u is not None and explore_u is not None:
         raise ValueError("sample_u (soft policies) and explore_u (epsilon-greedy) do not combine")
     if prob is not None and sample_u is None:
         raise ValueError("prob needs sample_u")
     for name, t in (("sample_u", sample_u), ("prob", prob)):
-        if t is not None and (tuple(t.shape) != (int(T), env.E, env.N) or t.dtype != torch.float32 or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous float32 [T, E, N] tensor")
+        if t is not None:
+            _args.check_tensor(name, t, (torch.float32,), (int(T), env.E, env.N), errors=_args.VALUE)
     env._sync_stream()   # the handle launches on torch's current stream
-    ws = actor._weights_struct()
-    ev = getattr(actor, "_pack_done", None)
-    if ev is not None:   # the weights were packed (once) on the then-current stream: order this stream behind them
-        if ev.query():
-            actor._pack_done = None
-        else:
-            torch.cuda.current_stream(env.device).wait_event(ev)
+    ws = actor.weights_for(torch.cuda.current_stream(env.device))
     pio = _lib.RgPolicyIO(ptr(hidden), ptr(restart), 1 if append_agent_id else 0, 1 if restart_on_done else 0, ptr(explore_u),
                           float(epsilon), ptr(actions), ptr(obs), ptr(reward_sum), ptr(ended), ptr(dist_sum))
     if sample_u is not None:
@@ -422,9 +370,8 @@ def run_eval(env, actor, steps, obs_agent_id=True, use_graph=False, fused=None, 
     one_launch: the fused loop with the actor and the env step inside ONE launch per (up to) 64 steps (rg_policy_rollout):
     the same statistics as fused=True bit for bit, and the env left in the same state.  Needs an actor packed as two binary16
     planes and the exact barrier QP; anything else raises ValueError."""
-    if one_launch and getattr(env, "disturbance", None) is not None:
-        raise ValueError("one_launch: an env with the pose disturbance (pose_noise_xy / pose_noise_theta) is not supported; the "
-                         "fused loop evaluates it with two launches per step")
+    if one_launch:
+        one_launch_refusals(env, actor, obs_agent_id)
     E, N = env.E, env.N
     dev = env.device
     eye = torch.eye(N, device=dev).unsqueeze(0).expand(E, N, N)
@@ -448,7 +395,6 @@ def run_eval(env, actor, steps, obs_agent_id=True, use_graph=False, fused=None, 
         obs_in.copy_(torch.where(keep, obs, 0.0))   # a finished env restarts from the reference's reset() observation (zeros)
 
     if one_launch:
-        from . import _lib
         if use_graph:
             raise ValueError("one_launch and use_graph are two different ways to cut launches: pick one")
         if env.elapsed is None:   # the launch always runs the gymma block: give it a TimeLimit that never fires
@@ -469,10 +415,7 @@ def run_eval(env, actor, steps, obs_agent_id=True, use_graph=False, fused=None, 
                            dist_sum=dist)
             done += k
         torch.cuda.synchronize(dev)
-        ret_sum, episodes, ep_steps = env.episode_stats()
-        n = max(int(episodes), 1)
-        return {"episodes": int(episodes), "mean_return": float(ret_sum) / n, "mean_steps": float(ep_steps) / n,
-                "mean_dist_per_step": float(dist.sum()) / (steps * E * N)}
+        return _eval_stats(env, dist, steps)
     if fused is None:
         fused = actor.fused_supported()
     if fused:
@@ -508,10 +451,16 @@ def run_eval(env, actor, steps, obs_agent_id=True, use_graph=False, fused=None, 
         finally:
             env.set_stream(prev)
         torch.cuda.synchronize(dev)
+    return _eval_stats(env, dist, steps)
+
+
+def _eval_stats(env, dist, steps):
+    """run_eval's return value (the statistics the reference's run_env prints, misc.py:134-221): from the env's on-device
+    accumulators and the per-agent distance sums `dist` of `steps` steps."""
     ret_sum, episodes, ep_steps = env.episode_stats()
     n = max(int(episodes), 1)
     return {"episodes": int(episodes), "mean_return": float(ret_sum) / n, "mean_steps": float(ep_steps) / n,
-            "mean_dist_per_step": float(dist.sum()) / (steps * E * N)}
+            "mean_dist_per_step": float(dist.sum()) / (steps * env.E * env.N)}
 
 
 def main(argv=None):

@@ -21,7 +21,7 @@ single-env form with EPyMARL's Python types, for dropping into an unmodified EPy
 import numpy as np
 import torch
 
-from .evaluate import explore_select, policy_rollout, soft_select
+from .evaluate import explore_select, one_launch_refusals, policy_rollout, soft_select
 from .vec_env import VecRobotariumEnv
 
 N_ACTIONS = {"PredatorCapturePrey": 5, "Warehouse": 5, "MaterialTransport": 20, "Simple": 5, "ArcticTransport": 5}
@@ -290,9 +290,8 @@ class BatchedRunner(object):
             raise ValueError("run(T) collects T >= 1 time steps")
         if into is not None:
             into.check_fits(E, N, D, v.episode_limit, self.action_selector == "soft_policies" and not self.test_mode)
-        if one_launch and getattr(env, "disturbance", None) is not None:
-            raise ValueError("one_launch: an env with the pose disturbance (pose_noise_xy / pose_noise_theta) is not supported; "
-                             "run(T) collects it on the two-launch path")
+        if one_launch:
+            one_launch_refusals(env)     # the env's part, before anything is allocated; policy_rollout says the actor's
         out = {"obs": torch.empty(T + 1, E, N, D, device=dev),
                "avail_actions": torch.ones(T + 1, E, N, A, dtype=torch.int32, device=dev),
                "actions": torch.empty(T, E, N, dtype=torch.int32, device=dev),
@@ -309,11 +308,6 @@ class BatchedRunner(object):
         s_all = torch.rand(T, E, N, generator=self.gen, device=dev) if soft else None
         if soft:
             out["prob"] = torch.empty(T, E, N, device=dev)
-        if one_launch and getattr(env, "teams", None) is not None:
-            raise ValueError("one_launch: an env with a team pool (teams) is not supported; run(T) collects it on the two-launch path")
-        if one_launch and env.lidar is not None:
-            raise ValueError("one_launch: an env with the lidar observation (lidar_rays > 0) is not supported; run(T) collects it "
-                             "on the two-launch path")
         if one_launch and not direct:
             raise ValueError("one_launch needs a fused GymmaVecEnv and an actor the fused kernel supports "
                              "(hidden size 64 / 128, at most 32 actions and 64 inputs)")

@@ -11,7 +11,9 @@ the state it already holds.
 """
 import ctypes as C
 
-from . import _lib
+import torch
+
+from . import _args, _lib
 
 # layer names, in draw order -> bits of rg_render_params.layers
 LAYERS = {"arena": _lib.RENDER_ARENA, "zones": _lib.RENDER_ZONES, "markers": _lib.RENDER_MARKERS, "rings": _lib.RENDER_RINGS,
@@ -78,17 +80,7 @@ def parse_view(view):
 
 def check_out(out, shape, device=None):
     """out: the caller's frame tensor -- uint8, contiguous, of `shape` [K, H, W, 3] (on `device`, 4-byte aligned)."""
-    import torch
-    if not isinstance(out, torch.Tensor):
-        raise TypeError("out must be a torch tensor")
-    if out.dtype != torch.uint8:
-        raise TypeError(f"out must be uint8, got {out.dtype}")
-    if tuple(out.shape) != tuple(shape):
-        raise ValueError(f"out must have the shape {tuple(shape)}, got {tuple(out.shape)}")
-    if not out.is_contiguous():
-        raise ValueError("out must be contiguous")
-    if device is not None and out.device != device:
-        raise ValueError(f"out is on {out.device}, the env on {device}")
+    _args.check_tensor("out", out, (torch.uint8,), shape, device, errors=(TypeError, TypeError))
     if out.data_ptr() % 4:
         raise ValueError("out must be 4-byte aligned")
     return out
@@ -97,7 +89,6 @@ def check_out(out, shape, device=None):
 def env_indices(envs, num_envs, device):
     """envs: None (all), an int, a sequence or an int tensor -> (K, int32 device tensor or None).  Host data is range-checked
     here (IndexError); a device tensor is taken as it is (rg_render draws an index outside [0, E) without the env's shapes)."""
-    import torch
     if envs is None:
         return num_envs, None
     if isinstance(envs, torch.Tensor) and envs.device.type != "cpu":
@@ -124,7 +115,6 @@ def env_indices(envs, num_envs, device):
 
 def render_frames(env, envs=None, size=84, out=None, layers=None, view=None):
     """VecRobotariumEnv.render (see there)."""
-    import torch
     h, w = parse_size(size)
     # with a team pool the rings would show the config's radii, not the episode's: dropped unless asked for by name
     mask = layer_mask(layers, ALL_LAYERS & ~LAYERS["rings"] if env.teams is not None else ALL_LAYERS)
@@ -136,17 +126,16 @@ def render_frames(env, envs=None, size=84, out=None, layers=None, view=None):
         if out is None:
             out = torch.empty((k, h, w, 3), dtype=torch.uint8, device=env.device)
         rp = _lib.RgRenderParams(w, h, k, mask, idx.data_ptr() if idx is not None else None, vx, vy, vw, vh)
-        stream = torch.cuda.current_stream(env.device).cuda_stream
-        rc = env.lib.rg_render(C.byref(env.params), C.byref(env._state), env.E, C.byref(rp), out.data_ptr(), C.c_void_p(stream))
+        rc = env.lib.rg_render(C.byref(env.params), C.byref(env._state), env.E, C.byref(rp), out.data_ptr(),
+                               _args.launch_stream(None, env.device)[1])
     if rc != 0:
-        raise _lib.RobogymError(f"rg_render failed ({rc}): {env.lib.rg_render_last_error().decode()}")
+        raise _args.launch_error(rc, "rg_render: " + env.lib.rg_render_last_error().decode(), refuses=False)
     return out
 
 
 def record(env, actions, size=84, envs=None):
     """Render, then step and render once per row of `actions` [T, E, N] (int, on the env's device): uint8
     [T + 1, K, H, W, 3], frame 0 the state before the first step."""
-    import torch
     h, w = parse_size(size)
     k, idx = env_indices(envs, env.E, env.device)
     steps = int(actions.shape[0])

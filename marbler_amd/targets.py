@@ -12,12 +12,16 @@ TargetMixer.forward() is the plain torch composition of the mixer (EPyMARL's QMi
 import ctypes as C
 import math
 
-from . import _lib
+import torch
+
+from . import _args, _lib
 
 KINDS = {"none": _lib.MIXER_NONE, "vdn": _lib.MIXER_VDN, "qmix": _lib.MIXER_QMIX}
 EMBED, HYPER = 32, 64                   # mixing_embed_dim, hypernet_embed (hypernet_layers: 2): the one instantiation
 MAX_STATE = 256                         # the padded state width the kernel's LDS image holds
 COLS = 2 * HYPER + 2 * EMBED            # the four first layers side by side: 192 columns
+# (first column, state-dict prefix, width) of each in w_in / b_in
+FIRST_LAYERS = ((0, "hyper_w_1.0", HYPER), (HYPER, "hyper_w_final.0", HYPER), (2 * HYPER, "V.0", EMBED), (2 * HYPER + EMBED, "hyper_b_1", EMBED))
 
 
 def qmix_shapes(n_agents, state_dim):
@@ -49,7 +53,6 @@ class TargetMixer(object):
     re-packs into the same storage: a soft or hard target update allocates nothing."""
 
     def __init__(self, kind, n_agents, state_dim, state_dict=None, device="cuda:0", seed=0):
-        import torch
         if kind not in KINDS:
             raise ValueError(f"kind must be one of {tuple(KINDS)}, got {kind!r}")
         for k, v in (("n_agents", n_agents), ("state_dim", state_dim)):
@@ -80,7 +83,6 @@ class TargetMixer(object):
     def load_state_dict(self, state_dict):
         """Checks and re-packs (qmix): ValueError for missing keys, wrong shapes, the shapes of hypernet_layers: 1, weights that are
         not finite.  Nothing is allocated on the mixer's device beyond the copies of the incoming tensors."""
-        import torch
         if self.kind != "qmix":
             if state_dict:
                 raise ValueError(f"a {self.kind!r} mixer has no weights")
@@ -115,8 +117,7 @@ class TargetMixer(object):
     def _pack(self):
         p, S = self.params, self.state_dim
         w_in = self._view("w_in")
-        for c, k, n in ((0, "hyper_w_1.0", HYPER), (HYPER, "hyper_w_final.0", HYPER), (2 * HYPER, "V.0", EMBED),
-                        (2 * HYPER + EMBED, "hyper_b_1", EMBED)):
+        for c, k, n in FIRST_LAYERS:
             w_in[:S, c:c + n].copy_(p[k + ".weight"].t())
             self._view("b_in")[c:c + n].copy_(p[k + ".bias"])
         w_in[S:].zero_()
@@ -132,8 +133,7 @@ class TargetMixer(object):
         S = self.state_dim
         w_in, b_in = self._view("w_in"), self._view("b_in")
         out = {}
-        for c, k, n in ((0, "hyper_w_1.0", HYPER), (HYPER, "hyper_w_final.0", HYPER), (2 * HYPER, "V.0", EMBED),
-                        (2 * HYPER + EMBED, "hyper_b_1", EMBED)):
+        for c, k, n in FIRST_LAYERS:
             out[k + ".weight"] = w_in[:S, c:c + n].t().clone()
             out[k + ".bias"] = b_in[c:c + n].clone()
         out["hyper_w_1.2.weight"], out["hyper_w_1.2.bias"] = self._view("w_w1").t().clone(), self._view("b_w1").clone()
@@ -144,7 +144,6 @@ class TargetMixer(object):
     def forward(self, agent_q, state):
         """The mixer in plain torch ops: agent_q [..., N], state [..., S] -> [..., 1] (`none`: agent_q itself).  EPyMARL's
         QMixer.forward / VDNMixer.forward."""
-        import torch
         import torch.nn.functional as F
         if self.kind == "none":
             return agent_q
@@ -185,13 +184,11 @@ def td_targets(qt, obs, reward, terminated, filled, mixer, gamma, sel=None, targ
     targets_out / mask_out / agent_q_out: outputs to reuse (the same number of rows per episode in all three); nothing is allocated
     when all three are given, so the call can be captured.  ValueError for a wrong dtype, shape, stride or device and for what the
     launch refuses."""
-    import torch
-    from .evaluate import BatchedActor
-    _pitch = lambda name, t, inner: BatchedActor._episode_pitch("td_targets: " + name, t, inner)  # noqa: E731
     if not isinstance(mixer, TargetMixer):
         raise ValueError(f"td_targets: mixer must be a TargetMixer, got {type(mixer).__name__}")
-    if not isinstance(qt, torch.Tensor) or qt.dtype != torch.float32 or qt.dim() != 4:
-        raise ValueError("td_targets: qt must be a float32 tensor [B, rows, N, A]")
+    _args.check_tensor("td_targets: qt", qt, (torch.float32,), None, contiguous=False, errors=_args.VALUE)
+    if qt.dim() != 4:
+        raise ValueError(f"td_targets: qt must be [B, rows, N, A], got {tuple(qt.shape)}")
     B, rows, N, A = qt.shape
     if B < 1 or rows < 2:
         raise ValueError(f"td_targets: qt must be [B, rows, N, A] with B >= 1 and rows >= 2, got {tuple(qt.shape)}")
@@ -199,8 +196,8 @@ def td_targets(qt, obs, reward, terminated, filled, mixer, gamma, sel=None, targ
         raise ValueError(f"td_targets: qt has {N} agents, the mixer {mixer.n_agents}")
     if not 1 <= A <= 32:
         raise ValueError(f"td_targets: n_actions must be in 1..32, qt has {A}")
-    if not isinstance(obs, torch.Tensor) or obs.dtype != torch.float32 or obs.dim() != 4 or tuple(obs.shape[:3]) != (B, rows, N) or obs.shape[3] < 1:
-        raise ValueError(f"td_targets: obs must be a float32 tensor [{B}, {rows}, {N}, D]")
+    if not isinstance(obs, torch.Tensor) or obs.dim() != 4 or obs.shape[3] < 1:
+        raise ValueError(f"td_targets: obs must be a float32 tensor [{B}, {rows}, {N}, D] with D >= 1")
     D = obs.shape[3]
     if mixer.kind == "qmix" and N * D != mixer.state_dim:
         raise ValueError(f"td_targets: the mixer's state_dim is {mixer.state_dim}, obs provides {N} x {D}")
@@ -209,57 +206,36 @@ def td_targets(qt, obs, reward, terminated, filled, mixer, gamma, sel=None, targ
     dev = qt.device
     T = rows - 1
     flags = (torch.uint8, torch.bool)
-    ins = [("obs", obs, (torch.float32,), (B, rows, N, D)), ("reward", reward, (torch.float32,), (B, rows)),
-           ("terminated", terminated, flags, (B, rows)), ("filled", filled, flags, (B, rows))]
-    if sel is not None:
-        ins.append(("sel", sel, (torch.int32,), (B, rows, N)))
-    t_shape = (B, T, N) if mixer.kind == "none" else (B, T)
-    outs = [("targets_out", targets_out, (torch.float32,), t_shape), ("mask_out", mask_out, (torch.float32,), (B, T)),
-            ("agent_q_out", agent_q_out, (torch.float32,), (B, T, N))]
-    for name, t, dtypes, shape in ins + [o for o in outs if o[1] is not None]:
-        if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or tuple(t.shape) != shape:
-            raise ValueError(f"td_targets: {name} must be a {' or '.join(str(d) for d in dtypes)} tensor {shape}")
-        if t.device != dev:
-            raise ValueError(f"td_targets: {name} is on {t.device}, qt on {dev}")
+    f32, t_shape = (torch.float32,), ((B, T, N) if mixer.kind == "none" else (B, T))
+    # (name, tensor, dtypes, shape), grouped as the launch addresses them: one pitch per group
+    qt_arg, sel_arg = ("qt", qt, f32, (B, rows, N, A)), ("sel", sel, (torch.int32,), (B, rows, N))
+    obs_arg = ("obs", obs, f32, (B, rows, N, D))
+    flag_args = [("reward", reward, f32, (B, rows)), ("terminated", terminated, flags, (B, rows)), ("filled", filled, flags, (B, rows))]
+    out_args = [("targets_out", targets_out, f32, t_shape), ("mask_out", mask_out, f32, (B, T)), ("agent_q_out", agent_q_out, f32, (B, T, N))]
+    for name, t, dtypes, shape in [obs_arg] + flag_args + [a for a in [sel_arg] + out_args if a[1] is not None]:
+        _args.check_tensor("td_targets: " + name, t, dtypes, shape, dev, contiguous=False, errors=_args.VALUE)
     if mixer.device != dev:
         raise ValueError(f"td_targets: the mixer is on {mixer.device}, qt on {dev}")
-    q_pitch = _pitch("qt", qt, (N, A))
-    if sel is not None and _pitch("sel", sel, (N,)) != q_pitch and B > 1:
-        raise ValueError(f"td_targets: qt and sel must take the same number of rows per episode ({q_pitch}, {_pitch('sel', sel, (N,))})")
-    obs_pitch = _pitch("obs", obs, (N, D))
-    flag_pitch = _pitch("reward", reward, ())
-    for name, t in (("terminated", terminated), ("filled", filled)):
-        if _pitch(name, t, ()) != flag_pitch:
-            raise ValueError(f"td_targets: reward, terminated and filled must take the same number of rows per episode ({flag_pitch}, {_pitch(name, t, ())})")
-    out_pitch = None
-    for name, t, _, shape in outs:
-        if t is None:
-            continue
-        pitch = _pitch(name, t, shape[2:])
-        if out_pitch not in (None, pitch):
-            raise ValueError(f"td_targets: targets_out, mask_out and agent_q_out must take the same number of rows per episode ({out_pitch}, {pitch})")
-        out_pitch = pitch
+    pitch = lambda args, dense: _args.shared_pitch("td_targets: ", [(n, t, shape[2:]) for n, t, _, shape in args], dense)  # noqa: E731
+    q_pitch, obs_pitch = pitch([qt_arg, sel_arg], rows), pitch([obs_arg], rows)
+    flag_pitch, out_pitch = pitch(flag_args, rows), pitch(out_args, T)
     if dev.type != "cuda":
         raise ValueError(f"td_targets: qt lives on {dev}; the launch runs on a HIP device and has no host path")
     lib = _lib.load()
-    if out_pitch is None:
-        out_pitch = T
     if targets_out is None:
         targets_out = torch.empty((B, out_pitch) + t_shape[2:], device=dev)[:, :T]
     if mask_out is None:
         mask_out = torch.empty(B, out_pitch, device=dev)[:, :T]
     if agent_q_out is None:
         agent_q_out = torch.empty(B, out_pitch, N, device=dev)[:, :T]
-    if stream is None:
-        stream = torch.cuda.current_stream(dev)
+    stream, hip_stream = _args.launch_stream(stream, dev)
     m = mixer.weights_struct()
     as_u8 = lambda t: t.view(torch.uint8) if t.dtype == torch.bool else t  # noqa: E731
     io = _lib.RgTdTargetsIO(qt.data_ptr(), sel.data_ptr() if sel is not None else None, obs.data_ptr(), reward.data_ptr(),
                             as_u8(terminated).data_ptr(), as_u8(filled).data_ptr(), targets_out.data_ptr(), mask_out.data_ptr(),
                             agent_q_out.data_ptr(), B, N, D, A, rows, q_pitch, obs_pitch, flag_pitch, out_pitch, float(gamma), 0)
     with torch.cuda.device(dev):
-        rc = lib.rg_td_targets(C.byref(m), C.byref(io), C.c_void_p(stream.cuda_stream))
+        rc = lib.rg_td_targets(C.byref(m), C.byref(io), hip_stream)
     if rc != 0:
-        msg = f"({rc}) {lib.rg_td_targets_last_error().decode()}"
-        raise (_lib.RobogymError if rc == -30 else ValueError)(msg)
+        raise _args.launch_error(rc, lib.rg_td_targets_last_error().decode())
     return {"targets": targets_out, "mask": mask_out, "agent_q": agent_q_out}

@@ -267,3 +267,67 @@ def test_two_binary16_planes_saturate_beyond_binary16s_range_and_keep_nans():
     bad = torch.isnan(q).any(dim=2)
     assert bool(bad[5, 2]) and int(bad.sum()) == 1
     assert int(act.min()) >= 0 and int(act.max()) < A
+
+
+@pytest.mark.parametrize("entry", ["forward_fused", "unroll", "policy_rollout"])
+def test_first_launch_on_a_side_stream_is_ordered_behind_the_weight_pack(entry):
+    """The GRU matrices are packed once, by two kernels queued on the stream that is current when the weights struct is first
+    built.  A first launch on ANOTHER stream must be ordered behind them (BatchedActor.weights_for): a freshly constructed actor,
+    its pack queued on the current stream behind a few large products, goes straight to a side stream through each entry that
+    takes the weights, and must give, bit for bit, what an actor that was packed and synchronised first gives for the same call.
+    The memory the unsynchronised actor packs into must not already hold the answer: the reference actor stays alive until the
+    comparison (its packed planes are not handed out again), a decoy actor of the same shapes and OTHER weights is packed and
+    dropped right before (what the allocator hands out next holds the decoy's planes), and each entry has its own weights.
+    A guard, not a proof: a launch that missed the wait would read weights that are not packed yet, which shows as wrong values
+    (never as a fault) -- unless the pack happened to finish first, and then the test passes by luck."""
+    from marbler_amd.evaluate import BatchedActor
+    from marbler_amd.gymma import BatchedRunner, GymmaVecEnv
+    dev = torch.device("cuda:0")
+    E, N, D, H, A, T = 8, 3, 5, 64, 6, 2
+    g = torch.Generator().manual_seed(11)
+    obs = (torch.rand(E, 3, N, D, generator=g) * 3 - 1.5).to(dev)                 # unroll: B = 8 episodes of 3 rows
+    hidden0 = (torch.rand(E, N, H, generator=g) * 2 - 1).to(dev)
+    obs0 = obs[:, 0].contiguous()
+    busy = torch.rand(4096, 4096, device=dev)
+    side = torch.cuda.Stream(device=dev)
+
+    seed = {"forward_fused": 3, "unroll": 13, "policy_rollout": 23}[entry]
+
+    def call(synchronised, seed):
+        """-> (the outputs, the actor: whoever holds it keeps its packed planes from being handed out again)"""
+        v = GymmaVecEnv("robotarium_gym:PredatorCapturePrey-v0", E, time_limit=10, seed=5) if entry == "policy_rollout" else None
+        n, width, n_act = (v.n_agents, v.obs_size + v.n_agents, v.n_actions) if v is not None else (N, D + N, A)
+        actor = BatchedActor(random_actor(1, width, H, n_act, True, seed=seed), n, device=dev)
+        runner = BatchedRunner(v, actor, seed=9) if v is not None else None
+        hidden = hidden0.clone()
+        torch.cuda.synchronize()
+        if not synchronised:
+            for _ in range(4):                      # the pack kernels queue up behind these
+                torch.mm(busy, busy)
+        actor._weights_struct()
+        if synchronised:
+            torch.cuda.synchronize()
+        if entry == "forward_fused":
+            q, act = actor.forward_fused(obs0, hidden, stream=side)
+            out = [q, act, hidden]
+        elif entry == "unroll":
+            h_out = torch.empty_like(hidden)
+            q, act = actor.unroll(obs, hidden=hidden, hidden_out=h_out, stream=side)
+            out = [q, act, h_out]
+        else:
+            with torch.cuda.stream(side):           # (the env's handle launches on torch's current stream)
+                batch = runner.run(T, one_launch=True)
+            out = [batch[k] for k in ("obs", "actions", "reward", "terminated")] + [runner.hidden]
+        torch.cuda.synchronize()
+        out = [t.clone() for t in out]
+        if v is not None:
+            v.close()
+        return out, actor
+
+    want, reference = call(True, seed)
+    decoy, _ = call(True, seed + 1)
+    del _                                           # the decoy's planes go back to the allocator; the reference's stay out
+    got, _ = call(False, seed)
+    assert reference._ws is not None and len(want) == len(got) and all(torch.equal(a, b) for a, b in zip(want, got))
+    assert bool(torch.isfinite(want[0]).all()) and bool(want[0].abs().sum() > 0)
+    assert not all(torch.equal(a, b) for a, b in zip(want, decoy))             # (other weights do give other values)
