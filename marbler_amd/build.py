@@ -8,6 +8,8 @@ bit; implicit fma contraction would break that.
 """
 import glob
 import os
+import re
+import shlex
 import shutil
 import subprocess
 import sys
@@ -15,13 +17,12 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librobogym_hip.so")
-SOURCES = ["robogym_kernels.hip", "robogym_resident.hip", "robogym_resident_shapes.hip", "robogym_rollout_group.hip", "robogym_kernels_ipm.hip", "robogym_rollout_group_ipm.hip",
-           "robogym_tpe.hip", "robogym_rollout_tpe.hip", "robogym_capi.hip", "actor_mfma.hip", "robogym_policy_h64.hip",
-           "robogym_policy_h128.hip", "robogym_policy_sample_h64.hip", "robogym_policy_sample_h128.hip", "robogym_lidar.hip", "robogym_lidar_rollout.hip", "robogym_lidar_ipm.hip",
-           "robogym_lidar_rollout_ipm.hip", "robogym_team.hip", "robogym_team_rollout.hip", "robogym_team_ipm.hip",
-           "robogym_team_rollout_ipm.hip", "robogym_disturb.hip", "robogym_disturb_rollout.hip", "robogym_disturb_ipm.hip",
-           "robogym_disturb_rollout_ipm.hip", "robogym_render.hip", "robogym_episodes.hip", "robogym_actor_unroll.hip",
-           "robogym_td_targets.hip"]
+# The files that are a translation unit each.  The lane-group step kernels' units and the policy rollouts' are derived below
+# (group_units, policy_units), each from one generic source.
+SOURCES = ["robogym_kernels.hip", "robogym_resident.hip", "robogym_resident_shapes.hip", "robogym_tpe.hip", "robogym_rollout_tpe.hip",
+           "robogym_capi.hip", "actor_mfma.hip", "robogym_team.hip", "robogym_render.hip", "robogym_episodes.hip",
+           "robogym_actor_unroll.hip", "robogym_td_targets.hip"]
+GROUP_UNIT, POLICY_UNIT = "robogym_group_unit.hip", "robogym_policy_unit.hip"
 # every header of csrc/ (a forgotten one would mean a stale library), and the C ABI's
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(CSRC, "probes", "*.h"))) + \
           [os.path.join(HERE, "..", "include", "robogym.h")]
@@ -69,24 +70,57 @@ RESIDENT_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 # exec restore), and tests/test_kernel_resources.py scans every shipped kernel.  Without the duplication the kernels have the
 # layout actor_kernel has, the same registers and LDS, and the scan is clean.
 UNROLL_LAYOUT = ["-mllvm", "-tail-dup-placement=false"]
+
+
+def group_flags(mode):
+    """The flags of a translation unit of lane-group kernels, whatever its family -- plain, lidar (step_group.h
+    lidar_step_kernel), team (team_step_kernel), pose disturbance (disturb_step_kernel) -- and the policy rollouts': GROUP_SLP,
+    and IPM_SCHED on top in the interior-point mode.  Hence a mode's kernels never share a unit with the other mode's: the
+    exact-projection kernels are better off with the default scheduling strategy (the figures above)."""
+    return GROUP_SLP + (IPM_SCHED if mode == "RG_QP_CVXOPT" else [])
+
+
 FILE_FLAGS = {"robogym_tpe.hip": ["-fno-slp-vectorize"], "robogym_rollout_tpe.hip": ["-fno-slp-vectorize"],
-              "robogym_kernels.hip": GROUP_SLP, "robogym_rollout_group.hip": GROUP_SLP,
+              # the plain and the team family's single launches of the exact mode, next to the reset kernel and the index writer
+              "robogym_kernels.hip": group_flags("RG_QP_EXACT"), "robogym_team.hip": group_flags("RG_QP_EXACT"),
               "robogym_resident.hip": GROUP_SLP + RESIDENT_PRELOAD,
               # the reference shapes' resident kernels (kernel_args.h RG_REF_SHAPES): the same kernels, the same flags
               "robogym_resident_shapes.hip": GROUP_SLP + RESIDENT_PRELOAD,
-              "robogym_kernels_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_rollout_group_ipm.hip": GROUP_SLP + IPM_SCHED,
-              "robogym_policy_h64.hip": GROUP_SLP, "robogym_policy_h128.hip": GROUP_SLP,
-              "robogym_policy_sample_h64.hip": GROUP_SLP, "robogym_policy_sample_h128.hip": GROUP_SLP,
-              # the lidar kernels (step_group.h lidar_step_kernel): lane-group kernels, with the flags of their mode
-              "robogym_lidar.hip": GROUP_SLP, "robogym_lidar_rollout.hip": GROUP_SLP,
-              "robogym_lidar_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_lidar_rollout_ipm.hip": GROUP_SLP + IPM_SCHED,
-              # the team kernels (step_group.h team_step_kernel): lane-group kernels, with the flags of their mode
-              "robogym_team.hip": GROUP_SLP, "robogym_team_rollout.hip": GROUP_SLP,
-              "robogym_team_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_team_rollout_ipm.hip": GROUP_SLP + IPM_SCHED,
-              # the pose-disturbance kernels (step_group.h disturb_step_kernel): lane-group kernels, with the flags of their mode
-              "robogym_disturb.hip": GROUP_SLP, "robogym_disturb_rollout.hip": GROUP_SLP,
-              "robogym_disturb_ipm.hip": GROUP_SLP + IPM_SCHED, "robogym_disturb_rollout_ipm.hip": GROUP_SLP + IPM_SCHED,
               "robogym_actor_unroll.hip": UNROLL_LAYOUT}
+# the rows of RG_GROUP_ENTRIES that a file above defines itself, next to a kernel or a launcher of its own
+OWN_ENTRIES = {"launch_step", "launch_obs", "launch_team_step", "launch_team_obs", "launch_step_resident", "launch_step_shape"}
+
+
+def group_rows():
+    """The rows of csrc/kernel_args.h RG_GROUP_ENTRIES -- the one list of the lane-group entries -- as (entry, family, mode, kind)."""
+    with open(os.path.join(CSRC, "kernel_args.h")) as f:
+        table = re.search(r"#define RG_GROUP_ENTRIES\(X\)((?:.*\\\n)*.*)", f.read()).group(1)
+    return re.findall(r"X\((\w+), (\w+), (\w+), (\w+)\)", table)
+
+
+def group_units():
+    """The lane-group units compiled from GROUP_UNIT, as (object name, source, flags, defines).  A unit is a family's single
+    launches of one solver mode (step, and obs where the family has one) or its rollout, and is handed its rows as they stand."""
+    units = {}
+    for entry, family, mode, kind in group_rows():
+        if entry not in OWN_ENTRIES:
+            units.setdefault((family, mode, kind == "GROUP_ROLLOUT"), []).append(f"X({entry},{family},{mode},{kind})")
+    # (the object's name: robogym_lidar_cvxopt_rollout for GROUP_LIDAR, RG_QP_CVXOPT, rollout)
+    return [(f"robogym_{family[6:]}_{mode[6:]}{'_rollout' if rollout else ''}".lower(), GROUP_UNIT, group_flags(mode),
+             ["RG_UNIT_ROWS=" + "".join(rows)]) for (family, mode, rollout), rows in units.items()]
+
+
+def policy_units():
+    """rg_policy_rollout's units: POLICY_UNIT per (hidden size, sampling), lane-group kernels of the exact mode."""
+    return [(f"robogym_policy{'_sample' if sample else ''}_h{h}", POLICY_UNIT, group_flags("RG_QP_EXACT"),
+             [f"RG_UNIT_H={h}", f"RG_UNIT_SAMPLE={sample}"]) for sample in (0, 1) for h in (64, 128)]
+
+
+def units():
+    """Every translation unit of the library: (object name, source, per-unit flags, the unit's own defines)."""
+    return [(os.path.splitext(s)[0], s, FILE_FLAGS.get(s, []), []) for s in SOURCES] + group_units() + policy_units()
+
+
 BASE_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 STAMP = LIB + ".flags"
 
@@ -101,15 +135,14 @@ def hipcc_path():
 def flags_stamp(defines=(), extra=(), file_flags=True):
     """What a library was built with, as one string: the rebuild check compares it (a library left behind by an A/B build
     with other flags is stale, whatever its mtime)."""
-    per_file = sorted(FILE_FLAGS.items()) if file_flags else []
-    return repr((BASE_FLAGS, sorted(defines), list(extra), per_file, SOURCES))
+    return repr((BASE_FLAGS, sorted(defines), list(extra), [(n, s, f if file_flags else [], d) for n, s, f, d in units()]))
 
 
 def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + HEADERS + [os.path.abspath(__file__)]
+    deps = [os.path.join(CSRC, s) for s in SOURCES + [GROUP_UNIT, POLICY_UNIT]] + HEADERS + [os.path.abspath(__file__)]
     if any(os.path.getmtime(d) > t for d in deps):
         return True
     try:
@@ -142,12 +175,12 @@ def build(force=False, verbose=False, defines=(), out=None):
     os.makedirs(objdir, exist_ok=True)
     flags = BASE_FLAGS + [f"-D{d}" for d in defines] + extra
     objs, procs = [], []
-    for src in SOURCES:
-        obj = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
-        per_file = [] if no_file_flags else FILE_FLAGS.get(src, [])   # (A/B builds)
-        cmd = [hipcc_path()] + flags + per_file + ["-c", os.path.join(CSRC, src), "-o", obj]
+    for name, src, unit_flags, unit_defines in units():
+        obj = os.path.join(objdir, name + ".o")
+        per_file = [] if no_file_flags else unit_flags   # (A/B builds)
+        cmd = [hipcc_path()] + flags + per_file + [f"-D{d}" for d in unit_defines] + ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
-            print(" ".join(cmd))
+            print(shlex.join(cmd))
         procs.append((cmd, subprocess.Popen(cmd)))
         objs.append(obj)
     for cmd, pr in procs:

@@ -129,8 +129,9 @@ inline hipError_t for_scenario(int scn, F &&f) {
 hipError_t launch_reset(const KernelArgs &a, hipStream_t stream);
 
 // The lane-group step kernels (step_group.h) come in four families -- plain, with the lidar block (rg_set_lidar), with a team
-// pool (rg_set_teams), with the pose disturbance (rg_set_disturbance) -- and every (family, solver mode, launch kind) has a translation unit of its own with ONE entry, so that
-// they compile side by side and each gets its mode's flags (build.py FILE_FLAGS).  The list: X(entry, family, qp_mode, kind).
+// pool (rg_set_teams), with the pose disturbance (rg_set_disturbance) -- and every (family, solver mode, launch kind) has ONE entry.
+// The list: X(entry, family, qp_mode, kind).  The build reads it too (build.py group_units): a family's single launches of a mode
+// and its rollout are a translation unit each, compiled from robogym_group_unit.hip side by side, each with its mode's flags.
 // An observation-only launch (rg_get_obs) runs no controller: it exists in the exact mode only and serves both.  The disturbance
 // family has none: rg_get_obs displaces nothing, and a disturbed handle's goes to the plain entry.  (GroupFamily, GroupKind and
 // the plan that selects a row: launch_plan.h.)

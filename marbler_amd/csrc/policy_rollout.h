@@ -1,5 +1,5 @@
 // policy_rollout.h -- rg_policy_rollout: T time steps of "actor -> action -> env step" in ONE launch (instantiated by
-// robogym_policy_h64.hip and robogym_policy_h128.hip, one file per hidden size so that the two compile side by side).
+// robogym_policy_unit.hip, compiled once per hidden size and selector so that they compile side by side).
 //
 // A workgroup is the actor's H / 32 wavefronts and owns the envs of one step wavefront (64 / GW envs, at most 64 agent rows: two
 // actor tiles of 32 rows; a non-shared actor takes one tile per agent index).  Envs are independent, so there is no device-wide

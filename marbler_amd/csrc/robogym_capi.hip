@@ -180,7 +180,7 @@ static int check_params(const rg_scenario_params *p) {
     return check_constants(p);
 }
 
-// rg_policy_rollout's kernels live in their own translation units (robogym_policy_h64.hip, robogym_policy_h128.hip).  Declared
+// rg_policy_rollout's kernels live in their own translation units (robogym_policy_unit.hip, one per hidden size and selector).  Declared
 // weak: the host-only sanitizer build of this file links without them, and the entry point then refuses to run.
 namespace rg {
 hipError_t launch_policy_rollout_h64(const KernelArgs &, const rg_actor_weights &, const rg_policy_io &, int32_t, hipStream_t)
@@ -191,7 +191,7 @@ hipError_t launch_policy_rollout_sample_h64(const KernelArgs &, const rg_actor_w
                                             int32_t, hipStream_t) __attribute__((weak));
 hipError_t launch_policy_rollout_sample_h128(const KernelArgs &, const rg_actor_weights &, const rg_policy_io &, const rg_policy_sample &,
                                              int32_t, hipStream_t) __attribute__((weak));
-// The lane-group step kernels' entries (kernel_args.h RG_GROUP_ENTRIES: one translation unit each), and the team pool's index
+// The lane-group step kernels' entries (kernel_args.h RG_GROUP_ENTRIES, in translation units of their own), and the team pool's index
 // writer next to them: weak for the same reason.
 #define RG_X(entry, family, mode, kind) GroupLaunch entry __attribute__((weak));
 RG_GROUP_ENTRIES(RG_X)

@@ -1,7 +1,7 @@
 // step_group.h -- the fused env-step kernel for gfx950 (MI355X, CDNA4), lane-group mapping.
 // (Templates only: the step, its kernels in four families -- plain, lidar, team pool, pose disturbance -- and their one launch
-// dispatcher.  Instantiated by robogym_kernels*.hip / robogym_rollout_group*.hip, robogym_lidar*.hip, robogym_team*.hip and
-// robogym_disturb*.hip, one translation unit per (family, solver mode, launch kind): kernel_args.h RG_GROUP_ENTRIES.)
+// dispatcher.  Instantiated by robogym_group_unit.hip, compiled once per (family, solver mode, single launch or rollout), and by
+// robogym_kernels.hip, robogym_team.hip and robogym_resident*.hip: kernel_args.h RG_GROUP_ENTRIES.)
 //
 // One launch = one env step for E envs: goal generation, U sim sub-iterations (controller with
 // the barrier-certificate QP every 15th, collision/boundary validation, Euler integration),

@@ -71,48 +71,40 @@ def broadcast_params(params, src=0, device=None):
     return params_from_bytes(buf.cpu().numpy().tobytes())
 
 
-def broadcast_lidar(lidar, src=0, device=None):
-    """The lidar block next to the parameter block: rank `src` sends its RgLidarParams (None = no lidar, sent as rays = 0);
-    every rank returns a copy of it, or None.  Every rank calls it (a collective), whatever its own argument."""
+def _broadcast_block(attr, struct, block, src, device):
+    """The side block `attr` of params.SIDE_BLOCKS, a ctypes `struct`: rank `src` sends its bytes (None: a zeroed one); every
+    rank returns a copy, or None where what it received counts as off by the table's rule."""
     import ctypes
-    from ._lib import RgLidarParams
+    from .params import SIDE_BLOCKS
     if not dist.is_initialized():
-        return lidar
+        return block
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     device = collective_device(device)
-    n = ctypes.sizeof(RgLidarParams)
+    n = ctypes.sizeof(struct)
     if dist.get_rank() == src:
-        blk = lidar if lidar is not None else RgLidarParams()
+        blk = block if block is not None else struct()
         buf = torch.frombuffer(bytearray(ctypes.string_at(ctypes.addressof(blk), n)), dtype=torch.uint8).to(device)
     else:
         buf = torch.zeros(n, dtype=torch.uint8, device=device)
     dist.broadcast(buf, src=src)
-    out = RgLidarParams()
+    out = struct()
     ctypes.memmove(ctypes.addressof(out), buf.cpu().numpy().tobytes(), n)
-    return out if out.rays > 0 else None
+    return None if next(b for b in SIDE_BLOCKS if b.attr == attr).off(out) else out
+
+
+def broadcast_lidar(lidar, src=0, device=None):
+    """The lidar block next to the parameter block: rank `src` sends its RgLidarParams (None = no lidar, sent as rays = 0);
+    every rank returns a copy of it, or None.  Every rank calls it (a collective), whatever its own argument."""
+    from ._lib import RgLidarParams
+    return _broadcast_block("lidar", RgLidarParams, lidar, src, device)
 
 
 def broadcast_disturbance(disturbance, src=0, device=None):
     """The disturbance block next to the parameter block: rank `src` sends its RgDisturbanceParams (None = none, sent as zeros);
     every rank returns a copy of it, or None.  Every rank calls it (a collective), whatever its own argument."""
-    import ctypes
     from ._lib import RgDisturbanceParams
-    if not dist.is_initialized():
-        return disturbance
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    device = collective_device(device)
-    n = ctypes.sizeof(RgDisturbanceParams)
-    if dist.get_rank() == src:
-        blk = disturbance if disturbance is not None else RgDisturbanceParams()
-        buf = torch.frombuffer(bytearray(ctypes.string_at(ctypes.addressof(blk), n)), dtype=torch.uint8).to(device)
-    else:
-        buf = torch.zeros(n, dtype=torch.uint8, device=device)
-    dist.broadcast(buf, src=src)
-    out = RgDisturbanceParams()
-    ctypes.memmove(ctypes.addressof(out), buf.cpu().numpy().tobytes(), n)
-    return out if (out.sigma_xy != 0.0 or out.sigma_theta != 0.0) else None
+    return _broadcast_block("disturbance", RgDisturbanceParams, disturbance, src, device)
 
 
 def broadcast_teams(teams, src=0, device=None):

@@ -16,6 +16,7 @@ import json
 import torch
 
 from . import _args, _lib
+from .params import SIDE_BLOCKS
 
 
 DEFAULT_PACK_GRU = "f16x2"   # what pack_gru=True means
@@ -226,10 +227,9 @@ def one_launch_refusals(env, actor=None, append_agent_id=True):
     attributes alone), then the actor's.  actor=None: the env's part only, for a caller that has not looked at its actor yet."""
     if int(env.params.qp_mode) != 0:
         raise ValueError("one launch: the interior-point mode (barrier_solver: cvxopt) is not supported")
-    for attr, what in (("teams", "a team pool (teams)"), ("lidar", "the lidar observation (lidar_rays > 0)"),
-                       ("disturbance", "the pose disturbance (pose_noise_xy / pose_noise_theta)")):
-        if getattr(env, attr, None) is not None:
-            raise ValueError(f"one launch: an env with {what} is not supported; use the two-launch path")
+    for b in sorted(SIDE_BLOCKS, key=lambda b: b.attr != "teams"):   # (the pool is asked first, the others in the table's order)
+        if getattr(env, b.attr, None) is not None:
+            raise ValueError(f"one launch: an env with {b.one_launch} is not supported; use the two-launch path")
     if actor is None:
         return
     if not (actor.use_rnn and actor.pack_gru == "f16x2"):

@@ -5,6 +5,7 @@ constructors (PredatorCapturePrey.py:15-59, warehouse.py:48-82, MaterialTranspor
 plus the rps constants of SURVEY.md Appendix A and the reset geometry of misc.py:49-63.
 All derived integers (grid sizes) are computed in float64 exactly as the reference does.
 """
+import collections
 import ctypes
 import math
 import os
@@ -314,10 +315,7 @@ def disturbance_params(scenario, cfg, params):
     sxy, sth = disturbance_config(cfg)
     if sxy == 0.0 and sth == 0.0:
         return None
-    if lidar_config(cfg)[0] > 0:
-        raise ValueError("pose_noise_xy / pose_noise_theta: the pose disturbance does not combine with the lidar (lidar_rays > 0)")
-    if cfg.get("teams") is not None:
-        raise ValueError("pose_noise_xy / pose_noise_theta: the pose disturbance does not combine with a team pool (teams)")
+    refuse_second_block("disturbance", lambda b: b.configured(cfg), "pose_noise_xy / pose_noise_theta")
     dp = RgDisturbanceParams()
     # (a bound rounded to binary32 may lie above it -- 0.1 does: the library compares in binary32 too)
     dp.sigma_xy, dp.sigma_theta = float(np.float32(sxy)), float(np.float32(sth))
@@ -382,8 +380,7 @@ def team_pool(scenario, cfg, params):
         return None
     if scenario == "ArcticTransport":
         raise ValueError("teams: ArcticTransport's agent types are fixed by the scenario (ArcticTransport.py:26-33); it takes no team pool")
-    if lidar_config(cfg)[0] > 0:
-        raise ValueError("teams: a team pool does not combine with the lidar (lidar_rays > 0)")
+    refuse_second_block("teams", lambda b: b.configured(cfg), "teams")
     if isinstance(teams, (str, bytes)) or not isinstance(teams, (list, tuple)) or not 1 <= len(teams) <= TEAM_MAX_SETS:
         raise ValueError(f"teams must be a list of 1..{TEAM_MAX_SETS} capability sets (got {teams!r:.80})")
     N = int(params.n_agents)
@@ -419,6 +416,36 @@ def team_pool(scenario, cfg, params):
             tables[caps[name]][t] = fv
     return TeamPool(TEAM_SAMPLING[sampling], tables["agent_step"], tables["sensing_radius"], tables["capture_radius"],
                     tables["torque"])
+
+
+# ------------------------------------------------------------------ the side blocks
+# What a handle can have on next to its parameter block -- at most ONE (the step kernels come in one family per block,
+# csrc/launch_plan.h) -- a row each, in the order they were added:
+#   attr        the keyword and attribute of VecRobotariumEnv that holds the block (None = off)
+#   what, keys  how a message names the block, and the config keys that switch it on
+#   one_launch  how evaluate.one_launch_refusals names it
+#   configured  cfg -> the config switches it on;  read  (scenario, cfg, params) -> the block, or None
+#   off         block -> it counts as None
+#   setter      the C entry that takes it;  value_errors = (lo, hi): its return codes in (lo, hi] are a ValueError
+SideBlock = collections.namedtuple("SideBlock", "attr what keys one_launch configured read off setter value_errors")
+SIDE_BLOCKS = (
+    SideBlock("lidar", "the lidar", "lidar_rays > 0", "the lidar observation (lidar_rays > 0)",
+              lambda cfg: lidar_config(cfg)[0] > 0, lidar_params, lambda b: int(b.rays) == 0, "rg_set_lidar", (-60, -50)),
+    SideBlock("teams", "a team pool", "teams", "a team pool (teams)",
+              lambda cfg: cfg.get("teams") is not None, team_pool, lambda b: False, "rg_set_teams", (-70, -60)),
+    SideBlock("disturbance", "the pose disturbance", "pose_noise_xy / pose_noise_theta",
+              "the pose disturbance (pose_noise_xy / pose_noise_theta)", lambda cfg: any(disturbance_config(cfg)), disturbance_params,
+              lambda b: float(b.sigma_xy) == 0.0 and float(b.sigma_theta) == 0.0, "rg_set_disturbance", (-80, -70)),
+)
+
+
+def refuse_second_block(attr, on, prefix):
+    """At most one side block: ValueError if block `attr` is to go on next to a block of an earlier row for which on(row) holds.
+    (A pair is refused once, in the name of its later block; `prefix` is how the caller addresses that one.)"""
+    i = [b.attr for b in SIDE_BLOCKS].index(attr)
+    for other in SIDE_BLOCKS[:i]:
+        if on(other):
+            raise ValueError(f"{prefix}: {SIDE_BLOCKS[i].what} does not combine with {other.what} ({other.keys})")
 
 
 def params_to_bytes(p):

@@ -15,7 +15,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .params import TeamPool, disturbance_params, lidar_params, load_config, make_params, team_pool
+from .params import SIDE_BLOCKS, TeamPool, load_config, make_params, refuse_second_block, team_pool
 
 VIOLATION_MESSAGES = ("", "collision", "boundary", "collision_boundary")  # roboEnv.py:82-94
 
@@ -45,34 +45,28 @@ class VecRobotariumEnv(object):
         self.lib = _lib.load()
         self.scenario = scenario
         self.cfg = None
+        # the side blocks (params.SIDE_BLOCKS): from the config where not given, an "off" one is None, at most one is on
+        blocks = {"lidar": lidar, "teams": teams, "disturbance": disturbance}
         if params is None:
             self.cfg = load_config(scenario, config_path, overrides)
             params = make_params(scenario, self.cfg)
-            if lidar is None:
-                lidar = lidar_params(scenario, self.cfg, params)
-            if teams is None:
-                teams = team_pool(scenario, self.cfg, params)
-            if disturbance is None:
-                disturbance = disturbance_params(scenario, self.cfg, params)
-        if lidar is not None and int(lidar.rays) == 0:
-            lidar = None
+            for b in SIDE_BLOCKS:
+                if blocks[b.attr] is None:
+                    blocks[b.attr] = b.read(scenario, self.cfg, params)
         if teams is not None and not isinstance(teams, TeamPool):
-            teams = team_pool(scenario, {"teams": teams}, params)
-        if teams is not None:
-            if teams.n_agents != int(params.n_agents):
-                raise ValueError(f"teams: the pool is built for {teams.n_agents} agents, the scenario has {int(params.n_agents)}")
-            if lidar is not None:
-                raise ValueError("teams: a team pool does not combine with the lidar (lidar_rays > 0)")
-        if disturbance is not None and float(disturbance.sigma_xy) == 0.0 and float(disturbance.sigma_theta) == 0.0:
-            disturbance = None
-        if disturbance is not None and lidar is not None:
-            raise ValueError("disturbance: the pose disturbance does not combine with the lidar (lidar_rays > 0)")
-        if disturbance is not None and teams is not None:
-            raise ValueError("disturbance: the pose disturbance does not combine with a team pool (teams)")
+            blocks["teams"] = team_pool(scenario, {"teams": teams}, params)
+        if blocks["teams"] is not None and blocks["teams"].n_agents != int(params.n_agents):
+            raise ValueError(f"teams: the pool is built for {blocks['teams'].n_agents} agents, the scenario has {int(params.n_agents)}")
+        for b in SIDE_BLOCKS:
+            if blocks[b.attr] is not None and b.off(blocks[b.attr]):
+                blocks[b.attr] = None
+            if blocks[b.attr] is not None:
+                refuse_second_block(b.attr, lambda other: blocks[other.attr] is not None, b.attr)
+            # lidar: RgLidarParams, the last lidar.rays columns of every observation row; teams: params.TeamPool;
+            # disturbance: RgDisturbanceParams, every step displaces the stored poses first; or None
+            setattr(self, b.attr, blocks[b.attr])
+        teams = self.teams
         self.params = params
-        self.disturbance = disturbance   # RgDisturbanceParams or None: every step displaces the stored poses first
-        self.teams = teams   # params.TeamPool or None
-        self.lidar = lidar   # RgLidarParams or None: the last lidar.rays columns of every observation row
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.RobogymError("VecRobotariumEnv runs on an AMD GPU only (device='cuda:N'); no CPU path exists")
@@ -152,31 +146,23 @@ class VecRobotariumEnv(object):
             self.next_episode.data_ptr() if self.next_episode is not None else None)
         _lib.check(self.lib.rg_bind_state(self._h, C.byref(st)), "rg_bind_state")
         self._state = st   # (render() reads the same arrays through the handle-free rg_render)
-        if self.lidar is not None:
-            rc = self.lib.rg_set_lidar(self._h, C.byref(self.lidar))
-            if rc != 0:
-                msg = "rg_set_lidar failed (%d): %s" % (rc, self.lib.rg_last_error().decode())
-                self.lib.rg_destroy(self._h)
-                self._h = None
-                raise (ValueError if -60 < rc <= -50 else _lib.RobogymError)(msg)
         if self.teams is not None:
             tt = self.team_table
             self._team_params = _lib.RgTeamParams(self.teams.n_sets, self.teams.mode, tt["agent_step"].data_ptr(),
                                                   tt["sensing_radius"].data_ptr(), tt["capture_radius"].data_ptr(),
                                                   tt["torque"].data_ptr(), self.team_index.data_ptr())
-            rc = self.lib.rg_set_teams(self._h, C.byref(self._team_params))
+        for b in SIDE_BLOCKS:
+            block = getattr(self, b.attr)
+            if block is None:
+                continue
+            # (the pool goes down as its device tables)
+            rc = getattr(self.lib, b.setter)(self._h, C.byref(self._team_params if block is self.teams else block))
             if rc != 0:
-                msg = "rg_set_teams failed (%d): %s" % (rc, self.lib.rg_last_error().decode())
+                msg = "%s failed (%d): %s" % (b.setter, rc, self.lib.rg_last_error().decode())
                 self.lib.rg_destroy(self._h)
                 self._h = None
-                raise (ValueError if -70 < rc <= -60 else _lib.RobogymError)(msg)
-        if self.disturbance is not None:
-            rc = self.lib.rg_set_disturbance(self._h, C.byref(self.disturbance))
-            if rc != 0:
-                msg = "rg_set_disturbance failed (%d): %s" % (rc, self.lib.rg_last_error().decode())
-                self.lib.rg_destroy(self._h)
-                self._h = None
-                raise (ValueError if -80 < rc <= -70 else _lib.RobogymError)(msg)
+                lo, hi = b.value_errors
+                raise (ValueError if lo < rc <= hi else _lib.RobogymError)(msg)
         self._io = _lib.RgStepIO(self.obs.data_ptr(), self.reward.data_ptr(), self.done_u8.data_ptr(),
                                  self.dist_travelled.data_ptr(), self.violation.data_ptr(),
                                  self.remaining.data_ptr(),

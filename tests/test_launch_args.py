@@ -100,3 +100,53 @@ def test_exports_and_late_queries_are_what_they_were():
     # every sizeof query is checked against a struct, and only those are
     assert {q for q, _ in _lib.LAYOUTS} == {n for n in EXPORTS if n.startswith("rg_sizeof_")}
     assert len({s for _, s in _lib.LAYOUTS}) == len(_lib.LAYOUTS)
+
+
+def test_group_units_and_side_blocks_come_from_their_tables():
+    """The build's lane-group units are derived from csrc/kernel_args.h RG_GROUP_ENTRIES, the Python side blocks from
+    params.SIDE_BLOCKS: every row of the first is defined by exactly one unit, whose flags are its mode's; the second names
+    exactly the three rg_set_* entries of _lib.ENTRIES."""
+    import os
+    import re
+    from marbler_amd import build, params
+    rows = build.group_rows()
+    assert len(rows) == 21 and len({r[0] for r in rows}) == 21
+    assert {r[1] for r in rows} == {"GROUP_PLAIN", "GROUP_LIDAR", "GROUP_TEAM", "GROUP_DISTURB"} and {r[2] for r in rows} == {"RG_QP_EXACT", "RG_QP_CVXOPT"}
+    by_entry = {r[0]: r for r in rows}
+    slp, ilp, preload = ["-mllvm", "-slp-threshold=-60"], ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
+    units = build.units()
+    assert len({name for name, _, _, _ in units}) == len(units)          # one object file per unit
+    defined = []
+    for name, src, flags, defines in units:
+        if src == build.GROUP_UNIT:
+            (d,) = defines
+            assert d.startswith("RG_UNIT_ROWS=")
+            mine = re.findall(r"X\((\w+),(\w+),(\w+),(\w+)\)", d)
+            assert mine and "".join("X(%s,%s,%s,%s)" % m for m in mine) == d[len("RG_UNIT_ROWS="):]
+            assert all(by_entry[m[0]] == m for m in mine)                 # the rows as the table has them
+            # a family's single launches of one mode, or its rollout alone
+            assert len({m[1:3] for m in mine}) == 1
+            assert [m[3] for m in mine] in (["GROUP_STEP"], ["GROUP_STEP", "GROUP_OBS"], ["GROUP_ROLLOUT"])
+            mine = [m[0] for m in mine]
+        else:
+            with open(os.path.join(build.CSRC, src)) as f:
+                mine = [e for e in re.findall(r"^hipError_t (\w+)\(const KernelArgs &\w+, const GroupSide &", f.read(), re.M) if e in by_entry]
+        defined += mine
+        if mine:
+            modes = {by_entry[e][2] for e in mine}
+            assert len(modes) == 1, (name, modes)
+            resident = {by_entry[e][3] for e in mine} <= {"GROUP_STEP_RESIDENT", "GROUP_STEP_SHAPE"}
+            assert flags == slp + (ilp if modes == {"RG_QP_CVXOPT"} else []) + (preload if resident else []), (name, flags)
+    assert sorted(defined) == sorted(by_entry)                            # every row once, by one unit
+    # the four policy-rollout units: one source, the exact mode's lane-group flags
+    policy = [(flags, sorted(defines)) for _, src, flags, defines in units if src == build.POLICY_UNIT]
+    assert sorted(policy) == sorted((slp, sorted([f"RG_UNIT_H={h}", f"RG_UNIT_SAMPLE={s}"])) for h in (64, 128) for s in (0, 1))
+    # every define and every source is part of what the rebuild check compares
+    stamp = build.flags_stamp()
+    assert all(d in stamp for _, _, _, defines in units for d in defines) and build.GROUP_UNIT in stamp and build.POLICY_UNIT in stamp
+    # the side blocks
+    setters = [n for n, _, _, _ in _lib.ENTRIES if n.startswith("rg_set_") and n != "rg_set_stream"]
+    assert sorted(b.setter for b in params.SIDE_BLOCKS) == sorted(setters) and len(setters) == 3
+    assert [(b.attr, b.setter, b.value_errors) for b in params.SIDE_BLOCKS] == [
+        ("lidar", "rg_set_lidar", (-60, -50)), ("teams", "rg_set_teams", (-70, -60)), ("disturbance", "rg_set_disturbance", (-80, -70))]
+    assert [b.read for b in params.SIDE_BLOCKS] == [params.lidar_params, params.team_pool, params.disturbance_params]
