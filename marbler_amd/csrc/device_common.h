@@ -275,6 +275,19 @@ __device__ __forceinline__ bool group_any(bool pred, int gbase) {
     constexpr unsigned long long GM = (GW == 64) ? ~0ull : ((1ull << GW) - 1ull);
     return ((m >> gbase) & GM) != 0ull;
 }
+#ifndef RG_HOST_SIM
+// ------------------------------------------------------------------ lane predicates as wave masks (the 16-lane-row kernels)
+// A predicate that is carried around a loop, captured by a lambda or assigned under a branch reaches its uses as a 0 / 1 integer in
+// a vector register, and every use turns it back into a mask (v_and, v_cmp_eq; a vote: two v_cndmask, an or, a compare).  Held
+// as the WAVE's mask in a scalar register pair instead -- it is one: such a value is the same in every lane -- it is combined
+// with s_and / s_or / s_andn2, voted on with a scalar compare, and selects with the pair as the operand of v_cndmask.
+// mask_of: the mask of a COMPARE (written in the call: v_cmp's own result; of any other bool the compiler goes through a
+// register).  Wave-uniform control flow with every lane running only: the mask of a lane that is off would read 0.
+typedef unsigned long long lane_mask;
+__device__ __forceinline__ lane_mask mask_of(bool compare) { return __builtin_amdgcn_ballot_w64(compare); }
+// this lane's bit of a mask, as the predicate of a select or a branch
+__device__ __forceinline__ bool mask_lane(lane_mask m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+#endif
 
 // ------------------------------------------------------------------ synchronisation of the step's one wavefront
 // The step and reset code below assumes a ONE-wave workgroup: its barriers make LDS (and the wave's own global stores) visible

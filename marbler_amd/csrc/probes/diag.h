@@ -10,7 +10,7 @@
 //   RG_TPE_DIAG              thread-per-env kernel: replayed-chunk mask and per-controller sweep counts in io.qp_sweeps
 //   RG_TPE_GUARD             thread-per-env kernel: stores through the LDS staging block are bounds-checked
 //   RG_HOST_SIM              the kernels compiled for the host (tests/sanitize/): 64 threads = 64 lanes
-// and the tuning constants RG_CHUNK, RG_MAX_WAVES, RG_ROW_ARG_REGS / SWAP_HALVES, RG_TPE_W4 / W5 / W78, RG_TPE_NO_W3
+// and the tuning constants RG_CHUNK, RG_MAX_WAVES, RG_ROW_ARG_REGS / SWAP_HALVES, RG_ROW_PRED_MASKS, RG_SHAPE_SCHEDULE, RG_TPE_W4 / W5 / W78, RG_TPE_NO_W3
 // (A/B builds), and RG_SHAPE_FIELDS (kernel_args.h: which fields of the reference shapes are compiled in; 127 = all seven).
 // One-off probes of rounds 2-4 (shadow copies, RG_PROBE_*, RG_FIXED_U, RG_DENSE_PRETEST, RG_NT_STORES, RG_NO_XCD_REMAP,
 // RG_TPE_NO_DMAX_GUARD) were removed in round 5; what they measured is in NOTEBOOK.md and profiles/, the code in git history.
@@ -29,6 +29,13 @@
 #endif
 #ifndef RG_ROW_SWAP_HALVES
 #define RG_ROW_SWAP_HALVES 1   // controller set-up: the replica's pair constants cross by an untied move
+#endif
+// the 16-lane-row kernels' sub-step loop, one switch per part (A/B builds; NOTEBOOK.md "lane predicates as masks"): 1 = shipped
+#ifndef RG_ROW_PRED_MASKS
+#define RG_ROW_PRED_MASKS 1    // lane predicates (live, dead, the pre-tests' hits) as wave masks in scalar register pairs
+#endif
+#ifndef RG_SHAPE_SCHEDULE
+#define RG_SHAPE_SCHEDULE 1    // reference shapes: the chunk schedule of a period from the shape's U and PERIOD
 #endif
 #ifndef RG_TPE_W4
 #define RG_TPE_W4 3   // waves per SIMD the N <= 4 instantiations are compiled for

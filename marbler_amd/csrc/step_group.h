@@ -393,6 +393,15 @@ __device__ __forceinline__ void write_neighbour_obs(Lds<GW> &lds, int N, int Knb
 }
 
 // ------------------------------------------------------------------ the step kernel
+// The lane predicates of the row kernels' sub-step loop as wave masks (device_common.h lane_mask; step_once PM): the envs of the
+// launch and their agents' lanes; the envs still running (env & !dead) and their agents' lanes (lane & !dead); the envs that ended
+// in this controller period (died_now); the lanes whose env cannot use the sparse pre-test in this period (lane & !sparse_ok).
+struct RowMasks {
+    lane_mask env, lane, alive, live, died, dense;
+};
+struct NoRowMasks {   // (every other kernel: nothing to hold; the names exist for the dead side of `PM ? ... : ...`)
+    static constexpr lane_mask env = 0, lane = 0, alive = 0, live = 0, died = 0, dense = 0;
+};
 // NT: the agent count when it is a compile-time constant (instantiated for GW = 8: 5..8), 0 = read
 // it from the parameter block.  One env step of the wave's envs; `sv` = this step's slice of the
 // action and output arrays.
@@ -437,6 +446,10 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     // RG_ARG_OR(a.x, q): the same for an argument the prologue holds as q.  (Macros, and a conditional on a constant, of which
     // the compiler emits the live side only: every other kernel is compiled from the plain member access, as before.)
     constexpr bool ARGV = SPAN && RG_ROW_ARG_REGS != 0;
+    constexpr bool SCHED = SPAN && RG_SHAPE_SCHEDULE != 0 && SH::U > 0 && SH::PERIOD > 0;   // the chunk schedule from the shape (below, at run_chunk)
+    // PM: the lane predicates of the sub-step loop as wave masks (below, at `dead`).  The resident row kernels: the ones a handle
+    // runs; the by-value row kernels (a handle without an image, RG_STEP_RESIDENT=0) stay as they were.
+    constexpr bool PM = SPAN && RES && RG_ROW_PRED_MASKS != 0;
     // RES (the resident form, kernel_args.h): `a` is the handle's image, read like the kernel arguments, and the per-call arguments
     // come through `sv`; in the registers they are the fifth (device_common.h resident_arg_off).
     int av[ARG_REGS] = {0, 0, 0, 0, 0};
@@ -521,6 +534,11 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
     const bool env_ok = (g < epw) & (e < q_E);
     const bool lane_ok = env_ok && ag < N;
     const bool env_st = env_ok & !helper, lane_st = lane_ok & !helper;   // the lanes that store
+    std::conditional_t<PM, RowMasks, NoRowMasks> rm;                     // PM: env_ok, lane_ok as wave masks (below, at `dead`)
+    if constexpr (PM) {
+        rm.env = mask_of(g < epw) & mask_of(e < q_E);
+        rm.lane = rm.env & mask_of(ag < N);
+    }
     const bool lane_nb = SPAN ? lane_ok : lane_st;                       // ... the neighbour rows (write_neighbour_obs)
     const size_t eN = static_cast<size_t>(e) * N;
 
@@ -774,6 +792,15 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         RG_CTRL_LOCALS()
         float acc = carry, last = 0.0f;  // dist incl. the pending sub-step; length of the last sub-step
         bool dead = false;               // group-uniform: the env hit a violation (roboEnv.py:92-94)
+        // PM (the resident row kernels): `dead` and every predicate formed from it as wave masks in scalar registers (device_common.h
+        // lane_mask; RowMasks above) -- a bool that is carried around the period and chunk loops and assigned in the replay reaches
+        // its uses as an integer in a vector register, turned back into a mask by each of them.  The masks change in the replay
+        // alone.  (Every use is under `if constexpr (PM)` or the live side of `PM ? ... : ...`: the other kernels are compiled from
+        // the statements they had, and stay instruction-identical.)
+        if constexpr (PM) {
+            rm.alive = rm.env;
+            rm.live = rm.lane;
+        }
         float fin_x = 0.0f, fin_y = 0.0f;
         // x, y = period base (bx, by) + displacement since the period began (ox, oy): a sub-step adds
         // dt*v*(cos, sin) to the small displacement and the position is the single rounding bx + ox, so the
@@ -784,7 +811,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         for (int it0 = 0; it0 < U; it0 += period) {
             const int n = (U - it0) < period ? (U - it0) : period;
             RG_HEADING_SINCOS(th, s, c);
-            const int sw = controller<GW, QPM, QpLds, SPAN>(p, k, N, ag, lane_ok, env_ok & !dead, x, y, c, s, gx, gy, v, w, qp_lds RG_CTRL_TICKS_ARG);
+            const int sw = controller<GW, QPM, QpLds, SPAN>(p, k, N, ag, lane_ok, PM ? mask_lane(rm.alive) : env_ok & !dead, x, y, c, s, gx, gy, v, w, qp_lds RG_CTRL_TICKS_ARG);
             max_sweeps = sw > max_sweeps ? sw : max_sweeps;
             const float dtv = k.dt * v, dtw = k.dt * w;
             float sd, cd;
@@ -800,6 +827,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             const float mrg = __builtin_fmaf((CHUNK - 1) * 1.000001f, __builtin_fabsf(dtv), PRE_SLACK);
             int n_exec = n;             // sub-steps this env executes in this period
             bool died_now = false;
+            if constexpr (PM) rm.died = 0;
             // SPARSE collision pre-test (kernel_args.h): v and w are constant inside the period, so between two sub-steps
             // a robot's collision point moves at most |dt v| (the body) + coll_off |dt w| (the chord of its turn) per
             // sub-step.  A test of sub-step u against a threshold widened by the travel of BOTH robots over `span` further
@@ -816,20 +844,26 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
             const int thr_s1 = thr_span(1), thr_s2 = thr_span(2);
             // the binary16 rounding bound behind lin_pre holds for differences below 0.25 m per axis
             const bool sparse_ok = (k.lin_pre + 2.0f * M2) < 0.24f;
+            if constexpr (PM) rm.dense = rm.lane & ~mask_of((k.lin_pre + 2.0f * M2) < 0.24f);
 
             // C sub-steps starting at sub-step j0 of this period
             auto run_chunk = [&](auto CC, int j0) {
                 constexpr int C = decltype(CC)::value;
                 const float x0 = x, y0 = y, ox0 = ox, oy0 = oy, c0 = c, s0 = s;
-                const bool live = lane_ok & !dead;
+                const bool live = PM ? mask_lane(rm.live) : lane_ok & !dead;
                 int q[C];
                 // every pre-update position of the chunk lies within (C-1)|dt v| of the first
                 const bool bnd_any = live & ((__builtin_fabsf(x - k.xc) + mrg > k.xh) | (__builtin_fabsf(y - k.yc) + mrg > k.yh));
+                lane_mask out_m = 0, hit_m = 0;   // PM: bnd_any before `live`; the pre-test's own hits (sparse_hit without `live & !sparse_ok`)
+                int q03 = 0;                      // PM: the point the sparse pre-test of this half of the row reads
+                if constexpr (PM) out_m = mask_of(__builtin_fabsf(x - k.xc) + mrg > k.xh) | mask_of(__builtin_fabsf(y - k.yc) + mrg > k.yh);
                 static_for<0, C>([&](auto UU) {
                     constexpr int u = decltype(UU)::value;
                     const float fx = __builtin_fmaf(k.coll_off, c, x), fy = __builtin_fmaf(k.coll_off, s, y);
                     const int qr = __builtin_bit_cast(int, __builtin_amdgcn_cvt_pkrtz(fx, fy));
                     q[u] = live ? qr : ghost_q;
+                    // (one select between the halves' sub-steps, one against the ghost: q[0], q[3] are then the dense path's only)
+                    if constexpr (PM && C >= 4 && (u == 0 || u == 3)) q03 = helper == (u == 3) ? qr : q03;
                     // Euler step (Appendix A.4); rotate (cos, sin) by dt*w
                     ox = __builtin_fmaf(c, dtv, ox);
                     oy = __builtin_fmaf(s, dtv, oy);
@@ -875,20 +909,23 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                         // the group tests sub-step 0, its replica sub-step 3; the wave's vote below ORs the two halves' hits,
                         // and each half's minimum goes across only if the chunk goes on to the dense pre-test
                         const int t3 = C == 4 ? thr_pre : thr_s1;
-                        const int dm = pair_min(helper ? q[3] : q[0]);
+                        const int dm = pair_min(PM ? (live ? q03 : ghost_q) : helper ? q[3] : q[0]);
                         sparse_hit = sparse_hit | (dm <= (helper ? t3 : t0));
+                        if constexpr (PM) hit_m = mask_of(dm <= (helper ? t3 : t0));
                         dmin_u[0] = dmin_u[3] = dm;
                     } else {
                         dmin_u[0] = pair_min(q[0]);
                         sparse_hit = sparse_hit | (dmin_u[0] <= t0);
+                        if constexpr (PM) hit_m = mask_of(dmin_u[0] <= t0);
                         if constexpr (C >= 4) {
                             const int t3 = C == 4 ? thr_pre : thr_s1;
                             dmin_u[3] = pair_min(q[3]);
                             sparse_hit = sparse_hit | (dmin_u[3] <= t3);
+                            if constexpr (PM) hit_m |= mask_of(dmin_u[3] <= t3);
                         }
                     }
                 }
-                if (penalize && __any(sparse_hit | bnd_any)) {
+                if (penalize && (PM ? (hit_m | (rm.live & (out_m | rm.dense))) != 0 : __any(sparse_hit | bnd_any))) {
                 RG_CHUNK_DENSE_BEGIN()
                 if constexpr (SPAN && C >= 4) {  // sub-step 0's minimum from the group, 3's from the replica, into both halves
                     const int mine = dmin_u[0], other = xor_lane_i<8>(mine);
@@ -909,7 +946,7 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                 int dmin = dmin_u[0];
                 static_for<1, C>([&](auto UU) { dmin = dmin_u[decltype(UU)::value] < dmin ? dmin_u[decltype(UU)::value] : dmin; });
                 RG_CHUNK_DENSE_END(dmin)
-                if (__any((dmin <= thr_pre) | bnd_any)) {
+                if (PM ? (mask_of(dmin <= thr_pre) | (rm.live & out_m)) != 0 : __any((dmin <= thr_pre) | bnd_any)) {
                     replayed = true;
                     // rare: replay the chunk with the exact float tests of _validate (roboEnv.py:82-94): the
                     // boundary test on every sub-step (per lane, cheap), the pair rounds only on the sub-steps
@@ -918,7 +955,8 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                     float rx = x0, ry = y0, rox = ox0, roy = oy0, rc = c0, rs = s0;
                     static_for<0, C>([&](auto UU) {
                         constexpr int u = decltype(UU)::value;
-                        const bool bnd = lane_ok & !dead & ((rx < k.xmin) | (rx > k.xmax) | (ry < k.ymin) | (ry > k.ymax));
+                        // (`dead` changes from sub-step to sub-step here, and rm.live with it)
+                        const bool bnd = (PM ? mask_lane(rm.live) : lane_ok & !dead) & ((rx < k.xmin) | (rx > k.xmax) | (ry < k.ymin) | (ry > k.ymax));
                         const float fx = __builtin_fmaf(k.coll_off, rc, rx), fy = __builtin_fmaf(k.coll_off, rs, ry);
                         bool col = false;
                         // The binary16 figure is a bound for collision points within 0.25 m of the arena only (kernel_args.h).
@@ -949,19 +987,26 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                                 col = col | (((ag ^ K) < N) & (dx * dx + dy * dy <= k.coll_lim2));
                             });
                         }
-                        col = col & lane_ok & !dead;
+                        col = PM ? col & mask_lane(rm.live) : col & lane_ok & !dead;
                         const int code = (group_any<GW>(col, gbase) ? 1 : 0) | (group_any<GW>(bnd, gbase) ? 2 : 0);
                         rox = __builtin_fmaf(rc, dtv, rox);  // the violating sub-step is still integrated
                         roy = __builtin_fmaf(rs, dtv, roy);
                         rx = bx + rox;
                         ry = by + roy;
-                        if (env_ok & !dead & (code != 0)) {
+                        lane_mask die_m = 0;   // PM: the envs that end in this sub-step
+                        if constexpr (PM) die_m = rm.alive & mask_of(code != 0);
+                        if (PM ? mask_lane(die_m) : env_ok & !dead & (code != 0)) {
                             viol = code;
                             n_exec = j0 + u + 1;
                             died_now = true;
                             dead = true;
                             fin_x = rx;
                             fin_y = ry;
+                        }
+                        if constexpr (PM) {
+                            rm.alive &= ~die_m;
+                            rm.live &= ~die_m;
+                            rm.died |= die_m;
                         }
                         const float cn = __builtin_fmaf(rc, cd, -(rs * sd));
                         const float sn = __builtin_fmaf(rs, cd, rc * sd);
@@ -972,14 +1017,33 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                 }
                 }
             };
+            if constexpr (SCHED) {
+                // The shape fixes the schedule: every period but the last is F full chunks and a remainder of R sub-steps, the last
+                // one FL and RL.  The FC full chunks both kinds have are one loop to a constant bound; ONE decision -- is this the
+                // last period? -- picks what follows, at constant j0, nothing where a remainder is 0: in place of the loop to a
+                // run-time bound and the chain of tests on n - j.  (29 sub-steps in periods of 15: 5 5 | 5, then 5 5 | 4.)  The loop
+                // stays rolled: each copy of a chunk carries its dense pre-test and its replay.
+                constexpr int PER = SH::PERIOD, LASTN = SH::U - PER * ((SH::U - 1) / PER);
+                constexpr int F = PER / CHUNK, R = PER % CHUNK, FL = LASTN / CHUNK, RL = LASTN % CHUNK, FC = F < FL ? F : FL;
+#pragma nounroll
+                for (int j = 0; j < FC * CHUNK; j += CHUNK) run_chunk(std::integral_constant<int, CHUNK>{}, j);
+                if (it0 + PER < SH::U) {
+                    static_for<FC, F>([&](auto II) { run_chunk(std::integral_constant<int, CHUNK>{}, decltype(II)::value * CHUNK); });
+                    if constexpr (R > 0) run_chunk(std::integral_constant<int, R>{}, F * CHUNK);
+                } else {
+                    static_for<FC, FL>([&](auto II) { run_chunk(std::integral_constant<int, CHUNK>{}, decltype(II)::value * CHUNK); });
+                    if constexpr (RL > 0) run_chunk(std::integral_constant<int, RL>{}, FL * CHUNK);
+                }
+            } else {
             int j = 0;
             for (; j + CHUNK <= n; j += CHUNK) run_chunk(std::integral_constant<int, CHUNK>{}, j);
             static_for<1, CHUNK>([&](auto RR) {  // the remainder as one shorter chunk
                 if (n - j == decltype(RR)::value) run_chunk(RR, j);
             });
+            }
 
             // period end: heading and distance for the sub-steps this env executed
-            const bool upd = env_ok & (!dead | died_now);
+            const bool upd = PM ? mask_lane(rm.alive | rm.died) : env_ok & (!dead | died_now);
             const float ne = static_cast<float>(n_exec);
             const float adv = __builtin_fabsf(dtv);
             th = upd ? wrap_spec(__builtin_fmaf(ne, dtw, th)) : th;
@@ -993,9 +1057,9 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
                 by = y;
             }
             if (it0 == 0) RG_STAMP(2);  // first period done
-            if (!__any(env_ok & !dead)) break;
+            if (PM ? rm.alive == 0 : !__any(env_ok & !dead)) break;
         }
-        if (dead) {
+        if (PM ? mask_lane(rm.env & ~rm.alive) : dead) {
             x = fin_x;
             y = fin_y;
         }
@@ -1598,7 +1662,9 @@ __device__ __forceinline__ void step_once(const KernelArgs &a, Lds<GW> &lds, con
         // A wavefront that is already long -- a QP of one of its envs needed more than two sweeps, or a chunk was
         // replayed -- leaves the draw to a later launch (an env that finishes before it happened runs the sampler as
         // before): the draw must not lengthen the waves the launch is waiting for.
-        if (AHEAD && ahead_e && !(replayed | __any(max_sweeps > 2)) && __any(env_ok & !ended & !have_next)) {
+        // (PM: "not a long wavefront" is the same in every lane and goes into the vote: one branch less on the common path)
+        if (PM ? AHEAD && ahead_e && __any(!(replayed | __any(max_sweeps > 2)) & env_ok & !ended & !have_next)
+               : AHEAD && ahead_e && !(replayed | __any(max_sweeps > 2)) && __any(env_ok & !ended & !have_next)) {
             const bool need = env_st & !ended & !have_next;
             Sync::sync();  // (LDS scratch of a reset above is free again)
             reset_group<SCN, GW, Sync>(RG_SAMPLER_ARGS, lds, e, g, ag, need, rc_raw, reset_dst_next(RG_SAMPLER_ARGS, e), sv.seed);
