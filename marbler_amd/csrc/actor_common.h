@@ -81,6 +81,14 @@ struct ActorArgs {
     float *prob;            // [E][N] or NULL: the probability the sampled action had
 };
 
+// ---- the launch's arithmetic, on the host: what rg_actor_forward*, rg_actor_unroll and rg_policy_rollout each need of it
+static_assert(MAX_IP % 8 == 0, "so that a padded width is within MAX_IP exactly when the width is");
+inline bool input_width_fits(int64_t in_dim) { return in_dim <= MAX_IP; }
+inline int padded_input_width(int in_dim) { return (in_dim + 7) / 8 * 8; }   // ActorArgs::ip, of a width that fits
+// shared weights: tiles of the flat [B * N] row space; otherwise a tile takes rows of ONE agent index (RG_ACTOR_LOCATE)
+inline int64_t actor_tiles(int n_sets, int64_t B, int64_t N) { return n_sets == 1 ? (B * N + TM - 1) / TM : N * ((B + TM - 1) / TM); }
+inline float explore_scale(const float *explore_u, int n_actions, float epsilon) { return explore_u ? static_cast<float>(n_actions) / epsilon : 0.0f; }
+
 // gate nonlinearities on the hardware exponential (v_exp_f32, ~1 ulp on 2^t): absolute error ~1e-7 on
 // outputs in [0, 1] / [-1, 1], far inside the 1e-5 parity bar, at a tenth of libm's instruction count
 // (v_rcp_f32 is within 1 ulp; `1.0f / x` would be the ten-instruction correctly rounded division, 48 times per lane and tile)

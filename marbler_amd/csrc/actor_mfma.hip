@@ -33,10 +33,12 @@
 //   so the whole tile uses one weight set.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
+
+#include <type_traits>
 
 #include "../../include/robogym.h"
 #include "actor_common.h"
+#include "host_checks.h"
 
 namespace rg {
 
@@ -154,56 +156,53 @@ __global__ void pack_gru_f16x2_kernel(const float *src, uint16_t *dst, int n_set
 
 static thread_local char g_actor_err[256] = "";
 
-extern "C" int rg_actor_pack_gru_f16x2(const float *src, int32_t n_sets, int32_t hidden_dim, void *dst, void *hip_stream) {
-    if (!src || !dst || n_sets < 1 || (hidden_dim != 64 && hidden_dim != 128)) {
-        snprintf(g_actor_err, sizeof(g_actor_err), "rg_actor_pack_gru_f16x2: NULL array, n_sets < 1 or hidden_dim not 64 / 128");
-        return -1;
-    }
-    if (reinterpret_cast<uintptr_t>(dst) & 15u) {
-        snprintf(g_actor_err, sizeof(g_actor_err), "rg_actor_pack_gru_f16x2: dst must be 16-byte aligned");
-        return -9;
-    }
-    hipLaunchKernelGGL(rg::pack_gru_f16x2_kernel, dim3(256), dim3(256), 0, static_cast<hipStream_t>(hip_stream), src,
-                       static_cast<uint16_t *>(dst), n_sets, hidden_dim);
+// the three pack entries: one check (rg_actor_pack_gru's float32 order takes any dst: align 1), one launch
+template <class T>
+static int pack_gru(const char *entry, void (*kernel)(const float *, T *, int, int), size_t align, const float *src, int32_t n_sets,
+                    int32_t hidden_dim, void *dst, void *hip_stream) {
+    const rg::Fail fail{g_actor_err, sizeof(g_actor_err), entry};
+    if (!src || !dst || n_sets < 1 || (hidden_dim != 64 && hidden_dim != 128)) return fail(-1, "NULL array, n_sets < 1 or hidden_dim not 64 / 128");
+    if (!rg::all_aligned(align, dst)) return fail(-9, "dst must be 16-byte aligned");
+    hipLaunchKernelGGL(kernel, dim3(256), dim3(256), 0, static_cast<hipStream_t>(hip_stream), src, static_cast<T *>(dst), n_sets, hidden_dim);
     return hipGetLastError() == hipSuccess ? 0 : -30;
+}
+
+extern "C" int rg_actor_pack_gru_f16x2(const float *src, int32_t n_sets, int32_t hidden_dim, void *dst, void *hip_stream) {
+    return pack_gru("rg_actor_pack_gru_f16x2", rg::pack_gru_f16x2_kernel, 16, src, n_sets, hidden_dim, dst, hip_stream);
 }
 
 extern "C" int rg_actor_pack_gru_bf16x3(const float *src, int32_t n_sets, int32_t hidden_dim, void *dst, void *hip_stream) {
-    if (!src || !dst || n_sets < 1 || (hidden_dim != 64 && hidden_dim != 128)) {
-        snprintf(g_actor_err, sizeof(g_actor_err), "rg_actor_pack_gru_bf16x3: NULL array, n_sets < 1 or hidden_dim not 64 / 128");
-        return -1;
-    }
-    if (reinterpret_cast<uintptr_t>(dst) & 15u) {
-        snprintf(g_actor_err, sizeof(g_actor_err), "rg_actor_pack_gru_bf16x3: dst must be 16-byte aligned");
-        return -9;
-    }
-    hipLaunchKernelGGL(rg::pack_gru_bf16x3_kernel, dim3(256), dim3(256), 0, static_cast<hipStream_t>(hip_stream), src,
-                       static_cast<uint16_t *>(dst), n_sets, hidden_dim);
-    return hipGetLastError() == hipSuccess ? 0 : -30;
+    return pack_gru("rg_actor_pack_gru_bf16x3", rg::pack_gru_bf16x3_kernel, 16, src, n_sets, hidden_dim, dst, hip_stream);
 }
 
 extern "C" int rg_actor_pack_gru(const float *src, int32_t n_sets, int32_t hidden_dim, float *dst, void *hip_stream) {
-    if (!src || !dst || n_sets < 1 || (hidden_dim != 64 && hidden_dim != 128)) {
-        snprintf(g_actor_err, sizeof(g_actor_err), "rg_actor_pack_gru: NULL array, n_sets < 1 or hidden_dim not 64 / 128");
-        return -1;
-    }
-    hipLaunchKernelGGL(rg::pack_gru_kernel, dim3(256), dim3(256), 0, static_cast<hipStream_t>(hip_stream), src, dst, n_sets,
-                       hidden_dim);
-    return hipGetLastError() == hipSuccess ? 0 : -30;
+    return pack_gru("rg_actor_pack_gru", rg::pack_gru_kernel, 1, src, n_sets, hidden_dim, dst, hip_stream);
 }
 
 extern "C" const char *rg_actor_last_error(void) { return g_actor_err; }
 
 RG_ACTOR_DIAG_ENTRY   // (diagnostic builds: rg_actor_occupancy)
 
+// (hidden_dim, split, sampling), each checked by the caller -> the kernel's template arguments, as integral constants
+template <class F>
+static void for_actor_kernel(int hidden_dim, int split, bool sampling, F &&f) {
+    using std::integral_constant;
+    auto with = [&](auto h, auto s) { sampling ? f(h, s, std::true_type()) : f(h, s, std::false_type()); };
+    switch (hidden_dim * 4 + split) {
+        case 64 * 4 + 0: return with(integral_constant<int, 64>(), integral_constant<int, 0>());
+        case 64 * 4 + 1: return with(integral_constant<int, 64>(), integral_constant<int, 1>());
+        case 64 * 4 + 2: return with(integral_constant<int, 64>(), integral_constant<int, 2>());
+        case 128 * 4 + 0: return with(integral_constant<int, 128>(), integral_constant<int, 0>());
+        case 128 * 4 + 1: return with(integral_constant<int, 128>(), integral_constant<int, 1>());
+        case 128 * 4 + 2: return with(integral_constant<int, 128>(), integral_constant<int, 2>());
+    }
+}
+
 static int actor_forward(const rg_actor_weights *w, int32_t num_envs, int32_t n_agents, const float *obs,
                          int32_t obs_dim, int32_t append_agent_id, const uint8_t *restart, float *hidden,
                          float *q, int32_t *actions, const float *explore_u, float epsilon, void *hip_stream,
                          const float *sample_u = nullptr, float *prob = nullptr) {
-    auto fail = [](int code, const char *msg) {
-        snprintf(g_actor_err, sizeof(g_actor_err), "%s", msg);
-        return code;
-    };
+    const rg::Fail fail{g_actor_err, sizeof(g_actor_err), nullptr};
     if (!w || !obs || !hidden) return fail(-1, "weights, obs or hidden is NULL");
     if (!w->w1 || !w->b1 || !w->wih || !w->bih || !w->w2 || !w->b2) return fail(-2, "a weight array is NULL");
     if (w->use_rnn && (!w->whh || !w->bhh)) return fail(-2, "GRU weights whh / bhh are NULL");
@@ -216,11 +215,8 @@ static int actor_forward(const rg_actor_weights *w, int32_t num_envs, int32_t n_
     if (explore_u && !actions) return fail(-11, "explore_u without an actions array");
     const int in_dim = obs_dim + (append_agent_id ? n_agents : 0);
     if (in_dim != w->input_dim) return fail(-7, "obs_dim (+ n_agents with append_agent_id) != the actor's input_dim");
-    const int ip = (in_dim + 7) / 8 * 8;
-    if (ip > rg::MAX_IP) return fail(-8, "input_dim above 64 is not supported");
-    if ((reinterpret_cast<uintptr_t>(hidden) | reinterpret_cast<uintptr_t>(w->w1) | reinterpret_cast<uintptr_t>(w->wih) |
-         reinterpret_cast<uintptr_t>(w->whh) | reinterpret_cast<uintptr_t>(w->w2)) & 15u)
-        return fail(-9, "hidden, w1, wih, whh and w2 must be 16-byte aligned");
+    if (!rg::input_width_fits(in_dim)) return fail(-8, "input_dim above 64 is not supported");
+    if (!rg::all_aligned(16, hidden, w->w1, w->wih, w->whh, w->w2)) return fail(-9, "hidden, w1, wih, whh and w2 must be 16-byte aligned");
     rg::ActorArgs a;
     a.w = *w;
     a.obs = obs;
@@ -229,37 +225,21 @@ static int actor_forward(const rg_actor_weights *w, int32_t num_envs, int32_t n_
     a.q = q;
     a.actions = actions;
     a.explore_u = explore_u;
-    a.explore_scale = explore_u ? static_cast<float>(w->n_actions) / epsilon : 0.0f;
+    a.explore_scale = rg::explore_scale(explore_u, w->n_actions, epsilon);
     a.sample_u = sample_u;
     a.prob = prob;
     a.E = num_envs;
     a.N = n_agents;
     a.D = obs_dim;
     a.append_agent_id = append_agent_id;
-    a.ip = ip;
-    const int tiles = w->n_sets == 1 ? (num_envs * n_agents + rg::TM - 1) / rg::TM
-                                     : n_agents * ((num_envs + rg::TM - 1) / rg::TM);
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    a.ip = rg::padded_input_width(in_dim);
+    const dim3 tiles(static_cast<uint32_t>(rg::actor_tiles(w->n_sets, num_envs, n_agents)));
     const int split = !w->use_rnn ? 0 : w->gru_packed == 2 ? 1 : w->gru_packed == 3 ? 2 : 0;
-    if (sample_u) {
-        if (w->hidden_dim == 64) {
-            if (split == 2) hipLaunchKernelGGL((rg::actor_sample_kernel<64, 2>), dim3(tiles), dim3(128), 0, stream, a);
-            else if (split == 1) hipLaunchKernelGGL((rg::actor_sample_kernel<64, 1>), dim3(tiles), dim3(128), 0, stream, a);
-            else hipLaunchKernelGGL((rg::actor_sample_kernel<64, 0>), dim3(tiles), dim3(128), 0, stream, a);
-        } else {
-            if (split == 2) hipLaunchKernelGGL((rg::actor_sample_kernel<128, 2>), dim3(tiles), dim3(256), 0, stream, a);
-            else if (split == 1) hipLaunchKernelGGL((rg::actor_sample_kernel<128, 1>), dim3(tiles), dim3(256), 0, stream, a);
-            else hipLaunchKernelGGL((rg::actor_sample_kernel<128, 0>), dim3(tiles), dim3(256), 0, stream, a);
-        }
-    } else if (w->hidden_dim == 64) {
-        if (split == 2) hipLaunchKernelGGL((rg::actor_kernel<64, 2>), dim3(tiles), dim3(128), 0, stream, a);
-        else if (split == 1) hipLaunchKernelGGL((rg::actor_kernel<64, 1>), dim3(tiles), dim3(128), 0, stream, a);
-        else hipLaunchKernelGGL((rg::actor_kernel<64, 0>), dim3(tiles), dim3(128), 0, stream, a);
-    } else {
-        if (split == 2) hipLaunchKernelGGL((rg::actor_kernel<128, 2>), dim3(tiles), dim3(256), 0, stream, a);
-        else if (split == 1) hipLaunchKernelGGL((rg::actor_kernel<128, 1>), dim3(tiles), dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((rg::actor_kernel<128, 0>), dim3(tiles), dim3(256), 0, stream, a);
-    }
+    for_actor_kernel(w->hidden_dim, split, sample_u != nullptr, [&](auto h, auto s, auto sampling) {
+        constexpr int H = decltype(h)::value, SPLIT = decltype(s)::value;
+        if constexpr (decltype(sampling)::value) hipLaunchKernelGGL((rg::actor_sample_kernel<H, SPLIT>), tiles, dim3(64 * (H / 32)), 0, static_cast<hipStream_t>(hip_stream), a);
+        else hipLaunchKernelGGL((rg::actor_kernel<H, SPLIT>), tiles, dim3(64 * (H / 32)), 0, static_cast<hipStream_t>(hip_stream), a);
+    });
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return fail(-30, hipGetErrorString(err));
     return 0;
@@ -283,14 +263,9 @@ extern "C" int rg_actor_forward_explore(const rg_actor_weights *w, int32_t num_e
 extern "C" int rg_actor_forward_sample(const rg_actor_weights *w, int32_t num_envs, int32_t n_agents, const float *obs,
                                        int32_t obs_dim, int32_t append_agent_id, const uint8_t *restart, float *hidden,
                                        float *q, int32_t *actions, const float *sample_u, float *prob, void *hip_stream) {
-    if (!sample_u) {
-        snprintf(g_actor_err, sizeof(g_actor_err), "rg_actor_forward_sample: sample_u is NULL");
-        return -12;
-    }
-    if (!actions) {
-        snprintf(g_actor_err, sizeof(g_actor_err), "rg_actor_forward_sample: sample_u without an actions array");
-        return -12;
-    }
+    const rg::Fail fail{g_actor_err, sizeof(g_actor_err), "rg_actor_forward_sample"};
+    if (!sample_u) return fail(-12, "sample_u is NULL");
+    if (!actions) return fail(-12, "sample_u without an actions array");
     return actor_forward(w, num_envs, n_agents, obs, obs_dim, append_agent_id, restart, hidden, q, actions, nullptr, 0.0f,
                          hip_stream, sample_u, prob);
 }

@@ -105,8 +105,8 @@ static hipError_t launch_policy_h(const KernelArgs &k, const rg_actor_weights &w
     pa.act.N = k.p.n_agents;
     pa.act.D = k.p.obs_dim;
     pa.act.append_agent_id = io.append_agent_id;
-    pa.act.ip = (w.input_dim + 7) / 8 * 8;
-    pa.act.explore_scale = io.explore_u ? static_cast<float>(w.n_actions) / io.epsilon : 0.0f;
+    pa.act.ip = padded_input_width(w.input_dim);
+    pa.act.explore_scale = explore_scale(io.explore_u, w.n_actions, io.epsilon);
     pa.act.sample_u = sample ? sample->sample_u : nullptr;
     pa.act.prob = sample ? sample->prob : nullptr;
     return for_scenario(k.p.scenario, [&](auto scn) { return launch_policy_scn<decltype(scn)::value, H, SAMPLE>(pa, stream); });

@@ -4,13 +4,14 @@
 // the device: state and outputs live in caller-owned HBM (torch-ROCm tensors).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <new>
 
 #include "../../include/robogym.h"
+#include "actor_common.h"
+#include "host_checks.h"
 #include "kernel_args.h"
 
 struct rg_handle {
@@ -90,10 +91,7 @@ struct DeviceGuard {
     DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
 
-static int fail(int code, const char *fmt, const char *detail = "") {
-    snprintf(g_err, sizeof(g_err), fmt, detail);
-    return code;
-}
+static int fail(int code, const char *fmt, const char *detail = "") { return rg::Fail{g_err, sizeof(g_err), nullptr}.text(code, fmt, detail); }
 
 // The rps constants' admitted domain (include/robogym.h "rps constants"): every limit is stated there with its reason.
 // !(v > lo) also refuses a NaN; the message names the field.
@@ -372,7 +370,7 @@ int rg_bind_state(rg_handle *h, const rg_state *st) {
         case RG_SCN_PREDATOR_CAPTURE_PREY:
             if (!st->prey_loc || !st->prey_sensed || !st->prey_captured)
                 return fail(-21, "PredatorCapturePrey needs prey_loc, prey_sensed, prey_captured");
-            if (reinterpret_cast<uintptr_t>(st->prey_loc) & 7u) return fail(-26, "prey_loc must be 8-byte aligned");
+            if (!rg::all_aligned(8, st->prey_loc)) return fail(-26, "prey_loc must be 8-byte aligned");
             break;
         case RG_SCN_WAREHOUSE:
             if (!st->loaded) return fail(-21, "Warehouse needs loaded");
@@ -383,7 +381,7 @@ int rg_bind_state(rg_handle *h, const rg_state *st) {
         case RG_SCN_ARCTIC_TRANSPORT:
             if (!st->grid || !st->goal_col || !st->pixel_type || !st->reached_goal)
                 return fail(-21, "ArcticTransport needs grid, goal_col, pixel_type, reached_goal");
-            if (reinterpret_cast<uintptr_t>(st->grid) & 3u) return fail(-26, "grid must be 4-byte aligned");
+            if (!rg::all_aligned(4, st->grid)) return fail(-26, "grid must be 4-byte aligned");
             break;
         default:
             if (!st->load || !st->zone_load || !st->messages)
@@ -393,7 +391,7 @@ int rg_bind_state(rg_handle *h, const rg_state *st) {
                       (st->done_steps_sum != nullptr);
     if (nstat != 0 && nstat != 4) return fail(-25, "rollout statistics arrays: set all four or none");
     if ((st->next_init != nullptr) != (st->next_episode != nullptr)) return fail(-25, "next_init / next_episode: set both or none");
-    if (reinterpret_cast<uintptr_t>(st->next_init) & 15u) return fail(-26, "next_init must be 16-byte aligned");
+    if (!rg::all_aligned(16, st->next_init)) return fail(-26, "next_init must be 16-byte aligned");
     h->state = *st;
     h->bound = true;
     refresh(h);
@@ -486,7 +484,7 @@ static int sync_seed(rg_handle *h, uint64_t seed) {
 static int check_io(const rg_step_io *io) {
     if (!io->obs || !io->reward || !io->done || !io->dist_travelled || !io->violation || !io->remaining)
         return fail(-24, "every rg_step_io array except qp_sweeps and the gymma block is required");
-    if (reinterpret_cast<uintptr_t>(io->obs) & 15u) return fail(-26, "obs must be 16-byte aligned");
+    if (!rg::all_aligned(16, io->obs)) return fail(-26, "obs must be 16-byte aligned");
     if (io->elapsed) {
         if (!io->truncated || !io->ended || !io->reward_sum) return fail(-24, "gymma block: elapsed needs truncated, ended and reward_sum");
         if (io->time_limit < 1) return fail(-29, "gymma block: time_limit must be > 0");
@@ -594,13 +592,11 @@ static int policy_rollout(rg_handle *h, const rg_actor_weights *w, int32_t num_s
     if (w->n_sets != 1 && w->n_sets != N) return fail(-43, "rg_policy_rollout: n_sets must be 1 (shared) or n_agents");
     if (w->input_dim != h->params.obs_dim + (pio->append_agent_id ? N : 0))
         return fail(-44, "rg_policy_rollout: the actor's input_dim != obs_dim (+ n_agents with append_agent_id)");
-    if (w->input_dim > 64) return fail(-44, "rg_policy_rollout: input_dim above 64 is not supported");
+    if (!rg::input_width_fits(w->input_dim)) return fail(-44, "rg_policy_rollout: input_dim above 64 is not supported");
     if (w->n_actions < 1 || w->n_actions > 32) return fail(-45, "rg_policy_rollout: n_actions must be in 1..32");
     if (!w->w1 || !w->b1 || !w->wih || !w->bih || !w->whh || !w->bhh || !w->w2 || !w->b2) return fail(-46, "rg_policy_rollout: a weight array is NULL");
     if (!pio->hidden || !pio->actions) return fail(-47, "rg_policy_rollout: hidden and actions are required");
-    if ((reinterpret_cast<uintptr_t>(pio->hidden) | reinterpret_cast<uintptr_t>(pio->obs) | reinterpret_cast<uintptr_t>(w->w1) |
-         reinterpret_cast<uintptr_t>(w->wih) | reinterpret_cast<uintptr_t>(w->whh) | reinterpret_cast<uintptr_t>(w->w2)) & 15u)
-        return fail(-26, "rg_policy_rollout: hidden, obs, w1, wih, whh and w2 must be 16-byte aligned");
+    if (!rg::all_aligned(16, pio->hidden, pio->obs, w->w1, w->wih, w->whh, w->w2)) return fail(-26, "rg_policy_rollout: hidden, obs, w1, wih, whh and w2 must be 16-byte aligned");
     if (pio->explore_u && !(pio->epsilon >= 1e-6f && pio->epsilon <= 1.0f)) return fail(-48, "rg_policy_rollout: epsilon must be in [1e-6, 1] with explore_u");
     if (!io->elapsed) return fail(-29, "rg_policy_rollout: the step io must carry the gymma block (elapsed, truncated, ended, reward_sum)");
     if (int rc = check_io(io)) return rc;
@@ -685,7 +681,7 @@ int rg_get_obs(rg_handle *h, float *obs) {
     rg::KernelArgs a;
     if (int rc = fill_args(h, a)) return rc;
     if (!obs) return fail(-23, "obs is NULL");
-    if (reinterpret_cast<uintptr_t>(obs) & 15u) return fail(-26, "obs must be 16-byte aligned");
+    if (!rg::all_aligned(16, obs)) return fail(-26, "obs must be 16-byte aligned");
     a.io.obs = obs;
     RG_ON_DEVICE(h);
     return launch_group_entry(h, a, plan(h, rg::GROUP_OBS));

@@ -20,9 +20,8 @@
 // before the first HIP call, so the refusals can be exercised without a device.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-
 #include "episodes.h"
+#include "host_checks.h"
 
 namespace rg {
 namespace episodes {
@@ -213,10 +212,7 @@ extern "C" int rg_sizeof_episode_stream(void) { return static_cast<int>(sizeof(r
 
 extern "C" int rg_episodes_append(const rg_episode_buffer *buffer, const rg_episode_stream *stream, void *hip_stream) {
     using namespace rg::episodes;
-    auto fail = [](int code, const char *what, const char *msg) {
-        snprintf(g_episodes_err, sizeof(g_episodes_err), "rg_episodes_append: %s %s", what, msg);
-        return code;
-    };
+    const rg::Fail fail{g_episodes_err, sizeof(g_episodes_err), "rg_episodes_append"};
     if (!buffer) return fail(-1, "buffer", "is NULL");
     if (!stream) return fail(-2, "stream", "is NULL");
     const rg_episode_buffer &b = *buffer;
@@ -227,46 +223,33 @@ extern "C" int rg_episodes_append(const rg_episode_buffer *buffer, const rg_epis
     if (b.n_agents < 1) return fail(-113, "buffer.n_agents", "must be >= 1");
     if (b.obs_dim < 1) return fail(-114, "buffer.obs_dim", "must be >= 1");
     if (s.T < 1) return fail(-115, "stream.T", "must be >= 1");
-    // the largest arrays are the obs ones; every product below is at most 2^31 times a 32-bit factor
-    const int64_t limit = 0x7fffffff;
-    const int64_t slots = static_cast<int64_t>(b.num_envs) * b.slots_per_env;
-    const int64_t rows = slots <= limit ? slots * (static_cast<int64_t>(b.episode_limit) + 1) : limit + 1;
-    const int64_t row_agents = rows <= limit ? rows * b.n_agents : limit + 1;
-    if (row_agents > limit || row_agents * b.obs_dim > limit)
+    // the largest arrays are the obs ones
+    if (!rg::elements_fit(b.num_envs, b.slots_per_env, static_cast<int64_t>(b.episode_limit) + 1, b.n_agents, b.obs_dim))
         return fail(-116, "buffer.num_envs * slots_per_env * (episode_limit + 1) * n_agents * obs_dim", "exceeds 2^31 - 1 elements");
-    const int64_t steps = (static_cast<int64_t>(s.T) + 1) * b.num_envs;
-    const int64_t step_agents = steps <= limit ? steps * b.n_agents : limit + 1;
-    if (step_agents > limit || step_agents * b.obs_dim > limit)
+    if (!rg::elements_fit(static_cast<int64_t>(s.T) + 1, b.num_envs, b.n_agents, b.obs_dim))
         return fail(-117, "(stream.T + 1) * buffer.num_envs * n_agents * obs_dim", "exceeds 2^31 - 1 elements");
-    const struct {
-        const void *p;
-        const char *name;
-        unsigned align;
-    } fields[] = {{b.obs, "buffer.obs", 4},
-                  {b.actions, "buffer.actions", 4},
-                  {b.reward, "buffer.reward", 4},
-                  {b.terminated, "buffer.terminated", 1},
-                  {b.filled, "buffer.filled", 1},
-                  {b.length, "buffer.length", 4},
-                  {b.episode_return, "buffer.episode_return", 4},
-                  {b.complete, "buffer.complete", 1},
-                  {b.fresh, "buffer.fresh", 1},
-                  {b.episode_index, "buffer.episode_index", 4},
-                  {b.cursor, "buffer.cursor", 4},
-                  {s.obs, "stream.obs", 4},
-                  {s.actions, "stream.actions", 4},
-                  {s.reward, "stream.reward", 4},
-                  {s.terminated, "stream.terminated", 1},
-                  {s.episode_start, "stream.episode_start", 1},
-                  {b.prob, "buffer.prob", 4},
-                  {s.prob, "stream.prob", 4}};
-    const int n_required = 16, n_fields = 18;
-    for (int i = 0; i < n_required; ++i)
-        if (!fields[i].p) return fail(-120 - i, fields[i].name, "is NULL");
+    const rg::NamedPtr fields[] = {{b.obs, "buffer.obs", 4},
+                                   {b.actions, "buffer.actions", 4},
+                                   {b.reward, "buffer.reward", 4},
+                                   {b.terminated, "buffer.terminated", 1},
+                                   {b.filled, "buffer.filled", 1},
+                                   {b.length, "buffer.length", 4},
+                                   {b.episode_return, "buffer.episode_return", 4},
+                                   {b.complete, "buffer.complete", 1},
+                                   {b.fresh, "buffer.fresh", 1},
+                                   {b.episode_index, "buffer.episode_index", 4},
+                                   {b.cursor, "buffer.cursor", 4},
+                                   {s.obs, "stream.obs", 4},
+                                   {s.actions, "stream.actions", 4},
+                                   {s.reward, "stream.reward", 4},
+                                   {s.terminated, "stream.terminated", 1},
+                                   {s.episode_start, "stream.episode_start", 1},
+                                   {b.prob, "buffer.prob", 4},   // (the 16 above are required; the two prob arrays: both or neither)
+                                   {s.prob, "stream.prob", 4}};
+    if (const rg::NamedPtr *f = rg::first_null(fields, 16)) return fail(-120 - static_cast<int>(f - fields), f->name, "is NULL");
     if (b.prob && !s.prob) return fail(-136, "stream.prob", "is NULL, but buffer.prob is not: the buffer keeps prob, the stream has none");
     if (s.prob && !b.prob) return fail(-137, "buffer.prob", "is NULL, but stream.prob is not: the stream has prob, the buffer keeps none");
-    for (int i = 0; i < n_fields; ++i)
-        if (reinterpret_cast<uintptr_t>(fields[i].p) & (fields[i].align - 1)) return fail(-150 - i, fields[i].name, "must be 4-byte aligned");
+    if (const rg::NamedPtr *f = rg::first_misaligned(fields)) return fail(-150 - static_cast<int>(f - fields), f->name, "must be 4-byte aligned");
 
     // the widest piece that divides a row and keeps every row of both obs arrays aligned
     const int nd = b.n_agents * b.obs_dim;

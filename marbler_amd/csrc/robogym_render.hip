@@ -21,8 +21,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdio>
 
+#include "host_checks.h"
 #include "render.h"
 #include "sim_math.h"
 
@@ -261,15 +261,12 @@ extern "C" int rg_sizeof_render_params(void) { return static_cast<int>(sizeof(rg
 extern "C" int rg_render(const rg_scenario_params *params, const rg_state *state, int32_t num_envs, const rg_render_params *rp,
                          uint8_t *rgb, void *hip_stream) {
     using namespace rg::render;
-    auto fail = [](int code, const char *msg) {
-        snprintf(g_render_err, sizeof(g_render_err), "rg_render: %s", msg);
-        return code;
-    };
+    const rg::Fail fail{g_render_err, sizeof(g_render_err), "rg_render"};
     if (!params) return fail(-1, "params is NULL");
     if (!state) return fail(-2, "state is NULL");
     if (!rp) return fail(-3, "rp (rg_render_params) is NULL");
     if (!rgb) return fail(-4, "rgb is NULL");
-    if (reinterpret_cast<uintptr_t>(rgb) & 3u) return fail(-5, "rgb must be 4-byte aligned");
+    if (!rg::all_aligned(4, rgb)) return fail(-5, "rgb must be 4-byte aligned");
     const rg_scenario_params &p = *params;
     if (p.scenario < RG_SCN_PREDATOR_CAPTURE_PREY || p.scenario > RG_SCN_ARCTIC_TRANSPORT) return fail(-80, "params.scenario unknown");
     if (p.n_agents < 1 || p.n_agents > RG_MAX_AGENTS) return fail(-81, "params.n_agents outside 1..16");
@@ -286,7 +283,7 @@ extern "C" int rg_render(const rg_scenario_params *params, const rg_state *state
     if (rp->height < 8 || rp->height > 1024) return fail(-88, "height outside 8..1024");
     if (rp->n_frames < 1) return fail(-89, "n_frames must be >= 1");
     const int64_t n_tiles = (static_cast<int64_t>(rp->width / 4) * rp->height + BLOCK * QUADS_PER_LANE - 1) / (BLOCK * QUADS_PER_LANE);
-    if (n_tiles * rp->n_frames > 0x7fffffff) return fail(-90, "n_frames: more than 2^31 - 1 work-groups at this width and height");
+    if (!rg::elements_fit(n_tiles, rp->n_frames)) return fail(-90, "n_frames: more than 2^31 - 1 work-groups at this width and height");
     const int32_t all = RG_RENDER_ARENA | RG_RENDER_ZONES | RG_RENDER_MARKERS | RG_RENDER_RINGS | RG_RENDER_ROBOTS | RG_RENDER_HEADING;
     if (rp->layers & ~all) return fail(-91, "layers has bits outside the RG_RENDER_* mask");
     if (!rp->env_index && rp->n_frames > num_envs) return fail(-92, "env_index is NULL and n_frames exceeds num_envs");

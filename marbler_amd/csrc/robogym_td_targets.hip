@@ -6,8 +6,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdio>
 #include <cstring>
+
+#include "host_checks.h"
 
 #ifndef RG_TD_TARGETS_HOST_ONLY   // (the sanitized host program, tests/sanitize/td_targets_host.cpp: the argument checks without the kernels)
 #include "td_targets.h"
@@ -39,31 +40,21 @@ extern "C" int rg_sizeof_td_targets_io(void) { return static_cast<int>(sizeof(rg
 extern "C" int rg_sizeof_mixer_weights(void) { return static_cast<int>(sizeof(rg_mixer_weights)); }
 
 extern "C" int rg_td_targets(const rg_mixer_weights *m, const rg_td_targets_io *io, void *hip_stream) {
-    auto fail = [](int code, const char *what, const char *msg) {
-        snprintf(g_td_err, sizeof(g_td_err), "rg_td_targets: %s %s", what, msg);
-        return code;
-    };
-    struct named {
-        const void *p;
-        const char *name;
-    };
+    const rg::Fail fail{g_td_err, sizeof(g_td_err), "rg_td_targets"};
     if (!m) return fail(-1, "m", "is NULL");
     if (!io) return fail(-2, "io", "is NULL");
-    const named required[] = {{io->qt, "io.qt"}, {io->reward, "io.reward"}, {io->terminated, "io.terminated"}, {io->filled, "io.filled"},
-                              {io->targets, "io.targets"}};
-    for (const auto &f : required)
-        if (!f.p) return fail(-3, f.name, "is NULL");
+    const rg::NamedPtr required[] = {{io->qt, "io.qt"}, {io->reward, "io.reward"}, {io->terminated, "io.terminated"}, {io->filled, "io.filled"},
+                                 {io->targets, "io.targets"}};
+    if (const rg::NamedPtr *f = rg::first_null(required)) return fail(-3, f->name, "is NULL");
     if (m->kind != RG_MIXER_NONE && m->kind != RG_MIXER_VDN && m->kind != RG_MIXER_QMIX)
         return fail(-4, "m.kind", "is none of RG_MIXER_NONE, RG_MIXER_VDN, RG_MIXER_QMIX");
     const bool qmix = m->kind == RG_MIXER_QMIX;
     if (qmix) {
         if (!io->obs) return fail(-3, "io.obs", "is NULL (the qmix mixer reads the state from it)");
-        const named weights[] = {{m->w_in, "m.w_in"}, {m->b_in, "m.b_in"}, {m->w_w1, "m.w_w1"}, {m->b_w1, "m.b_w1"},
-                                 {m->w_wf, "m.w_wf"}, {m->b_wf, "m.b_wf"}, {m->w_v, "m.w_v"}, {m->b_v, "m.b_v"}};
-        for (const auto &f : weights)
-            if (!f.p) return fail(-5, f.name, "is NULL (a weight array of the qmix mixer)");
-        for (const auto &f : weights)
-            if (reinterpret_cast<uintptr_t>(f.p) & 15u) return fail(-6, f.name, "must be 16-byte aligned");
+        const rg::NamedPtr weights[] = {{m->w_in, "m.w_in"}, {m->b_in, "m.b_in"}, {m->w_w1, "m.w_w1"}, {m->b_w1, "m.b_w1"},
+                                    {m->w_wf, "m.w_wf"}, {m->b_wf, "m.b_wf"}, {m->w_v, "m.w_v"}, {m->b_v, "m.b_v"}};
+        if (const rg::NamedPtr *f = rg::first_null(weights)) return fail(-5, f->name, "is NULL (a weight array of the qmix mixer)");
+        if (const rg::NamedPtr *f = rg::first_misaligned(weights, 16)) return fail(-6, f->name, "must be 16-byte aligned");
         if (m->embed_dim != 32) return fail(-7, "m.embed_dim", "must be 32 (mixing_embed_dim: 32 is the only instantiation)");
         if (m->hypernet_embed != 64) return fail(-7, "m.hypernet_embed", "must be 64 (hypernet_layers: 2 with hypernet_embed: 64 is the only instantiation)");
     }
@@ -85,8 +76,7 @@ extern "C" int rg_td_targets(const rg_mixer_weights *m, const rg_td_targets_io *
     if (!std::isfinite(io->gamma) || io->gamma < 0.0f || io->gamma > 1.0f) return fail(-19, "io.gamma", "must be finite and in [0, 1]");
     if (m->reserved != 0) return fail(-20, "m.reserved", "must be 0");
     if (io->reserved != 0) return fail(-20, "io.reserved", "must be 0");
-    // the element counts of every array: below 2^31 (num_episodes * pitch < 2^62, an array's row below 2^13 elements)
-    const int64_t limit = 0x7fffffff;
+    // the element counts of every array: below 2^31 (a row is a product of two 32-bit factors)
     const struct {
         int64_t pitch, row;
         const char *name;
@@ -94,10 +84,8 @@ extern "C" int rg_td_targets(const rg_mixer_weights *m, const rg_td_targets_io *
                   {io->obs_pitch, S, "io.num_episodes * obs_pitch * n_agents * obs_dim"},
                   {io->flag_pitch, 1, "io.num_episodes * flag_pitch"},
                   {io->out_pitch, io->n_agents, "io.num_episodes * out_pitch * n_agents"}};
-    for (const auto &c : counts) {
-        const int64_t batch_rows = static_cast<int64_t>(io->num_episodes) * c.pitch;
-        if (batch_rows > limit || c.row > limit || batch_rows * c.row > limit) return fail(-21, c.name, "exceeds 2^31 - 1 elements");
-    }
+    for (const auto &c : counts)
+        if (!rg::elements_fit(io->num_episodes, c.pitch, c.row)) return fail(-21, c.name, "exceeds 2^31 - 1 elements");
 
     const hipError_t err = launch(*m, *io, hip_stream);
     if (err != hipSuccess) return fail(-30, "the launch failed:", hipGetErrorString(err));
