@@ -164,6 +164,27 @@ class RgTdTargetsIO(C.Structure):
                 ("out_pitch", C.c_int32), ("gamma", C.c_float), ("reserved", C.c_int32)]
 
 
+# rg_nstep_returns: the target critic and MAPPO's n-step returns of an episode batch (include/robogym_returns.h; the rule:
+# csrc/nstep_returns.h)
+CRITIC_CV, CRITIC_CV_NS = 0, 1
+NSTEP_MAX, RETURNS_MAX_ROWS = 32, 4096
+
+
+class RgCriticWeights(C.Structure):
+    _fields_ = [("w1", C.c_void_p), ("w1_id", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p),
+                ("w3", C.c_void_p), ("b3", C.c_void_p), ("kind", C.c_int32), ("n_agents", C.c_int32), ("state_dim", C.c_int32),
+                ("hidden_dim", C.c_int32), ("net_stride", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RgNstepReturnsIO(C.Structure):
+    _fields_ = [("obs", C.c_void_p), ("reward", C.c_void_p), ("terminated", C.c_void_p), ("filled", C.c_void_p),
+                ("returns", C.c_void_p), ("values", C.c_void_p), ("mask", C.c_void_p),
+                ("num_episodes", C.c_int32), ("n_agents", C.c_int32), ("obs_dim", C.c_int32), ("rows", C.c_int32),
+                ("nstep", C.c_int32), ("add_value_last_step", C.c_int32), ("obs_pitch", C.c_int32), ("flag_pitch", C.c_int32),
+                ("out_pitch", C.c_int32), ("value_pitch", C.c_int32), ("gamma", C.c_float), ("value_scale", C.c_float),
+                ("value_shift", C.c_float), ("reserved", C.c_int32)]
+
+
 # rg_step_form: which form the last rg_step launch took (include/robogym.h RG_FORM_*)
 FORM_NONE, FORM_BY_VALUE, FORM_RESIDENT, FORM_SHAPE = 0, 1, 2, 16
 
@@ -227,7 +248,15 @@ LAYOUTS = (("rg_sizeof_params", RgScenarioParams), ("rg_sizeof_state", RgState),
            ("rg_sizeof_episode_stream", RgEpisodeStream), ("rg_sizeof_actor_unroll_io", RgActorUnrollIO),
            ("rg_sizeof_mixer_weights", RgMixerWeights), ("rg_sizeof_td_targets_io", RgTdTargetsIO))
 
+# The entries of include/robogym_returns.h, beside the table above (robogym.h's function list and ENTRIES stay as they are): typed
+# and layout-checked on first use by load_returns().  (name, restype, argtypes or None)
+RETURNS_ENTRIES = (
+    ("rg_sizeof_critic_weights", _INT, None), ("rg_sizeof_nstep_returns_io", _INT, None),
+    ("rg_nstep_returns", _INT, [_P(RgCriticWeights), _P(RgNstepReturnsIO), _VP]), ("rg_nstep_returns_last_error", _STR, None))
+RETURNS_LAYOUTS = (("rg_sizeof_critic_weights", RgCriticWeights), ("rg_sizeof_nstep_returns_io", RgNstepReturnsIO))
+
 _lib = None
+_returns_ready = False
 
 
 class RobogymError(RuntimeError):
@@ -260,6 +289,29 @@ def load():
             raise RobogymError(f"struct layout of the binding differs from the compiled library; rebuild ({struct.__name__} is "
                                f"{C.sizeof(struct)} bytes here, {query}() says {getattr(lib, query)()})")
     _lib = lib
+    return lib
+
+
+def load_returns():
+    """load(), with the entries of include/robogym_returns.h typed and their struct layouts checked (once).  A library that lacks
+    them -- one of an earlier build, loaded through ROBOGYM_LIB -- raises RobogymError here, when the feature is called, not at
+    load()."""
+    global _returns_ready
+    lib = load()
+    if _returns_ready:
+        return lib
+    for name, restype, argtypes in RETURNS_ENTRIES:
+        if not hasattr(lib, name):
+            raise RobogymError(f"{LIB_PATH} does not export {name} (include/robogym_returns.h): it was built before n-step returns")
+        f = getattr(lib, name)
+        f.restype = restype
+        if argtypes is not None:
+            f.argtypes = argtypes
+    for query, struct in RETURNS_LAYOUTS:
+        if getattr(lib, query)() != C.sizeof(struct):
+            raise RobogymError(f"struct layout of the binding differs from the compiled library; rebuild ({struct.__name__} is "
+                               f"{C.sizeof(struct)} bytes here, {query}() says {getattr(lib, query)()})")
+    _returns_ready = True
     return lib
 
 

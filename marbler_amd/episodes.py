@@ -253,6 +253,36 @@ class EpisodeBuffer(object):
         return {"targets": out["targets"] if mixer.kind == "none" else out["targets"].unsqueeze(-1),
                 "mask": out["mask"].unsqueeze(-1), "agent_q": out["agent_q"]}
 
+    def nstep_returns(self, target_critic, slots=None, trim=False, gamma=0.99, nstep=10, add_value_last_step=True, value_scale=1.0,
+                      value_shift=0.0, reward=None):
+        """Everything a PPO learner computes under no_grad for batch(slots, trim), in one launch: the episode mask, `target_critic`
+        (a returns.TargetCritic) over every needed row, and the n-step returns (returns.nstep_returns; the rule:
+        csrc/nstep_returns.h).  reward: an optional [B, rows] float32 replacement for the slots' rewards (a learner that
+        standardises rewards), over the same rows as batch(slots, trim).  Returns returns [B, rows - 1, N], values [B, rows, N] and
+        mask [B, rows - 1, 1].  ValueError for a critic or a `reward` that does not fit the buffer or that the launch refuses."""
+        from . import returns
+        if not isinstance(target_critic, returns.TargetCritic):
+            raise ValueError(f"target_critic must be a TargetCritic, got {type(target_critic).__name__}")
+        for name, have, want in (("critic's n_agents", target_critic.n_agents, self.N), ("critic's state_dim", target_critic.state_dim, self.N * self.D)):
+            if have != want:
+                raise ValueError(f"the {name} is {have}, the buffer's episodes need {want}")
+        if target_critic.device != self.device:
+            raise ValueError(f"the critic is on {target_critic.device}, the buffer on {self.device}")
+        idx, B, rows, _ = self._select(slots, trim, 2)
+        if reward is not None:
+            _args.check_tensor("reward", reward, (torch.float32,), (B, rows), self.device, contiguous=False, errors=_args.VALUE)
+        if B == 0:
+            return {"returns": torch.empty(0, rows - 1, self.N, device=self.device), "values": torch.empty(0, rows, self.N, device=self.device),
+                    "mask": torch.empty(0, rows - 1, 1, device=self.device)}
+        cut = lambda x: x[idx][:, :rows]  # noqa: E731  (the gathered copy is read in place)
+        if reward is not None:      # (a replacement has its own pitch: the flags then go dense beside it)
+            reward, flags = reward.contiguous(), (cut(self.terminated).contiguous(), cut(self.filled).contiguous())
+        else:
+            reward, flags = cut(self.reward), (cut(self.terminated), cut(self.filled))
+        out = returns.nstep_returns(cut(self.obs), reward, flags[0], flags[1], target_critic, gamma, nstep, add_value_last_step,
+                                    value_scale, value_shift)
+        return {"returns": out["returns"], "values": out["values"], "mask": out["mask"].unsqueeze(-1)}
+
     def sample(self, n, generator=None):
         """n slots drawn uniformly, without replacement, among the complete ones (int64); ValueError if fewer are complete."""
         if isinstance(n, bool) or not isinstance(n, int) or n < 1:
