@@ -185,6 +185,23 @@ class RgNstepReturnsIO(C.Structure):
                 ("value_shift", C.c_float), ("reserved", C.c_int32)]
 
 
+# rg_gru_scan_forward / rg_gru_scan_backward: the GRU recurrence of an episode batch with gradients (include/robogym_learn.h; the
+# rule: csrc/gru_scan.h)
+GRU_SCAN_MAX_ROWS = 4096
+
+
+class RgGruScanWeights(C.Structure):
+    _fields_ = [("w_hh", C.c_void_p), ("b_hh", C.c_void_p), ("w_hh_t", C.c_void_p), ("n_sets", C.c_int32), ("hidden_dim", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+class RgGruScanIO(C.Structure):
+    _fields_ = [("gi", C.c_void_p), ("hidden_in", C.c_void_p), ("h", C.c_void_p), ("gates", C.c_void_p), ("hidden_out", C.c_void_p),
+                ("dh_ext", C.c_void_p), ("d_hidden_out", C.c_void_p), ("dgi", C.c_void_p), ("dghn", C.c_void_p),
+                ("d_hidden_in", C.c_void_p), ("num_episodes", C.c_int32), ("n_agents", C.c_int32), ("rows", C.c_int32),
+                ("gi_pitch", C.c_int32), ("save_pitch", C.c_int32), ("grad_pitch", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 # rg_step_form: which form the last rg_step launch took (include/robogym.h RG_FORM_*)
 FORM_NONE, FORM_BY_VALUE, FORM_RESIDENT, FORM_SHAPE = 0, 1, 2, 16
 
@@ -255,8 +272,16 @@ RETURNS_ENTRIES = (
     ("rg_nstep_returns", _INT, [_P(RgCriticWeights), _P(RgNstepReturnsIO), _VP]), ("rg_nstep_returns_last_error", _STR, None))
 RETURNS_LAYOUTS = (("rg_sizeof_critic_weights", RgCriticWeights), ("rg_sizeof_nstep_returns_io", RgNstepReturnsIO))
 
+# The entries of include/robogym_learn.h, likewise: typed and layout-checked on first use by load_learn().
+LEARN_ENTRIES = (
+    ("rg_sizeof_gru_scan_weights", _INT, None), ("rg_sizeof_gru_scan_io", _INT, None),
+    ("rg_gru_scan_forward", _INT, [_P(RgGruScanWeights), _P(RgGruScanIO), _VP]),
+    ("rg_gru_scan_backward", _INT, [_P(RgGruScanWeights), _P(RgGruScanIO), _VP]), ("rg_gru_scan_last_error", _STR, None))
+LEARN_LAYOUTS = (("rg_sizeof_gru_scan_weights", RgGruScanWeights), ("rg_sizeof_gru_scan_io", RgGruScanIO))
+
 _lib = None
 _returns_ready = False
+_learn_ready = False
 
 
 class RobogymError(RuntimeError):
@@ -292,26 +317,43 @@ def load():
     return lib
 
 
+def _load_table(entries, layouts, header, feature):
+    """load(), with a side header's entries typed and its struct layouts checked."""
+    lib = load()
+    for name, restype, argtypes in entries:
+        if not hasattr(lib, name):
+            raise RobogymError(f"{LIB_PATH} does not export {name} (include/{header}): it was built before {feature}")
+        f = getattr(lib, name)
+        f.restype = restype
+        if argtypes is not None:
+            f.argtypes = argtypes
+    for query, struct in layouts:
+        if getattr(lib, query)() != C.sizeof(struct):
+            raise RobogymError(f"struct layout of the binding differs from the compiled library; rebuild ({struct.__name__} is "
+                               f"{C.sizeof(struct)} bytes here, {query}() says {getattr(lib, query)()})")
+    return lib
+
+
 def load_returns():
     """load(), with the entries of include/robogym_returns.h typed and their struct layouts checked (once).  A library that lacks
     them -- one of an earlier build, loaded through ROBOGYM_LIB -- raises RobogymError here, when the feature is called, not at
     load()."""
     global _returns_ready
-    lib = load()
     if _returns_ready:
-        return lib
-    for name, restype, argtypes in RETURNS_ENTRIES:
-        if not hasattr(lib, name):
-            raise RobogymError(f"{LIB_PATH} does not export {name} (include/robogym_returns.h): it was built before n-step returns")
-        f = getattr(lib, name)
-        f.restype = restype
-        if argtypes is not None:
-            f.argtypes = argtypes
-    for query, struct in RETURNS_LAYOUTS:
-        if getattr(lib, query)() != C.sizeof(struct):
-            raise RobogymError(f"struct layout of the binding differs from the compiled library; rebuild ({struct.__name__} is "
-                               f"{C.sizeof(struct)} bytes here, {query}() says {getattr(lib, query)()})")
+        return load()
+    lib = _load_table(RETURNS_ENTRIES, RETURNS_LAYOUTS, "robogym_returns.h", "n-step returns")
     _returns_ready = True
+    return lib
+
+
+def load_learn():
+    """load(), with the entries of include/robogym_learn.h typed and their struct layouts checked (once), exactly as
+    load_returns() does it for its header."""
+    global _learn_ready
+    if _learn_ready:
+        return load()
+    lib = _load_table(LEARN_ENTRIES, LEARN_LAYOUTS, "robogym_learn.h", "the GRU scan")
+    _learn_ready = True
     return lib
 
 

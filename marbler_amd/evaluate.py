@@ -90,25 +90,7 @@ class BatchedActor(object):
             if self.use_rnn:
                 t.update({k: getattr(self, k).contiguous() for k in ("wih", "bih", "whh", "bhh")})
             if self.use_rnn and self.pack_gru:
-                lib = _lib.load()   # the two GRU matrices once into the kernel's streaming order
-                stream = C.c_void_p(torch.cuda.current_stream(self.w1.device).cuda_stream)
-                for k in ("wih", "whh"):
-                    if self.pack_gru == "bf16x3":
-                        dst = torch.empty(t[k].numel() * 3, dtype=torch.int16, device=t[k].device)   # 6 bytes per weight
-                        rc = lib.rg_actor_pack_gru_bf16x3(t[k].data_ptr(), self.w1.shape[0], self.hidden_dim, dst.data_ptr(), stream)
-                    elif self.pack_gru == "f16x2":
-                        dst = torch.empty(t[k].numel() * 2, dtype=torch.int16, device=t[k].device)   # 4 bytes per weight
-                        rc = lib.rg_actor_pack_gru_f16x2(t[k].data_ptr(), self.w1.shape[0], self.hidden_dim, dst.data_ptr(), stream)
-                    else:
-                        dst = torch.empty_like(t[k])
-                        rc = lib.rg_actor_pack_gru(t[k].data_ptr(), self.w1.shape[0], self.hidden_dim, dst.data_ptr(), stream)
-                    if rc != 0:
-                        raise _lib.RobogymError("rg_actor_pack_gru: " + lib.rg_actor_last_error().decode())
-                    t[k] = dst
-                packed = {"bf16x3": 2, "f16x2": 3}.get(self.pack_gru, 1)
-                # a first launch on ANOTHER stream must not overtake the two pack kernels (weights_for orders every launch behind this)
-                self._pack_done = torch.cuda.Event()
-                self._pack_done.record(torch.cuda.current_stream(self.w1.device))
+                packed = self._pack_gru(t, {})
             if not self.use_rnn:
                 t.update({"wih": self.wr.contiguous(), "bih": self.br.contiguous()})
             ptr = lambda k: t[k].data_ptr() if k in t else None  # noqa: E731
@@ -117,6 +99,75 @@ class BatchedActor(object):
                                            ptr("w2"), ptr("b2"), self.w1.shape[0], self.input_dim, self.hidden_dim,
                                            self.n_actions, 1 if self.use_rnn else 0, packed)
         return self._ws
+
+    def _pack_gru(self, src, dst):
+        """The two GRU matrices src["wih"], src["whh"] into the kernel's streaming order on the current stream: into dst[k], or into
+        new buffers where dst has none; src[k] becomes the packed buffer.  Records the event weights_for orders every launch behind.
+        -> rg_actor_weights.gru_packed"""
+        lib = _lib.load()
+        stream = C.c_void_p(torch.cuda.current_stream(self.w1.device).cuda_stream)
+        for k in ("wih", "whh"):
+            if self.pack_gru == "bf16x3":
+                out = dst[k] if k in dst else torch.empty(src[k].numel() * 3, dtype=torch.int16, device=src[k].device)   # 6 bytes per weight
+                rc = lib.rg_actor_pack_gru_bf16x3(src[k].data_ptr(), self.w1.shape[0], self.hidden_dim, out.data_ptr(), stream)
+            elif self.pack_gru == "f16x2":
+                out = dst[k] if k in dst else torch.empty(src[k].numel() * 2, dtype=torch.int16, device=src[k].device)   # 4 bytes per weight
+                rc = lib.rg_actor_pack_gru_f16x2(src[k].data_ptr(), self.w1.shape[0], self.hidden_dim, out.data_ptr(), stream)
+            else:
+                out = dst[k] if k in dst else torch.empty_like(src[k])
+                rc = lib.rg_actor_pack_gru(src[k].data_ptr(), self.w1.shape[0], self.hidden_dim, out.data_ptr(), stream)
+            if rc != 0:
+                raise _lib.RobogymError("rg_actor_pack_gru: " + lib.rg_actor_last_error().decode())
+            src[k] = out
+        # a first launch on ANOTHER stream must not overtake the two pack kernels (weights_for orders every launch behind this)
+        self._pack_done = torch.cuda.Event()
+        self._pack_done.record(torch.cuda.current_stream(self.w1.device))
+        return {"bf16x3": 2, "f16x2": 3}.get(self.pack_gru, 1)
+
+    _FC1, _FC2 = (("fc1.weight", "w1"), ("fc1.bias", "b1")), (("fc2.weight", "w2"), ("fc2.bias", "b2"))
+    _GRU = (("rnn.weight_ih", "wih"), ("rnn.weight_hh", "whh"), ("rnn.bias_ih", "bih"), ("rnn.bias_hh", "bhh"))
+    _RNN = (("rnn.weight", "wr"), ("rnn.bias", "br"))
+
+    def _keys(self):
+        """(EPyMARL's parameter name, the attribute that holds it stacked), in the module's own order."""
+        return self._FC1 + (self._GRU if self.use_rnn else self._RNN) + self._FC2
+
+    def state_dict(self):
+        """The weights under EPyMARL's names (agents.{i}. in front with one network per agent): copies."""
+        keys = self._keys()
+        if self.non_shared:
+            return {f"agents.{i}.{k}": getattr(self, a)[i].clone() for i in range(self.n_agents) for k, a in keys}
+        return {k: getattr(self, a)[0].clone() for k, a in keys}
+
+    def load_state_dict(self, state_dict):
+        """New weights into the SAME storages (a learner's update: collect -> learn -> collect): every tensor is copied into the
+        array it replaces and, where the actor has handed its weights to a launch before, the GRU matrices are packed again into
+        the same packed buffers on the current stream and the event weights_for orders launches behind is recorded anew -- so the
+        cached weights struct, and every graph captured around a launch of this actor, stay valid and see the new weights.
+        ValueError for a state dict that is not a dict, lacks keys, changes a shape, or holds a tensor that is not floating-point
+        or not finite; a refused state dict leaves the actor alone."""
+        if not isinstance(state_dict, dict):
+            raise ValueError(f"state_dict must be a dict, got {type(state_dict).__name__}")
+        keys = self._keys()
+        A = self.w1.shape[0]
+        names = [((f"agents.{i}." if self.non_shared else "") + k, a, i) for i in range(A) for k, a in keys]
+        missing = [n for n, _, _ in names if n not in state_dict]
+        if missing:
+            raise ValueError(f"the state dict lacks {missing}")
+        for n, a, i in names:
+            t, want = state_dict[n], tuple(getattr(self, a).shape[1:])
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != want:
+                raise ValueError(f"state_dict[{n!r}] must be a tensor {want}, got {tuple(getattr(t, 'shape', ()))}")
+            if not t.is_floating_point():
+                raise ValueError(f"state_dict[{n!r}] must be a floating-point tensor, got {t.dtype}")
+        for n, _, _ in names:
+            if not bool(torch.isfinite(state_dict[n]).all()):
+                raise ValueError(f"state_dict[{n!r}] holds a value that is not finite")
+        with torch.no_grad():
+            for n, a, i in names:
+                getattr(self, a)[i].copy_(state_dict[n].detach())
+        if getattr(self, "_ws", None) is not None and self.use_rnn and self.pack_gru:
+            self._pack_gru({"wih": self.wih, "whh": self.whh}, {k: self._ws_tensors[k] for k in ("wih", "whh")})
 
     def weights_for(self, stream):
         """The weights struct for a launch on `stream` (a torch stream).  The weights were packed (once) on the then-current
