@@ -66,6 +66,51 @@ int rg_gru_scan_forward(const rg_gru_scan_weights *w, const rg_gru_scan_io *io, 
 int rg_gru_scan_backward(const rg_gru_scan_weights *w, const rg_gru_scan_io *io, void *hip_stream);
 const char *rg_gru_scan_last_error(void);
 
+/* rg_mixer_forward() and rg_mixer_backward(): the ONLINE mixer's pass of a Q-learner's training step with gradients -- the chosen
+ * actions' values of rows t < T = rows - 1 of an episode batch, mixed by none / vdn / EPyMARL's QMixer on the state of row t -- in one
+ * launch each.  The rule is stated once in csrc/mixer_grad.h (DESIGN.md section 4 "Trainable mixer").  The backward launch recomputes
+ * the forward pass and writes d_q whole (zeros included) and, for qmix, the per-row arrays that the weight gradients are sums of;
+ * the sums themselves are the caller's (marbler_amd/mixers.py does them with torch's GEMMs).
+ *
+ * The weights: `m` as rg_td_targets takes them (robogym.h rg_mixer_weights: the packed, K-major arrays; none / vdn: kind and n_agents
+ * alone), and for the qmix backward launch the second layers as torch keeps them: w1b = hyper_w_1.2.weight [32 N][64] and wfb =
+ * hyper_w_final.2.weight [32][64], 16-byte aligned.  Layout: 88 + 2 pointers = 104 bytes, checked with rg_sizeof_mixer_grad_weights(). */
+typedef struct rg_mixer_grad_weights {
+    rg_mixer_weights m;
+    const float *w1b;       /* [32 N][64]; the qmix backward launch only */
+    const float *wfb;       /* [32][64];   the qmix backward launch only */
+} rg_mixer_grad_weights;
+int rg_sizeof_mixer_grad_weights(void);
+/* Layout: 10 pointers + 10 ints = 120 bytes, checked with rg_sizeof_mixer_grad_io().  B = num_episodes, N = n_agents, T = rows - 1. */
+typedef struct rg_mixer_grad_io {
+    const float *q;             /* both (backward: qmix only), in: [B][q_pitch][N][A] */
+    const int32_t *actions;     /* both, in: [B][q_pitch][N] */
+    const float *obs;           /* qmix, both, in: [B][obs_pitch][N][D] */
+    const float *mask;          /* both, in: [B][out_pitch] */
+    float *mixed;               /* forward out: [B][out_pitch], with RG_MIXER_NONE [B][out_pitch][N] */
+    const float *d_mixed;       /* backward in: laid out as mixed */
+    float *d_q;                 /* backward out: [B][q_pitch][N][A], rows 0 .. T written */
+    float *d_pre;               /* qmix backward out: [B][aux_pitch][192], rows 0 .. T written */
+    float *d_p2;                /* qmix backward out: [B][aux_pitch][32 N + 32] */
+    float *g;                   /* qmix backward out: [B][aux_pitch][160] */
+    int32_t num_episodes, n_agents, obs_dim, n_actions, rows;
+    int32_t q_pitch, obs_pitch, out_pitch, aux_pitch;   /* rows an episode takes in q, actions and d_q; in obs; in mask, mixed and d_mixed; in d_pre, d_p2 and g */
+    int32_t reserved;
+} rg_mixer_grad_io;
+int rg_sizeof_mixer_grad_io(void);
+/* Handle-free; never allocate, copy or synchronise (safe under stream capture); launch on `hip_stream` of the caller's CURRENT
+ * device.  Every argument is checked before the first HIP call; a launch looks only at its own pointers and pitches.  Errors (text via
+ * rg_mixer_grad_last_error(), which names the argument): -1 w, -2 io NULL; -3 a required array of io NULL (forward: q, actions, mask,
+ * mixed, and obs with qmix; backward: actions, mask, d_mixed, d_q, and with qmix q, obs, d_pre, d_p2, g); -4 w.m.kind; -5 a weight array
+ * of the qmix mixer NULL (backward: w1b and wfb too); -6 a weight array not 16-byte aligned, or an array of io not 4-byte aligned; -7
+ * embed_dim != 32 or hypernet_embed != 64; -8 w.m.n_agents != io.n_agents; -9 w.m.state_dim != n_agents * obs_dim; -10 num_episodes
+ * below 1; -11 rows below 2; -12 n_agents outside 1..RG_MAX_AGENTS; -13 n_actions outside 1..32; -14 obs_dim below 1 or the padded
+ * state wider than 256 (qmix); -15 obs_pitch below rows (qmix); -16 q_pitch below rows; -17 out_pitch below rows - 1; -18 aux_pitch
+ * below rows (qmix backward); -20 a reserved field != 0; -21 an array of more than 2^31 - 1 elements; -30 the launch failed. */
+int rg_mixer_forward(const rg_mixer_grad_weights *w, const rg_mixer_grad_io *io, void *hip_stream);
+int rg_mixer_backward(const rg_mixer_grad_weights *w, const rg_mixer_grad_io *io, void *hip_stream);
+const char *rg_mixer_grad_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -202,6 +202,20 @@ class RgGruScanIO(C.Structure):
                 ("gi_pitch", C.c_int32), ("save_pitch", C.c_int32), ("grad_pitch", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+# rg_mixer_forward / rg_mixer_backward: the online mixer's pass of an episode batch with gradients (include/robogym_learn.h; the
+# rule: csrc/mixer_grad.h)
+class RgMixerGradWeights(C.Structure):
+    _fields_ = [("m", RgMixerWeights), ("w1b", C.c_void_p), ("wfb", C.c_void_p)]
+
+
+class RgMixerGradIO(C.Structure):
+    _fields_ = [("q", C.c_void_p), ("actions", C.c_void_p), ("obs", C.c_void_p), ("mask", C.c_void_p), ("mixed", C.c_void_p),
+                ("d_mixed", C.c_void_p), ("d_q", C.c_void_p), ("d_pre", C.c_void_p), ("d_p2", C.c_void_p), ("g", C.c_void_p),
+                ("num_episodes", C.c_int32), ("n_agents", C.c_int32), ("obs_dim", C.c_int32), ("n_actions", C.c_int32),
+                ("rows", C.c_int32), ("q_pitch", C.c_int32), ("obs_pitch", C.c_int32), ("out_pitch", C.c_int32),
+                ("aux_pitch", C.c_int32), ("reserved", C.c_int32)]
+
+
 # rg_step_form: which form the last rg_step launch took (include/robogym.h RG_FORM_*)
 FORM_NONE, FORM_BY_VALUE, FORM_RESIDENT, FORM_SHAPE = 0, 1, 2, 16
 
@@ -279,9 +293,18 @@ LEARN_ENTRIES = (
     ("rg_gru_scan_backward", _INT, [_P(RgGruScanWeights), _P(RgGruScanIO), _VP]), ("rg_gru_scan_last_error", _STR, None))
 LEARN_LAYOUTS = (("rg_sizeof_gru_scan_weights", RgGruScanWeights), ("rg_sizeof_gru_scan_io", RgGruScanIO))
 
+# The mixer entries of include/robogym_learn.h, in a table of their own (LEARN_ENTRIES stays as it is): typed and layout-checked on
+# first use by load_mixer_grad().
+MIXER_GRAD_ENTRIES = (
+    ("rg_sizeof_mixer_grad_weights", _INT, None), ("rg_sizeof_mixer_grad_io", _INT, None),
+    ("rg_mixer_forward", _INT, [_P(RgMixerGradWeights), _P(RgMixerGradIO), _VP]),
+    ("rg_mixer_backward", _INT, [_P(RgMixerGradWeights), _P(RgMixerGradIO), _VP]), ("rg_mixer_grad_last_error", _STR, None))
+MIXER_GRAD_LAYOUTS = (("rg_sizeof_mixer_grad_weights", RgMixerGradWeights), ("rg_sizeof_mixer_grad_io", RgMixerGradIO))
+
 _lib = None
 _returns_ready = False
 _learn_ready = False
+_mixer_grad_ready = False
 
 
 class RobogymError(RuntimeError):
@@ -354,6 +377,17 @@ def load_learn():
         return load()
     lib = _load_table(LEARN_ENTRIES, LEARN_LAYOUTS, "robogym_learn.h", "the GRU scan")
     _learn_ready = True
+    return lib
+
+
+def load_mixer_grad():
+    """load(), with the mixer entries of include/robogym_learn.h typed and their struct layouts checked (once), as load_learn()
+    does it for the GRU scan's."""
+    global _mixer_grad_ready
+    if _mixer_grad_ready:
+        return load()
+    lib = _load_table(MIXER_GRAD_ENTRIES, MIXER_GRAD_LAYOUTS, "robogym_learn.h", "the trainable mixer")
+    _mixer_grad_ready = True
     return lib
 
 

@@ -21,7 +21,8 @@ LIB = os.path.join(HERE, "librobogym_hip.so")
 # (group_units, policy_units), each from one generic source.
 SOURCES = ["robogym_kernels.hip", "robogym_resident.hip", "robogym_resident_shapes.hip", "robogym_tpe.hip", "robogym_rollout_tpe.hip",
            "robogym_capi.hip", "actor_mfma.hip", "robogym_team.hip", "robogym_render.hip", "robogym_episodes.hip",
-           "robogym_actor_unroll.hip", "robogym_td_targets.hip", "robogym_nstep_returns.hip", "robogym_gru_scan.hip"]
+           "robogym_actor_unroll.hip", "robogym_td_targets.hip", "robogym_nstep_returns.hip", "robogym_gru_scan.hip",
+           "robogym_mixer_grad.hip"]
 GROUP_UNIT, POLICY_UNIT = "robogym_group_unit.hip", "robogym_policy_unit.hip"
 # every header of csrc/ (a forgotten one would mean a stale library), and the C ABI's
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(CSRC, "probes", "*.h"))) + \

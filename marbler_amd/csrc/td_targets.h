@@ -72,18 +72,9 @@
 #include <stdint.h>
 
 #include "../../include/robogym.h"
+#include "mixer_tile.h"
 
 namespace rg {
-
-constexpr int TD_TM = 32;                 // rows of a tile
-constexpr int TD_NT = 192;                // threads of the qmix workgroup: three wavefronts
-constexpr int TD_EMBED = 32;              // mixing_embed_dim
-constexpr int TD_HYPER = 64;              // hypernet_embed
-constexpr int TD_C1 = 192;                // first-layer columns: 64 + 64 + 32 + 32
-constexpr int TD_H1S = TD_C1 + 1;         // row stride of the first layers' LDS image (odd)
-constexpr int TD_MAX_SP = 256;            // the padded state width the LDS image holds
-constexpr int TD_COL_WF = 64, TD_COL_V = 128, TD_COL_B1 = 160;   // where each hypernetwork's first layer starts
-constexpr int TD_PS = TD_EMBED + 1;       // row stride of the [32][32] images of step 5
 
 struct TdArgs {
     rg_mixer_weights m;
@@ -92,8 +83,6 @@ struct TdArgs {
     int32_t total;        // B T flat rows
     int32_t sp;           // S padded to a multiple of 4 (qmix)
 };
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 // 0: masked, 1: terminal, 2: live
 __device__ __forceinline__ int td_row_flag(const rg_td_targets_io &io, int b, int t) {

@@ -253,6 +253,28 @@ class EpisodeBuffer(object):
         return {"targets": out["targets"] if mixer.kind == "none" else out["targets"].unsqueeze(-1),
                 "mask": out["mask"].unsqueeze(-1), "agent_q": out["agent_q"]}
 
+    def mixed_q(self, mixer, q, mask, slots=None, trim=False):
+        """The online mixer's pass over batch(slots, trim) with gradients: `mixer` (a mixers.TrainableMixer) on q [B, rows, N, A]
+        (TrainableActor's output over the same slots and trim) with the buffer's own actions and observations of the selected
+        slots, and mask [B, rows - 1] or [B, rows - 1, 1] (td_targets' mask).  Returns mixed [B, rows - 1, 1] (a `none` mixer:
+        [B, rows - 1, N]) with a graph through q and the mixer's parameters (the rule: csrc/mixer_grad.h).  ValueError for a mixer
+        that does not fit the buffer, or a q or mask that does not fit the selection."""
+        from . import mixers
+        if not isinstance(mixer, mixers.TrainableMixer):
+            raise ValueError(f"mixer must be a TrainableMixer, got {type(mixer).__name__}")
+        fits = [("mixer's n_agents", mixer.n_agents, self.N)] + ([("mixer's state_dim", mixer.state_dim, self.N * self.D)] if mixer.kind == "qmix" else [])
+        for name, have, want in fits:
+            if have != want:
+                raise ValueError(f"the {name} is {have}, the buffer's episodes need {want}")
+        idx, B, rows, _ = self._select(slots, trim, 2)
+        _args.check_tensor("q", q, (torch.float32,), (B, rows, self.N, self.A), contiguous=False, errors=_args.VALUE)
+        if not isinstance(mask, torch.Tensor) or tuple(mask.shape) not in ((B, rows - 1), (B, rows - 1, 1)):
+            raise ValueError(f"mask must be a tensor {(B, rows - 1)} or {(B, rows - 1, 1)}, got {tuple(getattr(mask, 'shape', ()))}")
+        if B == 0:
+            return torch.empty(0, rows - 1, self.N if mixer.kind == "none" else 1, device=self.device)
+        mixed = mixer(q, self.actions[idx, :rows], self.obs[idx][:, :rows], mask)
+        return mixed if mixer.kind == "none" else mixed.unsqueeze(-1)
+
     def nstep_returns(self, target_critic, slots=None, trim=False, gamma=0.99, nstep=10, add_value_last_step=True, value_scale=1.0,
                       value_shift=0.0, reward=None):
         """Everything a PPO learner computes under no_grad for batch(slots, trim), in one launch: the episode mask, `target_critic`

@@ -114,8 +114,9 @@ class TargetMixer(object):
         off, shape = self.layout[name]
         return self.packed[off:off + math.prod(shape)].view(shape)
 
-    def _pack(self):
-        p, S = self.params, self.state_dim
+    def _pack(self, params=None):
+        """params: the tensors to pack in place of self.params (mixers.TrainableMixer hands its parameters over with this)."""
+        p, S = self.params if params is None else params, self.state_dim
         w_in = self._view("w_in")
         for c, k, n in FIRST_LAYERS:
             w_in[:S, c:c + n].copy_(p[k + ".weight"].t())
